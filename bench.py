@@ -13,11 +13,16 @@ process touches HIP or torch; RANK/LOCAL_RANK/WORLD_SIZE/MASTER_* in their envir
 external launcher (torchrun sets RANK) the process is a rank straight away.  `--total-log-n K` is
 the strong-scaling mode of BASELINE config #5: 2^K points in total, 2^K / N per rank.
 
-Prints ONE JSON line on rank 0.  `roofline` is for the dominant kernel (msm_accumulate):
-achieved = 96 B/point (32 B scalar + 64 B affine base) x points per launch / the
-kernel's mean duration, measured live with HIP events on the library stream during the timed
-steps.  `cpu_baseline` times the CPU oracle (own C restatement, NOT arkworks) on a bounded sample
-of the same workload on this node's host cores.
+Prints ONE JSON line on rank 0.  A plain run does only what the headline needs: set-up, `--warmup`
+untimed steps, `--steps` timed steps, the outputs of the last step if `--dump-outputs DIR` is given,
+the line; its `roofline`, `cpu_baseline` are null and `extra` is empty.  `--full` adds everything
+else, as below.
+
+`--full`: `roofline` is for the dominant kernel (msm_accumulate): achieved = 96 B/point (32 B scalar
++ 64 B affine base) x points per launch / the kernel's mean duration, measured live
+with HIP events on the library stream during the timed steps.  `cpu_baseline` times the CPU oracle
+(own C restatement, NOT arkworks) on a bounded sample of the same workload on this node's host
+cores.  `extra` carries the NTT, the other sizes and scalar sets and the prover-shaped workloads.
 """
 from __future__ import annotations
 
@@ -219,7 +224,14 @@ def main() -> None:
     ap.add_argument("--no-ntt", action="store_true")
     ap.add_argument("--window-bits", type=int, default=0)
     ap.add_argument("--no-extras", action="store_true", help="skip the window-table and prover-shape extras")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline: kernel profile and rooflines, clocks, NTT, extras, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's commitment to DIR/msm_result_affine.npy "
+                         "(canonical affine x, y as 32-bit limbs, float64 [2, 8])")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "RANK" not in os.environ:
         # parent: no torch, no HIP -- only children touch the GPU
@@ -402,9 +414,27 @@ def _cpu_baseline_proof(oc, np, threads: int, reps: int = 2) -> dict:
                       f"best of {reps} passes; uniform scalars are the MSM's worst case (a real witness is mostly 0 / 1)"}
 
 
+FQ_MODULUS = 0x30644E72E131A029B85045B68181585D97816A916871CA8D3C208C16D87CFD47   # BN254 base field
+
+
+def _dump_outputs(out_dir: str, b, np, result) -> None:
+    """--dump-outputs: the commitment the last timed step returned (a Jacobian point, 12 x u64 Montgomery limbs) as the affine point it
+    stands for -- the Jacobian representative is not unique, the affine point is -- in canonical form, so that two builds compare output
+    for output.  out_dir/msm_result_affine.npy: float64 [2, 8] = (x, y), 32-bit limbs least significant first (exact in float64);
+    the point at infinity is all zeros."""
+    aff = b.g1_to_affine(result)                                   # x, y: 4 x u64 Montgomery limbs each
+    rinv = pow(1 << 256, -1, FQ_MODULUS)
+    rows = []
+    for coord in (aff[:4], aff[4:]):
+        v = sum(int(w) << (64 * i) for i, w in enumerate(coord)) * rinv % FQ_MODULUS
+        rows.append([(v >> (32 * i)) & 0xFFFFFFFF for i in range(8)])
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "msm_result_affine.npy"), np.array(rows, dtype=np.float64))
+
+
 def dry_run_rank(args, rank, world, dist, np) -> None:
     """--dry-run: the launcher, the rendezvous, the all-gather of 96-byte partials and the fold, with no GPU:
-    rank r contributes (r + 1) * G (built with the host-side fold of the C ABI)."""
+    rank r contributes (r + 1) * G (built with the host-side fold of the C ABI).  With --full also what a full N > 1 line adds."""
     import torch
     from uzkge_amd import backend as b
     one_q = np.array([0xd35d438dc58f0d9d, 0x0a78eb28f5c70b3d, 0x666ea36f7879462c, 0x0e0a77c19a07df2f], dtype=np.uint64)
@@ -414,28 +444,31 @@ def dry_run_rank(args, rank, world, dist, np) -> None:
     part = b.g1_fold(np.stack([g] * (rank + 1)))
     total = ShardedCommitter(None).exchange(part)                  # the product's exchange: all-gather + fold on every rank
     aff = b.g1_to_affine(total)
-    # the proofs-per-device extra of a real N > 1 run: every rank reports its own rate, rank 0 prints the sum (here: 100 (r + 1))
-    proofs = _gather_proofs(dist, world, {"rank": rank, "proofs_per_s": 100.0 * (rank + 1)})
+    # the proofs-per-device extra of a real N > 1 --full run: every rank reports its own rate, rank 0 prints the sum (here: 100 (r + 1))
+    proofs = _gather_proofs(dist, world, {"rank": rank, "proofs_per_s": 100.0 * (rank + 1)}) if args.full else None
     if rank == 0:
-        # the two objects an N > 1 line must carry, built by the SAME code as a real run while the other ranks wait at the barrier:
-        # cpu_baseline (the C port on the reference's 2^14-point Lagrange SRS here -- no device points exist) and roofline.alu
-        # (strong-scaling shape of config #5 on 8 GPUs: 2^23 points per GPU; nominal duration and clock, nothing was timed)
-        sys.path.insert(0, os.path.join(ROOT, "oracle"))
-        import bn254_py as opy
-        import oracle_c as oc   # checker / reported baseline only
-        with open(os.path.join(ROOT, "tests", "golden", "lagrange-srs-16384.bin"), "rb") as f:
-            hp = oc.points_from_affine(opy.parse_srs_g1(f.read()))
-        rng = np.random.default_rng(5)
-        hs = rng.integers(0, 1 << 62, size=(hp.shape[0], 4), dtype=np.uint64)
-        _, cpu_baseline = _cpu_baseline_msm(oc, hp, hs, _cpu_threads(world), world)
-        alu = _alu_roofline(1 << 23, 17, 15, 8.5, True, {"sclk_mhz_timed": 2050, "source": "dry run: nominal duration (8.5 ms) and clock, nothing was timed"})
-        alu.pop("_achieved")
+        roofline, cpu_baseline, extra = None, None, {}
+        if args.full:
+            # the two objects a full N > 1 line carries, built by the SAME code as a real run while the other ranks wait at the barrier:
+            # cpu_baseline (the C port on the reference's 2^14-point Lagrange SRS here -- no device points exist) and roofline.alu
+            # (strong-scaling shape of config #5 on 8 GPUs: 2^23 points per GPU; nominal duration and clock, nothing was timed)
+            sys.path.insert(0, os.path.join(ROOT, "oracle"))
+            import bn254_py as opy
+            import oracle_c as oc   # checker / reported baseline only
+            with open(os.path.join(ROOT, "tests", "golden", "lagrange-srs-16384.bin"), "rb") as f:
+                hp = oc.points_from_affine(opy.parse_srs_g1(f.read()))
+            rng = np.random.default_rng(5)
+            hs = rng.integers(0, 1 << 62, size=(hp.shape[0], 4), dtype=np.uint64)
+            _, cpu_baseline = _cpu_baseline_msm(oc, hp, hs, _cpu_threads(world), world)
+            alu = _alu_roofline(1 << 23, 17, 15, 8.5, True, {"sclk_mhz_timed": 2050, "source": "dry run: nominal duration (8.5 ms) and clock, nothing was timed"})
+            alu.pop("_achieved")
+            roofline = {"bound": "hbm", "kernel": "msm_accumulate", "alu": alu}
+            extra = {"proofs_per_device": proofs}
         print(json.dumps({"metric": "bn254_g1_msm_points_per_sec", "value": 0.0, "unit": "points/s", "n_gpus": world,
                           "dry_run": True, "dist_world_size": dist.get_world_size() if world > 1 else 1,
                           "fold_of_rank_partials_affine": [int(x) for x in aff],
                           "expect": f"{world * (world + 1) // 2} * G", "host_cores": _host_cores(),
-                          "roofline": {"bound": "hbm", "kernel": "msm_accumulate", "alu": alu}, "cpu_baseline": cpu_baseline,
-                          "extra": {"proofs_per_device": proofs}}))
+                          "roofline": roofline, "cpu_baseline": cpu_baseline, "extra": extra}))
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
@@ -539,15 +572,20 @@ def run_rank(args) -> None:
 
     for _ in range(args.warmup):
         step()
-    b.profile_reset()
-    b.profile_enable(True)
+    if args.full:       # kernel durations (HIP events on every launch) and clocks during the timed steps: for the rooflines
+        b.profile_reset()
+        b.profile_enable(True)
     committer.reset_clocks()
-    sampler = _ClockSampler(local_rank).start() if rank == 0 else None
+    sampler = _ClockSampler(local_rank).start() if rank == 0 and args.full else None
     t_local = time.perf_counter()
     elapsed, local_elapsed, result = timed_steps(step, args.steps)     # local_elapsed: this rank's own clock, taken BEFORE the MAX all-reduce
     clocks_timed = sampler.stop(t_local, t_local + local_elapsed) if sampler else None
-    b.profile_enable(False)
-    prof = b.profile_table()
+    prof = {}
+    if args.full:
+        b.profile_enable(False)
+        prof = b.profile_table()
+    if args.dump_outputs and rank == 0:
+        _dump_outputs(args.dump_outputs, b, np, result)
     # per-rank view of the timed region, so that a multi-GPU run explains itself: every rank's ms per step, its MSM share and
     # its exchange share (all-gather of the 96-byte partials + fold; expected << 0.1 ms, i.e. flat weak scaling)
     mine = {"rank": rank, "ms_per_step": round(local_elapsed / args.steps * 1e3, 4), "msm_ms_per_step": round(committer.msm_s / args.steps * 1e3, 4),
@@ -570,55 +608,55 @@ def run_rank(args) -> None:
         dev_ids = [o[0] for o in objs]
         dev_uuids = [o[1] for o in objs]
 
-    acc_cnt, acc_ms = prof.get("msm_accumulate", (0, 0.0))
-    acc_avg_ms = acc_ms / max(acc_cnt, 1)
-    achieved = (96.0 * n) / (acc_avg_ms * 1e-3) / 1e9 if acc_cnt else 0.0
-    # HBM bytes per launch: rocprofv3 PMC passes summarised in profiles/pmc_traffic.json, used only when that file
-    # was measured on the kernel sources of this tree (it records their hash) and on this configuration
-    traffic, traffic_note = None, None
-    pmc, why = _load_counters("pmc_traffic.json")
-    if pmc is None:
-        traffic_note = why
-    else:
-        ent = pmc.get("msm_accumulate", {}).get(str(n.bit_length() - 1))
-        if ent and args.points == "random" and not args.window_bits and args.scalars == "uniform" and n & (n - 1) == 0:
-            traffic = ent["traffic_bytes"]
+    roofline, pmc, alu_achieved, extra = None, None, 0.0, {}
+    if args.full:
+        acc_cnt, acc_ms = prof.get("msm_accumulate", (0, 0.0))
+        acc_avg_ms = acc_ms / max(acc_cnt, 1)
+        achieved = (96.0 * n) / (acc_avg_ms * 1e-3) / 1e9 if acc_cnt else 0.0
+        # HBM bytes per launch: rocprofv3 PMC passes summarised in profiles/pmc_traffic.json, used only when that file
+        # was measured on the kernel sources of this tree (it records their hash) and on this configuration
+        traffic, traffic_note = None, None
+        pmc, why = _load_counters("pmc_traffic.json")
+        if pmc is None:
+            traffic_note = why
         else:
-            traffic_note = "no PMC pass for this configuration"
-    # The kernel's real bound is vector-instruction issue (_alu_roofline): ~2090 vector instructions per mixed addition, 1467 of
-    # them v_mad_u64_u32 (ec29.hpp), counted by the SQ pass of the same kernel; the achieved rate uses THIS run's mean duration.
-    cbits, nwin = (args.window_bits, 0)
-    try:
-        cbits, nwin = b.msm_plan_info(n)
-    except Exception:
-        pass
-    plain = args.scalars == "uniform" and not args.window_bits and n & (n - 1) == 0 and n >= (1 << 21)     # the c = 17 plan of the counted launch
-    alu = _alu_roofline(n, cbits, nwin, acc_avg_ms if acc_cnt else 0.0, plain, clocks_timed)
-    alu_achieved = alu.pop("_achieved")
-    roofline = {
-        "bound": "hbm", "kernel": "msm_accumulate", "achieved": round(achieved, 3), "peak": HBM_PEAK_GBS,
-        "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 6), "traffic": traffic,
-        "avg_launch_ms": round(acc_avg_ms, 4), "algorithmic_bytes_per_launch": 96 * n,
-        "alu": alu,
-        "note": "vector-issue bound (254-bit modular arithmetic, ~2090 instructions per mixed addition), not HBM bound: `alu` is the "
-                "binding roofline, `frac` the HBM one the contract asks for; see DESIGN.md 3.1",
-    }
-    if traffic_note:
-        roofline["traffic_note"] = traffic_note
-    # device kernels (HIP events) and, prefixed host_, the host-side sections of the call (wall clock)
-    kernels = {k: {"launches": v[0], "avg_ms": round(v[1] / max(v[0], 1), 4)} for k, v in sorted(prof.items())}
-
-    extra = {"msm_kernels": kernels}
-    solo = rank == 0 and world == 1 and not args.no_extras
+            ent = pmc.get("msm_accumulate", {}).get(str(n.bit_length() - 1))
+            if ent and args.points == "random" and not args.window_bits and args.scalars == "uniform" and n & (n - 1) == 0:
+                traffic = ent["traffic_bytes"]
+            else:
+                traffic_note = "no PMC pass for this configuration"
+        # The kernel's real bound is vector-instruction issue (_alu_roofline): ~2090 vector instructions per mixed addition, 1467 of
+        # them v_mad_u64_u32 (ec29.hpp), counted by the SQ pass of the same kernel; the achieved rate uses THIS run's mean duration.
+        cbits, nwin = (args.window_bits, 0)
+        try:
+            cbits, nwin = b.msm_plan_info(n)
+        except Exception:
+            pass
+        plain = args.scalars == "uniform" and not args.window_bits and n & (n - 1) == 0 and n >= (1 << 21)     # the c = 17 plan of the counted launch
+        alu = _alu_roofline(n, cbits, nwin, acc_avg_ms if acc_cnt else 0.0, plain, clocks_timed)
+        alu_achieved = alu.pop("_achieved")
+        roofline = {
+            "bound": "hbm", "kernel": "msm_accumulate", "achieved": round(achieved, 3), "peak": HBM_PEAK_GBS,
+            "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 6), "traffic": traffic,
+            "avg_launch_ms": round(acc_avg_ms, 4), "algorithmic_bytes_per_launch": 96 * n,
+            "alu": alu,
+            "note": "vector-issue bound (254-bit modular arithmetic, ~2090 instructions per mixed addition), not HBM bound: `alu` is the "
+                    "binding roofline, `frac` the HBM one the contract asks for; see DESIGN.md 3.1",
+        }
+        if traffic_note:
+            roofline["traffic_note"] = traffic_note
+        # device kernels (HIP events) and, prefixed host_, the host-side sections of the call (wall clock)
+        extra["msm_kernels"] = {k: {"launches": v[0], "avg_ms": round(v[1] / max(v[0], 1), 4)} for k, v in sorted(prof.items())}
+    solo = args.full and rank == 0 and world == 1 and not args.no_extras
 
     # ---- BASELINE config #5 next to the weak-scaling headline: 2^26 points in total, split over the ranks ------
-    if world > 1 and not strong and not args.no_extras and  (1 << 26) // world <= n:
+    if args.full and world > 1 and not strong and not args.no_extras and (1 << 26) // world <= n:
         m5 = (1 << 26) // world
 
         def step5():
             return committer.commit_device(sc.data_ptr(), m5)
         step5()
-        el5, _ = timed_steps(step5, max(3, args.steps // 2))
+        el5, _, _ = timed_steps(step5, max(3, args.steps // 2))
         extra["strong_2p26"] = {"what": "BASELINE config #5: 2^26 points in total, point-chunk sharded over the ranks, "
                                         "RCCL all-gather of the partial sums, fold on every rank",
                                 "points_per_gpu": m5, "total_points": m5 * world, "steps": max(3, args.steps // 2),
@@ -626,7 +664,7 @@ def run_rank(args) -> None:
                                 "value": m5 * world * max(3, args.steps // 2) / el5, "unit": "points/s", "scaling": "strong"}
 
     # ---- proofs per second, one prover process per device (the realistic scaling mode at n = 2^14) --------
-    if world > 1 and not args.no_extras:
+    if args.full and world > 1 and not args.no_extras:
         # host threads per rank: the reference's call pattern needs a caller thread per proof in flight; 32 per device when the host
         # has them, never more than twice this rank's share of the CPUs the job may use (8 ranks x 32 threads on a 16-CPU grant would
         # measure the host, not the GPUs) -- the line prints the host budget beside the rate
@@ -645,7 +683,7 @@ def run_rank(args) -> None:
             extra["proofs_per_s_total"] = proofs["proofs_per_s_total"]
 
     # ---- NTT 2^22 (single GPU path; replicas only under N > 1) --------------------------------
-    if not args.no_ntt and rank == 0:
+    if args.full and not args.no_ntt and rank == 0:
         nn = 1 << args.ntt_log_n
         x = torch.empty((nn, 4), dtype=torch.int64, device=dev)
         y = torch.empty((nn, 4), dtype=torch.int64, device=dev)
@@ -970,7 +1008,7 @@ def run_rank(args) -> None:
 
     # ---- CPU baseline + parity on a bounded sample (rank 0; under N > 1 the other ranks wait at the closing barrier) ----------
     cpu_baseline = None
-    if rank == 0 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and not args.no_cpu_baseline:
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
         import oracle_c as oc   # checker / reported baseline only
 

@@ -27,7 +27,7 @@ def _run(args, env_extra=None, timeout=240):
 
 @pytest.mark.parametrize("world", [2, 3])
 def test_gpus_flag_spawns_that_many_ranks(world):
-    r = _run(["--gpus", str(world), "--dry-run"])
+    r = _run(["--gpus", str(world), "--dry-run", "--full"])
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, "exactly one JSON line, from rank 0"
@@ -61,6 +61,13 @@ def test_a_failing_rank_fails_the_launcher():
     if b.device_count() > 0:
         pytest.skip("GPU present: the ranks succeed")
     assert r.returncode != 0
+    assert not [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+
+
+def test_steps_below_one_are_refused():
+    # --steps is the number of timed steps and ms_per_step is divided by it
+    r = _run(["--steps", "0", "--dry-run"])
+    assert r.returncode == 2 and "--steps" in r.stderr
     assert not [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
 
 

@@ -25,7 +25,7 @@ sha = bench._kernel_sources_sha()
 fetch, write, sq, grbm = table("fetch_size"), table("write_size"), table("sq"), table("grbm")
 KIB = 1024.0
 traffic = {"_doc": "HBM traffic per launch from rocprofv3 PMC passes (separate --pmc FETCH_SIZE / --pmc WRITE_SIZE runs of `python3 bench.py "
-                   "--steps 1 --warmup 0 --no-cpu-baseline --no-extras`; tools/profile_round.sh). FETCH_SIZE / WRITE_SIZE are KiB. gfx950 correction "
+                   "--full --steps 1 --warmup 0 --no-cpu-baseline --no-extras`; tools/profile_round.sh). FETCH_SIZE / WRITE_SIZE are KiB. gfx950 correction "
                    "(MI355X_MICROARCH.md, HBM): FETCH_SIZE reads 1/2 of a coalesced 16 B/lane stream -> x2 for the NTT passes; the bucket accumulation is "
                    "dominated by 64-byte gathers, for which the calibration of round 1 (tools/microbench/gather_calib.hip, "
                    "profiles/r01e_pmc_fetch_size_calibration.csv) measured a factor of 1.003 -> x1. WRITE_SIZE is exact.",

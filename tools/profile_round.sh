@@ -1,7 +1,7 @@
 #!/bin/bash
 # Round-end measurement set, run on the GPU box from the repo root:
 #   bash tools/profile_round.sh r02a
-# 1. bench.py (default flags)                         -> gpurun_out/<tag>_bench.json
+# 1. bench.py --full (every measurement it has)       -> <tag>_bench.json in the output directory below
 # 2. rocprofv3 --kernel-trace --stats of bench.py     -> gpurun_out/<tag>_kernel_stats.csv
 # 3. rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE    -> gpurun_out/<tag>_pmc_{fetch,write}_size.csv
 # 4. rocprofv3 --pmc <8 SQ counters> / GRBM           -> gpurun_out/<tag>_pmc_sq.csv, _pmc_grbm.csv
@@ -15,17 +15,17 @@ tag=${1:-rXX}
 out=gpurun_out
 mkdir -p $out
 export TMPDIR=/tmp
-python3 bench.py > $out/${tag}_bench.json 2> $out/${tag}_bench.err || { tail -5 $out/${tag}_bench.err; exit 1; }
+python3 bench.py --full > $out/${tag}_bench.json 2> $out/${tag}_bench.err || { tail -5 $out/${tag}_bench.err; exit 1; }
 echo "bench done"; cut -c1-400 $out/${tag}_bench.json
 rm -rf $out/prof_stats
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof_stats -- python3 bench.py --no-cpu-baseline --no-extras > $out/${tag}_bench_under_rocprof.json 2> $out/${tag}_rocprof.err || { tail -5 $out/${tag}_rocprof.err; exit 1; }
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof_stats -- python3 bench.py --full --no-cpu-baseline --no-extras > $out/${tag}_bench_under_rocprof.json 2> $out/${tag}_rocprof.err || { tail -5 $out/${tag}_rocprof.err; exit 1; }
 cp "$(find $out/prof_stats -name '*kernel_stats.csv' | head -1)" $out/${tag}_kernel_stats.csv
 rm -rf $out/prof_stats
 echo "kernel stats done"
 pmc_pass() {   # name, counters...
     local name=$1; shift
     rm -rf $out/prof_pmc
-    rocprofv3 --pmc "$@" --output-format csv -d $out/prof_pmc -- python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-extras > /dev/null 2> $out/${tag}_pmc_${name}.err || { tail -5 $out/${tag}_pmc_${name}.err; return 1; }
+    rocprofv3 --pmc "$@" --output-format csv -d $out/prof_pmc -- python3 bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-extras > /dev/null 2> $out/${tag}_pmc_${name}.err || { tail -5 $out/${tag}_pmc_${name}.err; return 1; }
     python3 tools/pmc_summary.py "$(find $out/prof_pmc -name '*counter_collection.csv' | head -1)" > $out/${tag}_pmc_${name}.csv
     rm -rf $out/prof_pmc
     echo "pmc $name done"
@@ -39,5 +39,5 @@ python3 tools/make_counter_files.py $tag && echo "counter files written" || exit
 #    <tag>_bench.json, <tag>_kernel_stats.csv and the counter passes all come from one machine and one binary
 cp $out/${tag}_pmc_traffic.json profiles/pmc_traffic.json && cp $out/${tag}_sq_counters.json profiles/sq_counters.json || exit 1
 mv $out/${tag}_bench.json $out/${tag}_bench_first.json
-python3 bench.py > $out/${tag}_bench.json 2> $out/${tag}_bench.err || { tail -5 $out/${tag}_bench.err; exit 1; }
+python3 bench.py --full > $out/${tag}_bench.json 2> $out/${tag}_bench.err || { tail -5 $out/${tag}_bench.err; exit 1; }
 echo "bench of record done"; cut -c1-300 $out/${tag}_bench.json
