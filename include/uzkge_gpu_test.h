@@ -30,6 +30,27 @@ int uzk_test_field_kat(int field, int op, const uint64_t* a, const uint64_t* b, 
  * Inputs affine (infinity = zeros), outputs Jacobian. */
 int uzk_test_g1_kat(int op, const uzk_g1_affine* a, const uzk_g1_affine* b, uzk_g1_jac* out, size_t n);
 
+/* ---- raw 9 x 29-bit limbs: the primitives of the hot loops (fp29.hpp) and the typed lazy operations (lz29.hpp) at their bounds ----
+ * in: n records of four operands a, b, c, d, 9 limbs (uint32) each, taken EXACTLY as given; out: n x 9 words, the raw result (no
+ * canon); an 8-word result (to_fp*, canon of lz29.hpp, to_wire) in words 0..7 with word 8 = 0.  field: 0 = Fq, 1 = Fr.  op:
+ * 0 mul(a, b), 1 sqr(a), 2 mul2(a, b, c, d) (generated assembly); 3..5 the same three in C++ (mul_cpp, sqr_cpp, mul2_cpp);
+ * 6 mulc(a, w = b, wq_of(w)) (b canonical), 7 mulcs with ONE wave-uniform w = record 0's b; 8 add(a, b), 9 norm(a), 10 norm1(a),
+ * 11 reduce(a), 12 reduce3(a), 13 canon(a), 14 to_fp(a), 15 to_fp_div<5>(a), 16 to_fp_div<10>(a), 17..19 sub<4 | 8 | 12>(a, b),
+ * 20 sub_off(a, b, OFF) with param 0..5 = OFF4, OFF8, OFF12, OFF4T3, OFF2T1, OFF8T1; 21 the typed operation of signature `param`
+ * of uzkge_amd/csrc/lz29_sigs.inc (its sub, to_wire or canon entries of this field); 22 reduce(from_fp_x32(words a.l[0..7]))
+ * (what the MSM accumulator does to a loaded coordinate). */
+int uzk_test_l29_kat(int field, int op, uint32_t param, const uint32_t* in, uint32_t* out, size_t n);
+/* The lazy XYZZ additions of ec29l.hpp on raw coordinate limbs: record i of in is two points a, b (x, y, zz, zzz; 9 limbs each, 72
+ * words), out[i] the raw result (36 words).  op: 0 a + b (p29_add), 1 2a (p29_dbl), 2 / 3 the same by the four lanes of a quad. */
+int uzk_test_p29_kat(int op, const uint32_t* in, uint32_t* out, size_t n);
+/* The prover's lane kernels (rounds.hip) on device polynomials: polynomial k of lane b holds its coefficients (wire elements) at
+ * d_polys[k] + b * lane_strides[k] elements.  op 0, linear combination: lens[lanes][count] lengths, args[lanes][count] scalars,
+ * out[lanes][len] = sum_k args[b][k] p_k,b (len = out_len).  op 1, evaluation: lens[count] lengths (every lane's), pts[count]
+ * in {0, 1}, args[lanes][2] points, out[lanes][count] = p_k,b(args[b][pts[k]]) (len = max_len, 1 .. 2^18).  *kernel: bit 0 set
+ * when the lazy 29-bit kernel ran, bit 1 when the wide one did (GS = 4 lanes per coefficient / PER = 16 per lane). */
+int uzk_test_lanes(int op, const void* const* d_polys, const uint64_t* lane_strides, uint32_t count, const uint32_t* lens, const uint32_t* pts,
+                   const uint64_t* args, uint32_t lanes, uint64_t len, uint64_t* out, int* kernel);
+
 /* ---- synthetic circuits ----
  * TEST / TIMING ONLY -- changes results.  Marks the circuit as synthetic (random polynomials no witness satisfies, the frozen
  * parity vectors and the timing chains): round 3 then takes t as its first 5 n - 2 + sum(hiding) coefficients, as

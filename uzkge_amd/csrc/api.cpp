@@ -1162,6 +1162,33 @@ int uzk_test_g1_kat(int op, const uzk_g1_affine* a, const uzk_g1_affine* b, uzk_
                         reinterpret_cast<Jac*>(out), n);
 } catch (...) { return uzk::on_exception("uzk_test_g1_kat"); }
 
+int uzk_test_l29_kat(int field, int op, uint32_t param, const uint32_t* in, uint32_t* out, size_t n) try {
+    API_LOCK;
+    if (n > 0 && (!in || !out)) { set_error("uzk_test_l29_kat: null pointer"); return UZK_ERR_PARAMETER; }
+    if (field < 0 || field > 1 || op < 0 || op > 22) { set_error("uzk_test_l29_kat: bad field/op"); return UZK_ERR_PARAMETER; }
+    if (op == 20 && param > 5) { set_error("uzk_test_l29_kat: sub_off takes offsets 0 .. 5"); return UZK_ERR_PARAMETER; }
+    if (op == 21 && !l29_sig_runnable(field, param)) { set_error("uzk_test_l29_kat: not a sub / to_wire / canon signature of this field"); return UZK_ERR_PARAMETER; }
+    UZK_TRY(require_ready());
+    return l29_op_device(ctx(), field, op, param, in, out, n);
+} catch (...) { return uzk::on_exception("uzk_test_l29_kat"); }
+int uzk_test_p29_kat(int op, const uint32_t* in, uint32_t* out, size_t n) try {
+    API_LOCK;
+    if (n > 0 && (!in || !out)) { set_error("uzk_test_p29_kat: null pointer"); return UZK_ERR_PARAMETER; }
+    if (op < 0 || op > 3) { set_error("uzk_test_p29_kat: bad op"); return UZK_ERR_PARAMETER; }
+    UZK_TRY(require_ready());
+    return p29_op_device(ctx(), op, in, out, n);
+} catch (...) { return uzk::on_exception("uzk_test_p29_kat"); }
+int uzk_test_lanes(int op, const void* const* d_polys, const uint64_t* lane_strides, uint32_t count, const uint32_t* lens, const uint32_t* pts,
+                   const uint64_t* args, uint32_t lanes, uint64_t len, uint64_t* out, int* kernel) try {
+    API_LOCK;
+    if (op < 0 || op > 1 || count == 0 || lanes == 0 || !kernel) { set_error("uzk_test_lanes: bad op / count / lanes"); return UZK_ERR_PARAMETER; }
+    if (!d_polys || !lane_strides || !lens || !args || !out || (op == 1 && !pts)) { set_error("uzk_test_lanes: null pointer"); return UZK_ERR_PARAMETER; }
+    for (uint32_t k = 0; k < count; ++k)
+        if (!d_polys[k] || (op == 1 && pts[k] > 1)) { set_error("uzk_test_lanes: null polynomial or point index > 1"); return UZK_ERR_PARAMETER; }
+    UZK_TRY(require_ready());
+    return lanes_test(ctx(), op, d_polys, lane_strides, count, lens, pts, as_fp(args), lanes, len, reinterpret_cast<Fp*>(out), kernel);
+} catch (...) { return uzk::on_exception("uzk_test_lanes"); }
+
 /* ---- measurement -------------------------------------------------------------------------- */
 int uzk_profile_enable(int on) try {
     API_LOCK;

@@ -288,5 +288,15 @@ int z_poly_run(Ctx& c, const Fp* w_host, const uint32_t* perm_host, const Fp* gr
 void poly_free(Ctx& c);
 int field_op_device(Ctx& c, int field, int op, const Fp* a, const Fp* b, Fp* out, size_t n);
 int g1_op_device(Ctx& c, int op, const Affine* a, const Affine* b, Jac* out, size_t n);
+// raw 9-limb known answers (fieldops.hip; include/uzkge_gpu_test.h uzk_test_l29_kat / uzk_test_p29_kat)
+bool l29_sig_runnable(int field, uint32_t idx);
+int l29_op_device(Ctx& c, int field, int op, uint32_t param, const uint32_t* in, uint32_t* out, size_t n);
+int p29_op_device(Ctx& c, int op, const uint32_t* in, uint32_t* out, size_t n);
+// which lane kernel runs (rounds.hip): the launchers and the test hook uzk_test_lanes share the choice
+struct LaneKernel { bool a29, wide; };
+LaneKernel poly_eval_lanes_kernel_of(const Ctx& c, uint32_t lanes, uint64_t max_len);
+LaneKernel poly_lincomb_lanes_kernel_of(const Ctx& c, uint32_t count, uint64_t out_len);
+int lanes_test(Ctx& c, int op, const void* const* d_polys, const uint64_t* lane_strides, uint32_t count, const uint32_t* lens, const uint32_t* pts,
+               const Fp* args, uint32_t lanes, uint64_t len, Fp* out, int* kernel);
 
 }  // namespace uzk

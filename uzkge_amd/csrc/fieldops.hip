@@ -1,6 +1,8 @@
 // Element-wise known-answer entry points: run the DEVICE field / group primitives on host arrays so
 // tests can compare them word-for-word with the oracle (Fq/Fr mont-mul/add/sub KATs, G1
 // add / double / mixed-add including P+P, P+(-P) and infinity; SURVEY.md 8c "golden vectors").
+#include <type_traits>
+
 #include "ctx.hpp"
 #include "ecquad.hpp"
 #include "ecquad29.hpp"
@@ -218,52 +220,218 @@ __global__ __launch_bounds__(256) void g1_p29_op_kernel(int op, const Affine* __
     const size_t gt = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     const size_t i = quad ? gt >> 2 : gt;
     const uint32_t q = (uint32_t)(gt & 3);
-    if (i >= n) return;
-    const Affine p = a[i], r = b[i];
-    XYZZ s = xyzz_from_affine(p), t = xyzz_from_affine(r);
+    const bool live = i < n;                             // no early return: the quad path below has a barrier
     const int f = quad ? op - 18 : op - 14;
     auto add = [&](P29& x, const P29& y) { if (quad) p29_add_quad(x, y, q); else p29_add(x, y); };
-    P29 acc;
-    if (f == 0) {
-        acc = p29_load(s);
-        add(acc, p29_load(t));
-    } else if (f == 1) {
-        xyzz_madd(s, r, false);
-        acc = p29_load(s);
-        const P29 same = acc;
-        add(acc, same);
-    } else if (f == 2) {
-        XYZZ u = s;
-        xyzz_madd(s, r, false);
-        xyzz_madd(u, r, true);
-        acc = p29_load(s);
-        add(acc, p29_load(u));
-    } else {
-        XYZZ u = s;
-        xyzz_madd(u, r, false);                          // a + b
-        XYZZ v = u;
-        v.y = Fq::neg(v.y);                              // -(a + b), same ZZ / ZZZ
-        acc = p29_load(u);
-        add(acc, p29_load(v));                           // infinity
-        add(acc, p29_load(s));                           // + a
-        P29 w = p29_load(t);
-        add(w, p29_inf());                               // b + infinity
-        add(acc, w);                                     // a + b
+    P29 acc = p29_inf();
+    if (live) {
+        const Affine p = a[i], r = b[i];
+        XYZZ s = xyzz_from_affine(p), t = xyzz_from_affine(r);
+        if (f == 0) {
+            acc = p29_load(s);
+            add(acc, p29_load(t));
+        } else if (f == 1) {
+            xyzz_madd(s, r, false);
+            acc = p29_load(s);
+            const P29 same = acc;
+            add(acc, same);
+        } else if (f == 2) {
+            XYZZ u = s;
+            xyzz_madd(s, r, false);
+            xyzz_madd(u, r, true);
+            acc = p29_load(s);
+            add(acc, p29_load(u));
+        } else {
+            XYZZ u = s;
+            xyzz_madd(u, r, false);                          // a + b
+            XYZZ v = u;
+            v.y = Fq::neg(v.y);                              // -(a + b), same ZZ / ZZZ
+            acc = p29_load(u);
+            add(acc, p29_load(v));                           // infinity
+            add(acc, p29_load(s));                           // + a
+            P29 w = p29_load(t);
+            add(w, p29_inf());                               // b + infinity
+            add(acc, w);                                     // a + b
+        }
     }
     if (quad) {
-        const Fp c = p29_is_inf(acc) ? Fq::zero() : p29_coord_to_fp(acc, q);
+        const Fp c = !live || p29_is_inf(acc) ? Fq::zero() : p29_coord_to_fp(acc, q);
         __shared__ Fp sh[64][4];
         sh[threadIdx.x >> 2][q] = c;
         __syncthreads();
-        if (q == 0) {
+        if (live && q == 0) {
             XYZZ o;
             o.x = sh[threadIdx.x >> 2][0]; o.y = sh[threadIdx.x >> 2][1]; o.zz = sh[threadIdx.x >> 2][2]; o.zzz = sh[threadIdx.x >> 2][3];
             out[i] = xyzz_to_jac(o);
         }
-    } else {
+    } else if (live) {
         out[i] = xyzz_to_jac(p29_store(acc));
     }
 #endif
+}
+
+// ---- raw 9-limb known-answer entry points (uzk_test_l29_kat, uzk_test_p29_kat) -------------------------------------------------
+// The primitives of fp29.hpp and the typed operations of lz29.hpp applied to limbs EXACTLY as given (no re-limbing, no canon on the
+// way out), so that tests can drive every operation to the edges of its stated contract and check the raw result against it.
+// Record i of `in` holds four operands a, b, c, d of 9 limbs each; out[i] is the raw result (8-word results in l[0..7], l[8] = 0).
+#define LZ29_FIELD_FQ 0
+#define LZ29_FIELD_FR 1
+#define LZ29_TYPE_FQ Fq29
+#define LZ29_TYPE_FR Fr29
+enum { LZ29_KIND_add, LZ29_KIND_sub, LZ29_KIND_mul, LZ29_KIND_sqr, LZ29_KIND_mul2, LZ29_KIND_norm, LZ29_KIND_assume, LZ29_KIND_canon,
+       LZ29_KIND_to_wire };
+struct Lz29SigInfo { int field, kind; };
+static const Lz29SigInfo kLz29Sigs[] = {
+#define LZ29_SIG(idx, fld, op, ar, ka, va, kb, vb, kc, vc, kd, vd, kr, vr) {LZ29_FIELD_##fld, LZ29_KIND_##op},
+#include "lz29_sigs.inc"
+#undef LZ29_SIG
+};
+// the typed operations whose code depends on the type parameters: sub (its Off29 constant), to_wire (its branch), canon
+bool l29_sig_runnable(int field, uint32_t idx) {
+    if (idx >= sizeof(kLz29Sigs) / sizeof(kLz29Sigs[0])) return false;
+    const Lz29SigInfo& s = kLz29Sigs[idx];
+    return s.field == field && (s.kind == LZ29_KIND_sub || s.kind == LZ29_KIND_to_wire || s.kind == LZ29_KIND_canon);
+}
+
+#if defined(__HIP_DEVICE_COMPILE__)
+__device__ __forceinline__ L29 l29_words(const Fp& w) {
+    L29 r;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) r.l[k] = w.v[k];
+    r.l[8] = 0;
+    return r;
+}
+template <class F, int Ka, int Va, int Kb, int Vb> __device__ __forceinline__ L29 sig_sub(const L29& a, const L29& b) {
+    Lz<F, Ka, Va> x; Lz<F, Kb, Vb> y; x.v = a; y.v = b;
+    return LzOps<F>::sub(x, y).v;
+}
+template <class F, int K, int V> __device__ __forceinline__ L29 sig_to_wire(const L29& a) { Lz<F, K, V> x; x.v = a; return l29_words(LzOps<F>::to_wire(x)); }
+template <class F, int K, int V> __device__ __forceinline__ L29 sig_canon(const L29& a) { Lz<F, K, V> x; x.v = a; return l29_words(LzOps<F>::canon(x)); }
+#endif
+
+template <class F>
+__global__ __launch_bounds__(256) void l29_op_kernel(int op, uint32_t param, const L29* __restrict__ in, L29* __restrict__ out, size_t n) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const L29 a = in[4 * i], b = in[4 * i + 1], c = in[4 * i + 2], d = in[4 * i + 3];
+    L29 r = F::zero();
+    switch (op) {
+        case 0: r = F::mul(a, b); break;
+        case 1: r = F::sqr(a); break;
+        case 2: r = F::mul2(a, b, c, d); break;
+        case 3: r = F::mul_cpp(a, b); break;
+        case 4: r = F::sqr_cpp(a); break;
+        case 5: r = F::mul2_cpp(a, b, c, d); break;
+        case 6: r = F::mulc(a, b, F::wq_of(b)); break;                               // b: canonical plain w
+        case 7: {                                                                     // one wave-uniform w: record 0's b
+            const L29 w = F::uniform(in[1]);
+            r = F::mulcs(a, w, F::uniform(F::wq_of(w)));
+        } break;
+        case 8: r = F::add(a, b); break;
+        case 9: r = F::norm(a); break;
+        case 10: r = F::norm1(a); break;
+        case 11: r = F::reduce(a); break;
+        case 12: r = F::reduce3(a); break;
+        case 13: r = F::canon(a); break;
+        case 14: r = l29_words(F::to_fp(a)); break;
+        case 15: r = l29_words(F::template to_fp_div<5>(a)); break;
+        case 16: r = l29_words(F::template to_fp_div<10>(a)); break;
+        case 17: r = F::template sub<4>(a, b); break;
+        case 18: r = F::template sub<8>(a, b); break;
+        case 19: r = F::template sub<12>(a, b); break;
+        case 20: {                                                                    // sub_off with the named offset `param`
+            using C = typename F::Cfg;
+            switch (param) {
+                case 0: r = F::sub_off(a, b, C::OFF4); break;
+                case 1: r = F::sub_off(a, b, C::OFF8); break;
+                case 2: r = F::sub_off(a, b, C::OFF12); break;
+                case 3: r = F::sub_off(a, b, C::OFF4T3); break;
+                case 4: r = F::sub_off(a, b, C::OFF2T1); break;
+                default: r = F::sub_off(a, b, C::OFF8T1); break;
+            }
+        } break;
+        case 21: {                                                                    // the inventoried typed signature `param`
+            switch (param) {
+#define LZ29_RUN(fld, body) if constexpr (std::is_same<F, LZ29_TYPE_##fld>::value) { r = body; }
+#define LZ29_RUN_sub(idx, fld, ka, va, kb, vb) case idx: LZ29_RUN(fld, (sig_sub<F, ka, va, kb, vb>(a, b))) break;
+#define LZ29_RUN_to_wire(idx, fld, ka, va, kb, vb) case idx: LZ29_RUN(fld, (sig_to_wire<F, ka, va>(a))) break;
+#define LZ29_RUN_canon(idx, fld, ka, va, kb, vb) case idx: LZ29_RUN(fld, (sig_canon<F, ka, va>(a))) break;
+#define LZ29_RUN_add(...)
+#define LZ29_RUN_mul(...)
+#define LZ29_RUN_sqr(...)
+#define LZ29_RUN_mul2(...)
+#define LZ29_RUN_norm(...)
+#define LZ29_RUN_assume(...)
+#define LZ29_SIG(idx, fld, op, ar, ka, va, kb, vb, kc, vc, kd, vd, kr, vr) LZ29_RUN_##op(idx, fld, ka, va, kb, vb)
+#include "lz29_sigs.inc"
+#undef LZ29_SIG
+                default: break;
+            }
+        } break;
+        case 22: r = F::reduce(F::from_fp_x32(*reinterpret_cast<const Fp*>(&a))); break;   // acc29_set's step: a.l[0..7] are wire words
+        default: break;
+    }
+    out[i] = r;
+#endif
+}
+
+int l29_op_device(Ctx& c, int field, int op, uint32_t param, const uint32_t* in, uint32_t* out, size_t n) {
+    if (n == 0) return UZK_OK;
+    L29 *din = nullptr, *dout = nullptr;
+    UZK_HIP(hipMalloc(reinterpret_cast<void**>(&din), 4 * n * sizeof(L29)));
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&dout), n * sizeof(L29));
+    if (e == hipSuccess) e = hipMemcpyAsync(din, in, 4 * n * sizeof(L29), hipMemcpyHostToDevice, c.stream);
+    if (e == hipSuccess) {
+        const unsigned grid = (unsigned)((n + 255) / 256);
+        if (field == 0) hipLaunchKernelGGL(l29_op_kernel<Fq29>, dim3(grid), dim3(256), 0, c.stream, op, param, din, dout, n);
+        else hipLaunchKernelGGL(l29_op_kernel<Fr29>, dim3(grid), dim3(256), 0, c.stream, op, param, din, dout, n);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(out, dout, n * sizeof(L29), hipMemcpyDeviceToHost, c.stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c.stream);
+    if (din) (void)hipFree(din);
+    if (dout) (void)hipFree(dout);
+    UZK_HIP(e);
+    return UZK_OK;
+}
+
+// ec29l.hpp's additions on raw coordinate limbs: record i of `in` is two P29 (a, then b: x, y, zz, zzz), out[i] the raw P29 result.
+// op 0 a + b (p29_add), 1 2a (p29_dbl), 2 / 3 the same by the four lanes of a quad (lane 0's result).
+__global__ __launch_bounds__(256) void p29_op_kernel(int op, const P29* __restrict__ in, P29* __restrict__ out, size_t n) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    const bool quad = op >= 2;
+    const size_t gt = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t i = quad ? gt >> 2 : gt;
+    const uint32_t q = (uint32_t)(gt & 3);
+    if (i >= n) return;                              // whole quads leave together (4 n threads, blocks of 256); no barrier below
+    P29 acc = in[2 * i];
+    const P29 p = in[2 * i + 1];
+    if (op == 0) p29_add(acc, p);
+    else if (op == 1) p29_dbl(acc);
+    else if (op == 2) p29_add_quad(acc, p, q);
+    else p29_dbl_quad(acc, q);
+    if (!quad || q == 0) out[i] = acc;
+#endif
+}
+
+int p29_op_device(Ctx& c, int op, const uint32_t* in, uint32_t* out, size_t n) {
+    if (n == 0) return UZK_OK;
+    P29 *din = nullptr, *dout = nullptr;
+    UZK_HIP(hipMalloc(reinterpret_cast<void**>(&din), 2 * n * sizeof(P29)));
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&dout), n * sizeof(P29));
+    if (e == hipSuccess) e = hipMemcpyAsync(din, in, 2 * n * sizeof(P29), hipMemcpyHostToDevice, c.stream);
+    if (e == hipSuccess) {
+        const size_t threads = op >= 2 ? 4 * n : n;
+        hipLaunchKernelGGL(p29_op_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, c.stream, op, din, dout, n);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(out, dout, n * sizeof(P29), hipMemcpyDeviceToHost, c.stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c.stream);
+    if (din) (void)hipFree(din);
+    if (dout) (void)hipFree(dout);
+    UZK_HIP(e);
+    return UZK_OK;
 }
 
 int g1_op_device(Ctx& c, int op, const Affine* a, const Affine* b, Jac* out, size_t n) {

@@ -19,8 +19,10 @@
 //               normalized subtrahends), OFF2T1 / OFF8T1 (one).  The caller keeps b's VALUE <= k*M.
 //   sqr(a), mul2(a, b, c, d)  a*a and a*b + c*d with one reduction; same contracts (sum of the limb
 //               bound products < 2^60.6).
-//   norm(a)     carry propagation: limbs < B again, value unchanged.
-//   reduce(a)   value < 16 M  ->  normalized, value < 2M.
+//   norm(a)     carry propagation, limbs < 2^32 - 2^3 (a limb and the carry into it, < 2^3, share 32 bits): limbs < B again, value
+//               unchanged.
+//   reduce(a)   value < 32 M  ->  normalized, value < 2M.  (q = floor(l8 MU / 2^32) with MU = floor(2^264 / M) undershoots
+//               floor(value / M) by at most one below 32 M: acc29_set passes it from_fp_x32 of a canonical coordinate, < 32 (M - 1).)
 //   canon(a)    value < 16 M  ->  the unique representative in [0, M), normalized.
 // The external 4 x u64 Montgomery form has radix 2^256.  NTT data stays in 2^256-form (it is only ever
 // multiplied by twiddles, which the plan stores in 2^261-form); MSM bases are used as they arrive
@@ -80,7 +82,8 @@ struct Field29 {
     // The way back: value / 2^S mod M as 8 x 32-bit words, by EXACT division -- add the multiple k M (k < 2^S) that clears the low
     // S bits, shift.  S = 5 maps the 2^261-form to the wire's 2^256-form, S = 10 the 2^266-form; ~90 instructions against a product
     // by a constant plus canon (~300).  a: limbs < 2^32, value < V M with (V + 2^S) / 2^S <= 2: the result is < 2 M (and < 2^256);
-    // the caller's canon (one conditional subtraction) makes it canonical.
+    // the caller's canon (one conditional subtraction) makes it canonical.  The sum a + k M must also fit the nine limbs (top limb
+    // < 2^32): V + 2^S <= 1354, so S = 10 takes V <= 330 (S = 5: V <= 32 as above).
     template <int S>
     __device__ __forceinline__ static Fp to_fp_div(const L29& a) {
         static_assert(S >= 1 && S <= 10, "k M must stay below 2^10 M");
@@ -301,7 +304,7 @@ struct Field29 {
         for (int i = 0; i < 9; ++i) { z |= a.l[i]; m1 |= a.l[i] ^ C::M[i]; m2 |= a.l[i] ^ C::M2[i]; }
         return z == 0 || m1 == 0 || m2 == 0;
     }
-    // a: limbs < 2^32 - 2^3, value < 16 M  ->  normalized, value < 2M, same residue.
+    // a: limbs < 2^32 - 2^3, value < 32 M  ->  normalized, value < 2M, same residue (tests/test_gpu_lz29_bounds.py drives it to 32 M).
     // r = a - q*M with q = floor(value / M) or one less, estimated from the top limb.
     __device__ __forceinline__ static L29 reduce(const L29& a_in) {
         const L29 a = norm(a_in);

@@ -58,11 +58,17 @@ template <class C> struct WireCfg;
 template <> struct WireCfg<Fq29Cfg> { using type = FqCfg; };
 template <> struct WireCfg<Fr29Cfg> { using type = FrCfg; };
 
+// The largest V whose values fit the nine limbs at all: a value < V M has a top limb (bits 232 and up) < V ((M >> 232) + 1), which must
+// stay below 2^32 -- V <= 1354 for both fields.  (M >> 232 is the top limb of the normalized modulus.)
+template <class C>
+constexpr bool value_fits(int v) { return (uint64_t)v * ((uint64_t)C::M[8] + 1) <= (1ull << 32); }
+
 template <class F, int K, int V>
 struct Lz {
     L29 v;
     static constexpr int limb_k = K, val_v = V;
     static_assert(K >= 1 && K <= 7, "limbs must stay below 2^32");
+    static_assert(V >= 1 && value_fits<typename F::Cfg>(V), "a value below V M does not fit nine limbs with a top limb below 2^32");
 };
 
 template <class F>
@@ -102,7 +108,8 @@ struct LzOps {
         return r;
     }
     // UNCHECKED restatement of the bounds, for values whose bound rests on an argument the types cannot see (a running sum over a
-    // run-time number of terms that the host has limited): every use states that argument in a comment
+    // run-time number of terms that the host has limited): every use states that argument in a comment and names the test that
+    // drives it to its limit
     template <int K2, int V2, int K, int V>
     __device__ __forceinline__ static E<K2, V2> assume(const E<K, V>& a) {
         E<K2, V2> r;
@@ -167,7 +174,8 @@ struct LzOps {
         if constexpr (V <= 33) {
             return Field<typename WireCfg<C>::type>::canon(F::template to_fp_div<5>(a.v));
         } else {
-            static_assert(V <= 169 * 14, "value bound of to_wire");
+            static_assert(value_fits<C>(V), "value bound of to_wire: the top limb must stay below 2^32");
+            static_assert(cols_fit(K, V, 1, 1), "a column of the product by 2^256 can overflow 64 bits");
             return F::to_fp(F::canon(F::to_256(a.v)));
         }
     }

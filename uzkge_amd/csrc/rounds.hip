@@ -14,6 +14,7 @@
 //   trimmed_len_lanes     FpPolynomial::from_coefs' trim, field_polynomial.rs:86-90 rounds 3, 5
 #include <algorithm>
 #include <cstring>
+#include <vector>
 
 #include "ctx.hpp"
 #include "host_math.hpp"
@@ -196,20 +197,23 @@ __global__ __launch_bounds__(256) void poly_eval_lanes29_kernel(const EvalPoly* 
         if (e & 1) wblk = Z::template relax<1, 8>(Z::mul(wblk, sp));
         sp = Z::template relax<1, 8>(Z::sqr(sp));
     }
-    { S8 t; t.v = get(pw, tid); put(sh, tid, Z::mul(h, t).v); }         // < 4 M each, normalized
+    using Term = Lz<Fr29, 1, 4>;                                        // mul(h, pw[tid]): prod_v(48, 8) = 4
+    { S8 t; t.v = get(pw, tid); const Term p = Z::mul(h, t); put(sh, tid, p.v); }   // normalized
     __syncthreads();
-    // 256 values < 4 M: the tree's sums stay below 1024 M; one carry step per level keeps the limbs normalized
+    // 256 values < 4 M: the tree's sums stay below 1024 M; one carry step per level keeps the limbs normalized.  LDS holds limbs,
+    // not types: sh[i] is restated as a sum of Term values, at most 128 of them in either half that a level adds (assume: < 512 M),
+    // 256 at the root (< 1024 M).  Driven to that limit by tests/test_gpu_lane_bounds.py (2^18 coefficients, the coefficients and
+    // the point the words of r - 1).
+    auto sum_at = [&](uint32_t i) { Term t; t.v = get(sh, i); return t; };
     for (uint32_t st = 128; st > 0; st >>= 1) {
         if (tid < st) {
-            Lz<Fr29, 1, 1024> u, v;
-            u.v = get(sh, tid); v.v = get(sh, tid + st);
+            const auto u = Z::template assume<1, 512>(sum_at(tid)), v = Z::template assume<1, 512>(sum_at(tid + st));
             put(sh, tid, Z::norm(Z::add(u, v)).v);
         }
         __syncthreads();
     }
     if (tid == 0) {
-        Lz<Fr29, 1, 1024> tot;
-        tot.v = get(sh, 0);
+        const auto tot = Z::template assume<1, 1024>(sum_at(0));
         partial[(uint64_t)slot * stride + blk] = Z::to_wire(Z::mul(tot, wblk));
         __threadfence();
         last = (atomicAdd(&counters[slot], 1u) == nblocks - 1) ? 1u : 0u;
@@ -225,16 +229,21 @@ __global__ __launch_bounds__(256) void poly_eval_lanes29_kernel(const EvalPoly* 
 #endif
 }
 
+// Which evaluation kernel runs: PER = 16 (wide) for several lanes of long polynomials, the lazy 29-bit products when
+// uzk_tune("arith29", mask) has bit 1.  The launcher and the test hook (uzk_test_lanes) both ask here.
+LaneKernel poly_eval_lanes_kernel_of(const Ctx& c, uint32_t lanes, uint64_t max_len) {
+    return LaneKernel{(c.tune_arith29 & 2) != 0, lanes >= 4 && max_len >= 4096};
+}
 // d_polys: `count` EvalPoly in device memory; d_counters: lanes * count zeroed words; out_host: pinned.  Asynchronous.
 int poly_eval_lanes(Ctx& c, const void* d_polys, uint32_t count, uint64_t max_len, const Fp* d_points, uint32_t lanes, uint32_t* d_counters, Fp* out_host_pinned) {
     if (count == 0 || lanes == 0) return UZK_OK;
     if (max_len == 0 || max_len > (1ull << 18)) { set_error("poly_eval_lanes: lengths must be 1 .. 2^18"); return UZK_ERR_PARAMETER; }
-    const bool wide = lanes >= 4 && max_len >= 4096;
+    const LaneKernel pick = poly_eval_lanes_kernel_of(c, lanes, max_len);
+    const bool wide = pick.wide, a29 = pick.a29;
     const uint64_t per_block = wide ? 4096 : 1024, blocks = (max_len + per_block - 1) / per_block;
     UZK_TRY(c.poly_tmp.reserve((size_t)lanes * count * blocks * sizeof(Fp)));
     KernelScope ks(c, "poly_eval");
     const dim3 grid((unsigned)blocks, count, lanes);
-    const bool a29 = (c.tune_arith29 & 2) != 0;       // the products on the lazy 29-bit limbs (uzk_tune("arith29", mask) bit 1)
     if (wide && a29) hipLaunchKernelGGL(poly_eval_lanes29_kernel<16>, grid, dim3(256), 0, c.stream, static_cast<const EvalPoly*>(d_polys), d_points, c.poly_tmp.as<Fp>(), d_counters, out_host_pinned);
     else if (a29) hipLaunchKernelGGL(poly_eval_lanes29_kernel<4>, grid, dim3(256), 0, c.stream, static_cast<const EvalPoly*>(d_polys), d_points, c.poly_tmp.as<Fp>(), d_counters, out_host_pinned);
     else if (wide) hipLaunchKernelGGL(poly_eval_lanes_kernel<16>, grid, dim3(256), 0, c.stream, static_cast<const EvalPoly*>(d_polys), d_points, c.poly_tmp.as<Fp>(), d_counters, out_host_pinned);
@@ -279,60 +288,81 @@ __global__ __launch_bounds__(256) void poly_lincomb_lanes_kernel(const LinPoly* 
 }
 // ---- the same two lane kernels on the lazy 29-bit limbs (lz29.hpp; round 6) ------------------------------------------------------
 // Linear combination: two terms share one reduction (mul2); the running sum stays lazy between terms (one parallel carry step per
-// pair).  Value bound: every pair adds < 14 M, the host admits count <= 128 (< 900 M in all: the top limb stays below 2^32).
+// pair).  Value bound: every pair adds < 14 M, the host admits count <= kLincomb29Max = 128 terms, so one of the GS lanes that share
+// a coefficient sums at most 64 / GS pairs: < 896 / GS M, typed < 1024 / GS M; each shuffle level of the reduction over the GS lanes
+// doubles the bound, and the whole sum is < 1024 M (the top limb stays below 2^32 up to 1354 M).
+constexpr uint32_t kLincomb29Max = 128;
+#if defined(__HIP_DEVICE_COMPILE__)
+// one shuffle level of the GS-lane reduction: lanes sub < GS - O add the partial sum O lanes above theirs
+template <int O, int GS, int V>
+__device__ __forceinline__ Lz<Fr29, 1, 2 * V> lincomb_shfl_add(const Lz<Fr29, 1, V>& a, uint32_t sub) {
+    using Z = LzOps<Fr29>;
+    Lz<Fr29, 1, V> q;
+#pragma unroll
+    for (int w = 0; w < 9; ++w) q.v.l[w] = (uint32_t)__shfl_down((int)a.v.l[w], O);
+    Lz<Fr29, 1, 2 * V> r = Z::template relax<1, 2 * V>(a);
+    if (sub + (uint32_t)O < (uint32_t)GS) r = Z::norm(Z::add(a, q));
+    return r;
+}
+#endif
 template <int GS>
 __global__ __launch_bounds__(256) void poly_lincomb_lanes29_kernel(const LinPoly* __restrict__ polys, uint32_t count, const uint32_t* __restrict__ lens,
                                                                    const Fp* __restrict__ scalars, Fp* __restrict__ out, uint64_t out_stride, uint64_t out_len) {
 #if defined(__HIP_DEVICE_COMPILE__)
+    static_assert(GS == 1 || GS == 4, "the shuffle levels below are written out for GS = 4");
     using Z = LzOps<Fr29>;
-    using Acc = Lz<Fr29, 1, 1024>;
+    constexpr int VL = 1024 / GS;                 // one lane's partial sum: < 64 / GS pairs of < 14 M each
+    using Acc = Lz<Fr29, 1, VL>;
     const uint32_t b = blockIdx.y;
     const uint64_t gid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const uint64_t j = gid / GS;
     const uint32_t sub = (uint32_t)(gid % GS);
     const bool live = j < out_len;
     lens += (uint64_t)b * count; scalars += (uint64_t)b * count;
-    Acc acc = Z::template relax<1, 1024>(Z::zero());
+    Acc acc = Z::template relax<1, VL>(Z::zero());
     if (live) {
         auto term = [&](uint32_t k) { return polys[k].p[(uint64_t)b * polys[k].lane_stride + j]; };
+        // assume: the running sum of at most kLincomb29Max / (2 GS) pairs (< 14 M each) stays below VL M -- driven to that limit by
+        // tests/test_gpu_lane_bounds.py (count = 128 with every scalar and coefficient the words of r - 1, GS = 1 and 4)
         for (uint32_t k = sub; k < count; k += 2 * GS) {
             const uint32_t k2 = k + GS;
             const bool has1 = j < lens[k], has2 = k2 < count && j < lens[k2];
             if (has1 && has2) {
                 const auto t = Z::mul2(Z::ld(scalars[k]), Z::ld(term(k)), Z::ld(scalars[k2]), Z::ld(term(k2)));
-                acc = Z::template assume<1, 1024>(Z::norm(Z::add(acc, t)));
+                acc = Z::template assume<1, VL>(Z::norm(Z::add(acc, t)));
             } else if (has1 || has2) {
                 const uint32_t kk = has1 ? k : k2;
                 const auto t = Z::mul(Z::ld(scalars[kk]), Z::ld(term(kk)));
-                acc = Z::template assume<1, 1024>(Z::norm(Z::add(acc, t)));
+                acc = Z::template assume<1, VL>(Z::norm(Z::add(acc, t)));
             }
         }
     }
-    if constexpr (GS > 1) {
-#pragma unroll
-        for (int o = GS / 2; o > 0; o >>= 1) {
-            Acc q;
-#pragma unroll
-            for (int w = 0; w < 9; ++w) q.v.l[w] = (uint32_t)__shfl_down((int)acc.v.l[w], o);
-            if (sub + (uint32_t)o < (uint32_t)GS) acc = Z::template assume<1, 1024>(Z::norm(Z::add(acc, q)));
-        }
-    }
-    if (live && sub == 0) out[(uint64_t)b * out_stride + j] = Z::to_wire(acc);
+    Lz<Fr29, 1, 1024> tot;
+    if constexpr (GS == 4) tot = lincomb_shfl_add<1, GS>(lincomb_shfl_add<2, GS>(acc, sub), sub);   // < 512 M after the first level
+    else tot = acc;
+    if (live && sub == 0) out[(uint64_t)b * out_stride + j] = Z::to_wire(tot);
 #endif
 }
 
 
+// Which linear-combination kernel runs: GS = 4 lanes per coefficient (wide) for short outputs of many terms; the lazy 29-bit
+// products when uzk_tune("arith29", mask) has bit 1 AND count <= kLincomb29Max (the bound of its running sum).  The launcher and the
+// test hook (uzk_test_lanes) both ask here.
+LaneKernel poly_lincomb_lanes_kernel_of(const Ctx& c, uint32_t count, uint64_t out_len) {
+    return LaneKernel{(c.tune_arith29 & 2) != 0 && count <= kLincomb29Max, out_len <= (1ull << 17) && count >= 8};
+}
 int poly_lincomb_lanes(Ctx& c, const void* d_polys, uint32_t count, const uint32_t* d_lens, const Fp* d_scalars, uint32_t lanes, Fp* d_out, uint64_t out_stride,
                        uint64_t out_len) {
     if (count == 0 || lanes == 0 || out_len == 0) return UZK_OK;
     KernelScope ks(c, "poly_lincomb");
     const LinPoly* polys = static_cast<const LinPoly*>(d_polys);
-    const bool a29 = (c.tune_arith29 & 2) != 0 && count <= 128;      // (the 29-bit kernel's running sum is bounded for <= 128 terms)
-    if (a29 && out_len <= (1ull << 17) && count >= 8)
+    const LaneKernel pick = poly_lincomb_lanes_kernel_of(c, count, out_len);
+    const bool a29 = pick.a29;
+    if (a29 && pick.wide)
         hipLaunchKernelGGL(poly_lincomb_lanes29_kernel<4>, dim3((unsigned)((out_len * 4 + 255) / 256), lanes), dim3(256), 0, c.stream, polys, count, d_lens, d_scalars, d_out, out_stride, out_len);
     else if (a29)
         hipLaunchKernelGGL(poly_lincomb_lanes29_kernel<1>, dim3((unsigned)((out_len + 255) / 256), lanes), dim3(256), 0, c.stream, polys, count, d_lens, d_scalars, d_out, out_stride, out_len);
-    else if (out_len <= (1ull << 17) && count >= 8)
+    else if (pick.wide)
         hipLaunchKernelGGL(poly_lincomb_lanes_kernel<4>, dim3((unsigned)((out_len * 4 + 255) / 256), lanes), dim3(256), 0, c.stream, polys, count, d_lens, d_scalars, d_out, out_stride, out_len);
     else
         hipLaunchKernelGGL(poly_lincomb_lanes_kernel<1>, dim3((unsigned)((out_len + 255) / 256), lanes), dim3(256), 0, c.stream, polys, count, d_lens, d_scalars, d_out, out_stride, out_len);
@@ -344,6 +374,53 @@ void lin_poly_fill(void* host_entry, const void* p, uint64_t lane_stride) {
     e.p = static_cast<const Fp*>(p); e.lane_stride = lane_stride;
 }
 size_t lin_poly_bytes() { return sizeof(LinPoly); }
+
+// ---- test hook (uzk_test_lanes): the two lane kernels above on the caller's device polynomials ---------------------------------
+// op 0: linear combination, lens[lanes][count], args[lanes][count] scalars, out[lanes][len] (len = out_len);
+// op 1: evaluation, lens[count] (every lane's), pts[count] in {0, 1}, args[lanes][2] points, out[lanes][count] (len = max_len).
+// *kernel: bit 0 the lazy 29-bit kernel ran, bit 1 the wide one (GS = 4 / PER = 16) -- from the launchers' own choice.
+int lanes_test(Ctx& c, int op, const void* const* d_polys, const uint64_t* lane_strides, uint32_t count, const uint32_t* lens, const uint32_t* pts,
+               const Fp* args, uint32_t lanes, uint64_t len, Fp* out, int* kernel) {
+    const LaneKernel pick = op == 0 ? poly_lincomb_lanes_kernel_of(c, count, len) : poly_eval_lanes_kernel_of(c, lanes, len);
+    *kernel = (pick.a29 ? 1 : 0) | (pick.wide ? 2 : 0);
+    const size_t entry = op == 0 ? sizeof(LinPoly) : sizeof(EvalPoly);
+    const size_t n_lens = op == 0 ? (size_t)lanes * count : count, n_args = op == 0 ? (size_t)lanes * count : 2 * (size_t)lanes;
+    const size_t n_out = op == 0 ? (size_t)lanes * len : (size_t)lanes * count;
+    std::vector<unsigned char> host(entry * count);
+    for (uint32_t k = 0; k < count; ++k) {
+        if (op == 0) lin_poly_fill(&host[entry * k], d_polys[k], lane_strides[k]);
+        else eval_poly_fill(&host[entry * k], d_polys[k], lane_strides[k], lens[k], pts[k]);
+    }
+    unsigned char* d_polys_arr = nullptr;
+    uint32_t *d_lens = nullptr, *d_counters = nullptr;
+    Fp *d_args = nullptr, *d_out = nullptr, *h_out = nullptr;
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&d_polys_arr), entry * count + 16);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d_lens), n_lens * sizeof(uint32_t) + 16);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d_counters), (size_t)lanes * count * sizeof(uint32_t) + 16);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d_args), n_args * sizeof(Fp));
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d_out), n_out * sizeof(Fp) + 16);
+    if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&h_out), n_out * sizeof(Fp) + 16, hipHostMallocDefault);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_polys_arr, host.data(), entry * count, hipMemcpyHostToDevice, c.stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_lens, lens, n_lens * sizeof(uint32_t), hipMemcpyHostToDevice, c.stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_args, args, n_args * sizeof(Fp), hipMemcpyHostToDevice, c.stream);
+    if (e == hipSuccess) e = hipMemsetAsync(d_counters, 0, (size_t)lanes * count * sizeof(uint32_t), c.stream);
+    int rc = UZK_OK;
+    if (e == hipSuccess) {
+        rc = op == 0 ? poly_lincomb_lanes(c, d_polys_arr, count, d_lens, d_args, lanes, d_out, len, len)
+                     : poly_eval_lanes(c, d_polys_arr, count, len, d_args, lanes, d_counters, h_out);
+        if (rc == UZK_OK && op == 0) e = hipMemcpyAsync(h_out, d_out, n_out * sizeof(Fp), hipMemcpyDeviceToHost, c.stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c.stream);
+        if (rc == UZK_OK && e == hipSuccess) std::memcpy(out, h_out, n_out * sizeof(Fp));
+    }
+    if (d_polys_arr) (void)hipFree(d_polys_arr);
+    if (d_lens) (void)hipFree(d_lens);
+    if (d_counters) (void)hipFree(d_counters);
+    if (d_args) (void)hipFree(d_args);
+    if (d_out) (void)hipFree(d_out);
+    if (h_out) (void)hipHostFree(h_out);
+    UZK_HIP(e);
+    return rc;
+}
 
 // ---- division by X - z ----------------------------------------------------------------------------------------------------
 // The blocked scan of poly.hip's open_div_* kernels with one opening per blockIdx.y: h_v of n coefficients at h + v * h_stride,
