@@ -218,6 +218,32 @@ int uzk_ntt_fr_batch_device(const void* d_in, void* d_out, uint64_t n, uint32_t 
 int uzk_ntt_fr_batch_strided_device(const void* d_in, uint64_t in_stride, void* d_out, uint64_t out_stride, uint64_t n,
                                     uint32_t batch, int inverse, const uint64_t* coset_shift_mont, int sync);
 
+/* ---- NTT over G1: EvaluationDomain::{fft, ifft} over Vec<G1Projective> ------------------------------------------------------
+ * The elements are curve points (64 B affine, (0,0) = infinity, in and out), the twiddles the powers of uzk_domain_group_gen(n);
+ * natural order in and out:
+ *   forward  out[k] = sum_i w^(ik) in[i]              inverse  out[i] = (1/n) sum_k w^(-ik) in[k]
+ * With M[k] = [tau^k] G (a monomial SRS) and L[i] = [L_i(tau)] G (the Lagrange bases every commit of the round API takes):
+ * L = inverse(M), M = forward(L).  The reference ships L for n = 4096, 8192, 16384 only (gen_params/mod.rs:175-177) and cannot
+ * derive it; uzk_srs_to_lagrange does, for every n = 2^k up to the bound.  Complete: any input may be infinity, any output too.
+ * The largest size is the largest one the parity suite checks on the whole vector (tests/test_gpu_g1_ntt.py), as for the Fr
+ * transforms above: that case (two transforms of each direction, 0.36 / 0.40 s each, and four MSMs of 2^20 points by the CPU oracle) takes 4 s of
+ * the suite. */
+#define UZK_NTT_G1_MAX_LOG2 20
+/* 1 if n = 2^k with k <= UZK_NTT_G1_MAX_LOG2, else 0 (3 * 2^k domains are not transformed over G1). */
+int uzk_ntt_g1_supported(uint64_t n);
+/* Host arrays of n points; `points` and `out` may be the same array.  n = 1 is the identity map. */
+int uzk_ntt_g1(const uzk_g1_affine* points, uzk_g1_affine* out, uint64_t n, int inverse);
+/* Device arrays (may alias), asynchronous on the calling context's stream unless `sync` != 0. */
+int uzk_ntt_g1_device(const void* d_in, void* d_out, uint64_t n, int inverse, int sync);
+/* The Lagrange bases of size n from the first n points of a registered (monomial) SRS: inverse transform into memory the new
+ * handle owns (released with uzk_srs_release).  n > uzk_srs_len -> UZK_ERR_DEGREE; unsupported n -> UZK_ERR_FFT. */
+int uzk_srs_to_lagrange(uint64_t monomial_handle, uint64_t n, uint64_t* lagrange_handle_out);
+/* Reads n points of a handle back from `offset` on (what a caller needs to save a derived basis): offset + n > len ->
+ * UZK_ERR_DEGREE. */
+int uzk_srs_download(uint64_t handle, size_t offset, size_t n, uzk_g1_affine* out);
+/* Group operations one transform of size n runs (doublings, additions), counted from its plan: tools/g1_ntt_shape.py. */
+int uzk_ntt_g1_plan_info(uint64_t n, int inverse, uint64_t* doublings_out, uint64_t* additions_out);
+
 /* ---- polynomial helpers next to the hot path ------------------------ */
 /* out[b] = sum_j coefs[b*n + j] * x^j : FpPolynomial::eval (field_polynomial.rs:198-209) for a batch of
  * polynomials at one point (the prover's 19 + 20 openings at zeta / zeta*omega, prover.rs:246-273). */

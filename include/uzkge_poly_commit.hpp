@@ -152,6 +152,17 @@ class KZGCommitmentSchemeBN254 {
         return out;
     }
     uint64_t handle() const { return handle_; }
+    // A scheme over the Lagrange bases of size n (2^k) derived on the device from the first n powers of this monomial scheme
+    // (uzk_srs_to_lagrange: the inverse transform over G1): usable wherever the reference loads lagrange_pcs from a file.
+    KZGCommitmentSchemeBN254 lagrange(size_t n) const {
+        uint64_t h = 0;
+        check(uzk_srs_to_lagrange(handle_, n, &h));
+        std::vector<G1Affine> g1(n);
+        const int rc = uzk_srs_download(h, 0, n, g1.data());
+        if (rc != UZK_OK) (void)uzk_srs_release(h);
+        check(rc);
+        return KZGCommitmentSchemeBN254(std::move(g1), h);
+    }
 
     // element-wise field helpers of the host mirrors (device primitives through the KAT entry point)
     static std::vector<Fr> fr_neg(const std::vector<Fr>& a) { return fr_op(5, a, a); }
@@ -159,6 +170,7 @@ class KZGCommitmentSchemeBN254 {
     static std::vector<Fr> fr_sub(const std::vector<Fr>& a, const std::vector<Fr>& b) { return fr_op(2, a, b); }
 
   private:
+    KZGCommitmentSchemeBN254(std::vector<G1Affine> g1, uint64_t handle) : public_parameter_group_1(std::move(g1)), handle_(handle) {}
     static std::vector<Fr> fr_op(int op, const std::vector<Fr>& a, const std::vector<Fr>& b) {
         std::vector<Fr> out(a.size());
         if (!a.empty())

@@ -142,6 +142,26 @@ pub(crate) fn resident_srs(public_parameter_group_1: &[G1Projective]) -> Result<
     Ok(srs)
 }
 
+/// The Lagrange bases of a size-`n` circuit derived on the device from the first `n` powers of the monomial SRS
+/// (`Srs::to_lagrange`: the inverse transform over G1): what `load_lagrange_params` (gen_params/mod.rs:186-199) can fall back to
+/// when its embedded table has no entry for `n` -- the reference ships 4096, 8192 and 16384 only and cannot derive others.
+/// `None`: no device, `n` is not a size the library transforms, or the SRS holds fewer than `n` powers.
+pub fn lagrange_pcs_for(public_parameter_group_1: &[G1Projective], n: usize) -> Option<Vec<G1Projective>> {
+    if n == 0 || n > public_parameter_group_1.len() || unsafe { sys::uzk_ntt_g1_supported(n as u64) } != 1 {
+        return None;
+    }
+    let srs = resident_srs(public_parameter_group_1).ok()?;
+    let bases = srs.to_lagrange(n).ok()?;
+    let wire = bases.download(0, n).ok()?;
+    Some(wire.iter().map(affine_from_wire).collect())
+}
+fn affine_from_wire(p: &sys::uzk_g1_affine) -> G1Projective {
+    if p.x == [0u64; 4] && p.y == [0u64; 4] {
+        return G1Projective::default(); // (0, 0) is the wire's point at infinity
+    }
+    G1Affine::new_unchecked(Fq::new_unchecked(BigInt(p.x)), Fq::new_unchecked(BigInt(p.y))).into()
+}
+
 /// Drops the device copy of this parameter set (HBM is released when the last commit using it returns).
 pub fn release_srs(public_parameter_group_1: &[G1Projective]) {
     if public_parameter_group_1.is_empty() {

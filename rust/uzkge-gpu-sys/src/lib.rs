@@ -83,6 +83,20 @@ impl Srs {
         check(unsafe { uzk_msm_g1_batch(self.handle, offset, scalars_mont.as_ptr() as *const u64, n, batch as u32, out.as_mut_ptr()) })?;
         Ok(out)
     }
+    /// The Lagrange bases of size `n` (a power of two up to 2^UZK_NTT_G1_MAX_LOG2) from the first `n` points of this monomial
+    /// SRS: the inverse G1 transform on the device (`uzk_srs_to_lagrange`) -- what the reference reads from one of its three
+    /// `lagrange-srs-*.bin` files (gen_params/mod.rs:186-199), for any size.  The new SRS owns its memory.
+    pub fn to_lagrange(&self, n: usize) -> Result<Srs, Error> {
+        let mut handle = 0u64;
+        check(unsafe { uzk_srs_to_lagrange(self.handle, n as u64, &mut handle) })?;
+        Ok(Srs { handle, len: n })
+    }
+    /// `n` points from `offset` on, read back from the device (to keep or save a derived basis).
+    pub fn download(&self, offset: usize, n: usize) -> Result<Vec<uzk_g1_affine>, Error> {
+        let mut out = vec![uzk_g1_affine::default(); n];
+        check(unsafe { uzk_srs_download(self.handle, offset, n, out.as_mut_ptr()) })?;
+        Ok(out)
+    }
 }
 
 impl Srs {

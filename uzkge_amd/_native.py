@@ -64,6 +64,12 @@ PROTOTYPES = {
     "uzk_ntt_fr_batch": (_I, [_P, _U64, ctypes.c_uint32, _I, _P]),
     "uzk_ntt_fr_batch_device": (_I, [_P, _P, _U64, ctypes.c_uint32, _I, _P, _I]),
     "uzk_ntt_fr_batch_strided_device": (_I, [_P, _U64, _P, _U64, _U64, ctypes.c_uint32, _I, _P, _I]),
+    "uzk_ntt_g1_supported": (_I, [_U64]),
+    "uzk_ntt_g1": (_I, [_P, _P, _U64, _I]),
+    "uzk_ntt_g1_device": (_I, [_P, _P, _U64, _I, _I]),
+    "uzk_srs_to_lagrange": (_I, [_U64, _U64, ctypes.POINTER(_U64)]),
+    "uzk_srs_download": (_I, [_U64, _SZ, _SZ, _P]),
+    "uzk_ntt_g1_plan_info": (_I, [_U64, _I, ctypes.POINTER(_U64), ctypes.POINTER(_U64)]),
     "uzk_hide_polynomial_batch_device": (_I, [_P, _U64, _U64, ctypes.c_uint32, _P, ctypes.c_uint32, _U64]),
     "uzk_fold_blinds_batch_device": (_I, [_P, _U64, _P, _U64, ctypes.c_uint32, _P, _U64, _P, ctypes.c_uint32, _P]),
     "uzk_poly_trimmed_len_device": (_I, [_P, _U64, _P, ctypes.c_uint32, _P, _I]),

@@ -131,6 +131,21 @@ class Srs:
         """Build the window table for a static SRS (uzk_srs_precompute)."""
         check(lib.uzk_srs_precompute(self.handle, window_bits))
 
+    def to_lagrange(self, n: int) -> "Srs":
+        """The Lagrange bases of size n from the first n points of this (monomial) SRS: the inverse G1 transform on the
+        device (uzk_srs_to_lagrange).  The new SRS owns its memory."""
+        h = ctypes.c_uint64(0)
+        check(lib.uzk_srs_to_lagrange(self.handle, n, ctypes.byref(h)))
+        return Srs(h.value, n)
+
+    def download(self, offset: int = 0, n: Optional[int] = None) -> np.ndarray:
+        """Points [n, 8] of the SRS read back from the device (uzk_srs_download)."""
+        if n is None:
+            n = self.n - offset
+        out = np.zeros((max(n, 0), 8), dtype=np.uint64)
+        check(lib.uzk_srs_download(self.handle, offset, n, _ptr(out) if out.shape[0] else None))
+        return out
+
     def release(self) -> None:
         if self.handle:
             check(lib.uzk_srs_release(self.handle))
@@ -249,6 +264,30 @@ def ntt_device(d_in: int, d_out: int, n: int, inverse: bool = False, coset_shift
         cs = np.ascontiguousarray(coset_shift, dtype=np.uint64).reshape(4)
     check(lib.uzk_ntt_fr_device(ctypes.c_void_p(d_in), ctypes.c_void_p(d_out), n, int(inverse),
                                 _ptr(cs) if cs is not None else None, int(sync)))
+
+
+def ntt_g1_supported(n: int) -> bool:
+    return bool(lib.uzk_ntt_g1_supported(n))
+
+
+def ntt_g1(points: np.ndarray, inverse: bool = False) -> np.ndarray:
+    """EvaluationDomain::fft / ifft over a vector of G1 points ([n, 8] affine wire rows, (0, 0) = infinity), natural
+    order in and out; returns a new array.  inverse(monomial SRS) = Lagrange SRS."""
+    p = np.ascontiguousarray(points, dtype=np.uint64).reshape(-1, 8)
+    out = np.zeros_like(p)
+    check(lib.uzk_ntt_g1(_ptr(p) if p.shape[0] else None, _ptr(out) if p.shape[0] else None, p.shape[0], int(inverse)))
+    return out
+
+
+def ntt_g1_device(d_in: int, d_out: int, n: int, inverse: bool = False, sync: bool = False) -> None:
+    check(lib.uzk_ntt_g1_device(ctypes.c_void_p(d_in), ctypes.c_void_p(d_out), n, int(inverse), int(sync)))
+
+
+def ntt_g1_plan_info(n: int, inverse: bool = False) -> Tuple[int, int]:
+    """(doublings, additions) one G1 transform of size n runs."""
+    d, a = ctypes.c_uint64(0), ctypes.c_uint64(0)
+    check(lib.uzk_ntt_g1_plan_info(n, int(inverse), ctypes.byref(d), ctypes.byref(a)))
+    return d.value, a.value
 
 
 def poly_eval_batch(coefs: np.ndarray, x_mont: np.ndarray) -> np.ndarray:

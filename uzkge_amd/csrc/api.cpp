@@ -222,6 +222,7 @@ static void ctx_release(Ctx& c) {
     (void)hipSetDevice(c.device);
     (void)hipStreamSynchronize(c.stream);
     ntt_free_plans(c);
+    g1ntt_free(c);
     msm_free(c);
     poly_free(c);
     c.ntt_scratch[0].release(); c.ntt_scratch[1].release(); c.ntt_io.release(); c.msm_scalars.release();
@@ -955,6 +956,85 @@ int uzk_ntt_fr_batch(uint64_t* data, uint64_t n, uint32_t batch, int inverse, co
     API_LOCK;
     return ntt_host_common(data, n, batch, inverse, coset_shift_mont);
 } catch (...) { return uzk::on_exception("uzk_ntt_fr_batch"); }
+
+/* ---- NTT over G1 --------------------------------------------------------------------------- */
+static bool g1_ntt_supported(uint64_t n) { return n != 0 && (n & (n - 1)) == 0 && n <= (1ull << UZK_NTT_G1_MAX_LOG2); }
+static int g1_ntt_size_checked(uint64_t n, const char* who) {
+    if (g1_ntt_supported(n)) return UZK_OK;
+    set_error("%s: no G1 transform of size %llu (need 2^k, k <= %d)", who, (unsigned long long)n, UZK_NTT_G1_MAX_LOG2);
+    return UZK_ERR_FFT;
+}
+int uzk_ntt_g1_supported(uint64_t n) try { return g1_ntt_supported(n) ? 1 : 0; } catch (...) { return uzk::on_exception("uzk_ntt_g1_supported"); }
+
+int uzk_ntt_g1_plan_info(uint64_t n, int inverse, uint64_t* doublings_out, uint64_t* additions_out) try {
+    if (!doublings_out || !additions_out) { set_error("uzk_ntt_g1_plan_info: null pointer"); return UZK_ERR_PARAMETER; }
+    UZK_TRY(g1_ntt_size_checked(n, "uzk_ntt_g1_plan_info"));
+    g1ntt_op_count(n, inverse != 0, doublings_out, additions_out);
+    return UZK_OK;
+} catch (...) { return uzk::on_exception("uzk_ntt_g1_plan_info"); }
+
+int uzk_ntt_g1_device(const void* d_in, void* d_out, uint64_t n, int inverse, int sync) try {
+    API_LOCK;
+    UZK_TRY(g1_ntt_size_checked(n, "uzk_ntt_g1_device"));
+    if (!d_in || !d_out) { set_error("uzk_ntt_g1_device: null pointer"); return UZK_ERR_PARAMETER; }
+    UZK_TRY(require_ready());
+    Ctx& c = ctx();
+    UZK_TRY(g1ntt_run(c, static_cast<const Affine*>(d_in), static_cast<Affine*>(d_out), n, inverse != 0));
+    if (sync) UZK_HIP(hipStreamSynchronize(c.stream));
+    return UZK_OK;
+} catch (...) { return uzk::on_exception("uzk_ntt_g1_device"); }
+
+int uzk_ntt_g1(const uzk_g1_affine* points, uzk_g1_affine* out, uint64_t n, int inverse) try {
+    API_LOCK;
+    UZK_TRY(g1_ntt_size_checked(n, "uzk_ntt_g1"));
+    if (!points || !out) { set_error("uzk_ntt_g1: null pointer"); return UZK_ERR_PARAMETER; }
+    UZK_TRY(require_ready());
+    Ctx& c = ctx();
+    const size_t bytes = (size_t)n * sizeof(Affine);
+    UZK_TRY(c.g1ntt_io.reserve(bytes));
+    UZK_HIP(hipMemcpyAsync(c.g1ntt_io.p, points, bytes, hipMemcpyHostToDevice, c.stream));
+    UZK_TRY(g1ntt_run(c, c.g1ntt_io.as<Affine>(), c.g1ntt_io.as<Affine>(), n, inverse != 0));
+    UZK_HIP(hipMemcpyAsync(out, c.g1ntt_io.p, bytes, hipMemcpyDeviceToHost, c.stream));
+    UZK_HIP(hipStreamSynchronize(c.stream));
+    return UZK_OK;
+} catch (...) { return uzk::on_exception("uzk_ntt_g1"); }
+
+int uzk_srs_to_lagrange(uint64_t monomial_handle, uint64_t n, uint64_t* lagrange_handle_out) try {
+    API_LOCK;
+    if (!lagrange_handle_out) { set_error("uzk_srs_to_lagrange: null pointer"); return UZK_ERR_PARAMETER; }
+    UZK_TRY(g1_ntt_size_checked(n, "uzk_srs_to_lagrange"));
+    Ctx::Srs m;
+    if (!srs_lookup(monomial_handle, &m)) { set_error("uzk_srs_to_lagrange: unknown SRS handle %llu", (unsigned long long)monomial_handle); return UZK_ERR_PARAMETER; }
+    if (n > m.n) { set_error("uzk_srs_to_lagrange: n %llu exceeds SRS length %zu", (unsigned long long)n, m.n); return UZK_ERR_DEGREE; }
+    UZK_TRY(require_ready());
+    Ctx& c = ctx();
+    if (m.device != c.device) { set_error("uzk_srs_to_lagrange: the SRS lives on device %d, the calling context on device %d", m.device, c.device); return UZK_ERR_PARAMETER; }
+    Ctx::Srs l;
+    l.n = n;
+    l.owned = true;
+    l.device = c.device;
+    UZK_HIP(hipMalloc(reinterpret_cast<void**>(&l.d_points), (size_t)n * sizeof(Affine)));
+    int rc = g1ntt_run(c, m.d_points, l.d_points, n, true);
+    if (rc == UZK_OK && hipStreamSynchronize(c.stream) != hipSuccess) { (void)hipGetLastError(); set_error("uzk_srs_to_lagrange: the transform failed on the device"); rc = UZK_ERR_DEVICE; }
+    if (rc != UZK_OK) { (void)hipFree(l.d_points); return rc; }
+    *lagrange_handle_out = srs_insert(l);
+    return UZK_OK;
+} catch (...) { return uzk::on_exception("uzk_srs_to_lagrange"); }
+
+int uzk_srs_download(uint64_t handle, size_t offset, size_t n, uzk_g1_affine* out) try {
+    API_LOCK;
+    if (n > 0 && !out) { set_error("uzk_srs_download: null pointer"); return UZK_ERR_PARAMETER; }
+    Ctx::Srs s;
+    if (!srs_lookup(handle, &s)) { set_error("uzk_srs_download: unknown SRS handle %llu", (unsigned long long)handle); return UZK_ERR_PARAMETER; }
+    if (offset > s.n || n > s.n - offset) { set_error("uzk_srs_download: offset %zu + n %zu exceeds SRS length %zu", offset, n, s.n); return UZK_ERR_DEGREE; }
+    UZK_TRY(require_ready());
+    Ctx& c = ctx();
+    if (s.device != c.device) { set_error("uzk_srs_download: the SRS lives on device %d, the calling context on device %d", s.device, c.device); return UZK_ERR_PARAMETER; }
+    if (n == 0) return UZK_OK;
+    UZK_HIP(hipMemcpyAsync(out, s.d_points + offset, n * sizeof(Affine), hipMemcpyDeviceToHost, c.stream));
+    UZK_HIP(hipStreamSynchronize(c.stream));
+    return UZK_OK;
+} catch (...) { return uzk::on_exception("uzk_srs_download"); }
 
 /* ---- polynomial helpers next to the hot path ------------------------------------------------ */
 int uzk_poly_eval_batch(const uint64_t* coefs, uint64_t n, uint32_t batch, const uint64_t* x_mont, uint64_t* out) try {

@@ -133,6 +133,10 @@ struct Ctx {
     PowCache pow_cache[8];
     uint64_t pow_stamp = 0;
     std::vector<void*> ntt_fused;   // NttFused* (ntt.hip): tables of the fused coset / radix-3 transforms
+    // g1ntt.hip: twiddle digits keyed by n (G1NttPlan*), the working array of extended points, the prefix products of the
+    // conversion to affine, staging for the host-pointer API (grow-only)
+    std::map<uint64_t, void*> g1ntt_plans;
+    DevBuf g1ntt_work, g1ntt_prefix, g1ntt_io;
     // an entry of the process-wide SRS registry
     struct Srs {
         Affine* d_points = nullptr;
@@ -223,6 +227,9 @@ struct KernelScope {
 int ntt_run(Ctx& c, const Fp* d_in, Fp* d_out, uint64_t n, bool inverse, const Fp* coset_shift_host, uint32_t batch,
             uint64_t in_stride = 0, uint64_t out_stride = 0, uint64_t in_len = 0);
 void ntt_free_plans(Ctx& c);
+int g1ntt_run(Ctx& c, const Affine* d_in, Affine* d_out, uint64_t n, bool inverse);
+void g1ntt_op_count(uint64_t n, bool inverse, uint64_t* dbl_out, uint64_t* add_out);
+void g1ntt_free(Ctx& c);
 void msm_plan_info(Ctx& c, size_t n, int* window_bits, int* windows);
 int msm_run(Ctx& c, const Affine* points, const ScalarView& scalars, size_t n, uint32_t batch, Jac* out_host, int pre_c,
             uint32_t pre_stride, uint32_t pre_off);

@@ -173,6 +173,28 @@ def parse_srs_g1_wire(data: bytes) -> np.ndarray:
     return out
 
 
+def srs_g1_wire_to_bytes(g1_wire: np.ndarray, len_g2: int = 0, g2_bytes: bytes = b"") -> bytes:
+    """The writer for parse_srs_g1_wire (host only; `to_unchecked_bytes`, kzg_poly_commitment.rs:228-264): u32 len_g1 | u32 len_g2 |
+    64 B per point -- canonical little-endian x and y out of the Montgomery wire words, bit 7 of the last byte set when
+    y > (p - 1) / 2, bit 6 for infinity over zero coordinates -- then the G2 block, which this library never interprets and
+    passes through as bytes."""
+    pts = np.ascontiguousarray(g1_wire, dtype=np.uint64).reshape(-1, 8)
+    r_inv = pow(1 << 256, -1, FQ_MODULUS)
+    half = (FQ_MODULUS - 1) // 2
+    out = bytearray(struct.pack("<II", pts.shape[0], len_g2))
+    for row in pts:
+        if not row.any():
+            out += bytes(63) + b"\x40"
+            continue
+        x = _wire_int(row[:4]) * r_inv % FQ_MODULUS
+        y = _wire_int(row[4:]) * r_inv % FQ_MODULUS
+        yb = bytearray(y.to_bytes(32, "little"))
+        if y > half:
+            yb[31] |= 0x80
+        out += x.to_bytes(32, "little") + bytes(yb)
+    return bytes(out) + bytes(g2_bytes)
+
+
 def srs_params_wire(srs_blob: bytes, size: int) -> np.ndarray:
     """load_srs_params (uzkge/src/gen_params/mod.rs:151-183) as a wire array (host only): powers 0..2050, the identity
     up to `size`, then the three padding powers size, size + 1, size + 2."""
@@ -220,6 +242,20 @@ class KZGCommitmentSchemeBN254:
         plus = B.msm(self._srs, b, offset=0)
         minus = B.msm(self._srs, fr_neg(b), offset=zeroing_degree)
         return B.g1_fold(np.stack([np.asarray(commitment, dtype=np.uint64).reshape(12), plus, minus]))
+
+    def to_unchecked_bytes(self) -> bytes:
+        """The G1 powers in the reference's blob format, no G2 part (as the reference's Lagrange files)."""
+        return srs_g1_wire_to_bytes(self.public_parameter_group_1)
+
+    def lagrange(self, n: int) -> "KZGCommitmentSchemeBN254":
+        """A scheme over the Lagrange bases of size n derived on the device from the first n powers of this (monomial)
+        scheme: usable wherever the reference loads `lagrange_pcs` from a file (ProverCommit), at any n = 2^k the G1
+        transform supports."""
+        srs = self._srs.to_lagrange(n)
+        out = KZGCommitmentSchemeBN254.__new__(KZGCommitmentSchemeBN254)
+        out._srs = srs
+        out.public_parameter_group_1 = srs.download()
+        return out
 
     def release(self) -> None:
         self._srs.release()
