@@ -539,6 +539,60 @@ int uzk_prove_round5(uint64_t prover, const uint64_t* r_scalars, size_t r_count,
  * Without wire selectors the slot order of 0..2 is w0..4, pi, z (7 slots used). */
 int uzk_prover_buffer(uint64_t prover, int which, void** d_out, uint64_t* elems_out);
 
+/* ---- batch verification: M proofs folded into one pairing check ------------------------------------------------------------------
+ * The reference's verifier (uzkge/src/plonk/verifier.rs:17-164) ends in  e(left, [tau] G2) = e(right, G2)  with left and right
+ * sums of (commitment, scalar) products (batch_verify_diff_points, kzg_poly_commitment.rs:373-422).  With one weight rho_i per
+ * proof, M such equations collapse into ONE:
+ *     e(L, [tau] G2) = e(R, G2),      L = sum_i rho_i left_i,      R = sum_i rho_i right_i,
+ * which holds for weights nobody could predict only if every proof's own equation does.  Everything in front of the two pairings
+ * is data-parallel over proofs and runs on the device: decoding and checking the proof bytes, the M Keccak transcripts, the
+ * verifier scalars, and two MSMs (R over 16 M + 45 points, L over 2 M).  The commitments of the key are shared by the batch:
+ * their scalars are summed in Fr and each enters the MSM once.  The pairing stays with the caller (arkworks'
+ * Bn254::multi_pairing): the library holds no G2. */
+#define UZK_VERIFY_MAX_BATCH 4096
+#define UZK_VERIFY_MAX_PI 1024
+/* What PlonkVerifierParams (indexer.rs) carries, in the wire forms above: points in Montgomery form with (0,0) as infinity,
+ * scalars as 4 Montgomery words. */
+typedef struct {
+    uint32_t cs_size;                     /* verifier_params.cs_size: a power of two */
+    uint32_t n_pi;                        /* public inputs per proof (public_vars_constraint_indices.len()), <= UZK_VERIFY_MAX_PI */
+    uint32_t shuffle;                     /* as in uzk_circuit_desc.  0: cm_q_ecc, cm_shuffle_public_key and cm_shuffle_generator are
+                                             ignored, a proof has 1312 bytes and r(X) 19 scalars; else 1632 bytes and 43 */
+    uint32_t transcript_prefix_len;       /* <= 256, a multiple of 8 (the transcript of utils/transcript.rs holds 32-byte slots) */
+    const uint8_t* transcript_prefix;     /* the caller's transcript bytes in front of transcript_init_plonk; zshuffle: the label
+                                             "Plonk shuffle Proof" left-padded to 32 bytes, then n_cards as a 32-byte big-endian word */
+    const uint64_t* pi_root_powers;       /* n_pi elements: verifier_params.public_vars_constraint_indices as powers of the root */
+    const uint64_t* pi_lagrange;          /* n_pi elements: verifier_params.lagrange_constants */
+    uzk_g1_affine cm_q[9], cm_s[5], cm_qb, cm_prk[4], cm_q_ecc, cm_shuffle_public_key[12], cm_shuffle_generator[12];
+    uzk_g1_affine g1_0;                   /* the SRS's first point: the base of the value term */
+    uint64_t k[5][4], anemoi_g[4], anemoi_g_inv[4], edwards_a[4], root[4];
+} uzk_vk_desc;
+/* Makes the key resident on the calling context's device and absorbs the prefix and the key's part of transcript_init_plonk
+ * ("PLONK", cs_size, r, cm_q, cm_s, root, k: plonk/transcript.rs:9-31) into a cached Keccak sponge state -- the same for every
+ * proof under this key.  The handle is process-wide. */
+int uzk_vk_create(const uzk_vk_desc* desc, uint64_t* vk_out);
+/* No fold over the key may still be running. */
+int uzk_vk_release(uint64_t vk);
+/* cs_size, public inputs per proof, bytes per proof (1632 or 1312) and the device the key lives on; every output optional. */
+int uzk_vk_info(uint64_t vk, uint32_t* cs_size_out, uint32_t* n_pi_out, uint32_t* proof_bytes_out, int* device_out);
+/* Replaces cm_shuffle_public_key once per game (the counterpart of uzk_circuit_refresh_tables).  These commitments are not part
+ * of the transcript: the cached sponge state stays valid.  No fold over the key may still be running (on any context): a fold reads
+ * the commitments this call overwrites.  UZK_ERR_PARAMETER for a key made with shuffle == 0. */
+int uzk_vk_set_public_key(uint64_t vk, const uzk_g1_affine pk[12]);
+/* proofs       m blobs in PlonkProof::to_bytes_be's layout (indexer.rs:539-590): 1632 (1312) bytes of big-endian canonical words
+ * pi_mont      m x n_pi public inputs
+ * weights_mont m elements of Fr drawn by the CALLER after it has seen the proofs (128 random bits suffice; any element is
+ *              accepted).  NULL only with m == 1: weight 1.  NULL with m > 1 is UZK_ERR_PARAMETER -- unweighted sums let errors cancel
+ * status_out   m bytes: 0 = decoded and folded; 1 = a word is not canonical (a coordinate >= p, a scalar >= r); 2 = a point is
+ *              not on y^2 = x^3 + 3.  A proof with a nonzero status contributes NOTHING to either sum; the call still returns UZK_OK
+ *              and the caller decides what a bad proof means.  Zeros are the point at infinity, as in to_transcript_bytes
+ * challenges_out  optional, m x 7 elements: beta, gamma, alpha, zeta, u, and the challenges of PolyComScheme::batch at zeta
+ *              and at zeta omega (undefined for a proof with a nonzero status)
+ * m == 0: two points at infinity.  m > UZK_VERIFY_MAX_BATCH: UZK_ERR_PARAMETER.
+ * With m == 1 and weight 1, left_out and right_out are left_first and right_first of batch_verify_diff_points as group elements. */
+int uzk_verify_fold(uint64_t vk, const uint8_t* proofs, const uint64_t* pi_mont, uint32_t m, const uint64_t* weights_mont,
+                    uzk_g1_jac* left_out, uzk_g1_jac* right_out, uint8_t* status_out, uint64_t* challenges_out);
+
 /* ---- synthetic workloads (bench / tests; generated on device, nothing uploaded) -------- */
 /* d_points[i] = (i + 1) * Q with Q = seed_scalar * G: n distinct valid G1 points whose discrete
  * logs relative to Q are known, so MSM(points, s) == (sum_i s_i (i+1)) * Q for any size. */
@@ -592,7 +646,9 @@ int uzk_msm_plan_info(size_t n, int* window_bits, int* windows);
  *   "arith29"             bit mask, default 7: which of the prover's kernels run on the lazy 29-bit limbs (csrc/lz29.hpp) instead of
  *                         8 x 32-bit Montgomery words -- 1: the quotient kernel, 2: the lane evaluations and linear combinations,
  *                         4: the MSM's bucket-side additions (class sums, folds, the small pipeline's quads).  Same bytes either way
- * The last five exist so that the tests reach every pipeline and instantiation at sizes the CPU oracle can check
+ *   "verify_transcript"   which transcript kernel uzk_verify_fold runs: 1 one proof per lane, 2 a proof's sponge state spread over the
+ *                         lanes of a half wave (default 0: the same as 2)
+ * The last six exist so that the tests reach every pipeline and instantiation at sizes the CPU oracle can check
  * (tests/test_gpu_variants.py, tests/test_gpu_arith29.py).  Unknown keys are UZK_ERR_PARAMETER. */
 int uzk_tune(const char* key, int value);
 

@@ -51,6 +51,10 @@ int uzk_test_p29_kat(int op, const uint32_t* in, uint32_t* out, size_t n);
 int uzk_test_lanes(int op, const void* const* d_polys, const uint64_t* lane_strides, uint32_t count, const uint32_t* lens, const uint32_t* pts,
                    const uint64_t* args, uint32_t lanes, uint64_t len, uint64_t* out, int* kernel);
 
+/* Keccak-256 (padding byte 0x01) of `count` messages by the sponge of the verifier's transcript kernel (csrc/verify.hip), one lane
+ * per message: message i is bytes [offsets[i], offsets[i + 1]) of msgs (count + 1 offsets), digests_out count x 32 bytes. */
+int uzk_test_keccak256(const uint8_t* msgs, const uint64_t* offsets, uint32_t count, uint8_t* digests_out);
+
 /* ---- synthetic circuits ----
  * TEST / TIMING ONLY -- changes results.  Marks the circuit as synthetic (random polynomials no witness satisfies, the frozen
  * parity vectors and the timing chains): round 3 then takes t as its first 5 n - 2 + sum(hiding) coefficients, as

@@ -286,4 +286,52 @@ inline PreprocessedTables preprocess_tables(const ProverCommit& commit, const st
     return out;
 }
 
+// PlonkVerifierParams (uzkge/src/plonk/indexer.rs) resident on the device, for batches of proofs (uzk_vk_create): fold() runs
+// everything of the reference's verifier (verifier.rs:17-164) in front of its two pairings for m proofs at once and returns the two
+// G1 points of the ONE check  e(L, [tau] G2) = e(R, G2)  that stands for all of them.  The pairing is the caller's.
+class PlonkVerifierKey {
+  public:
+    struct Folded {
+        G1Projective left, right;
+        std::vector<uint8_t> status;      // per proof: 0 folded, 1 a non-canonical word, 2 a point off the curve (left out of both sums)
+    };
+    // `desc` and everything it points to are read before this returns.
+    explicit PlonkVerifierKey(const uzk_vk_desc& desc) {
+        check(uzk_vk_create(&desc, &handle_));
+        uint32_t cs = 0, n_pi = 0, bytes = 0;
+        int device = 0;
+        check(uzk_vk_info(handle_, &cs, &n_pi, &bytes, &device));
+        n_pi_ = n_pi;
+        proof_bytes_ = bytes;
+    }
+    PlonkVerifierKey(const PlonkVerifierKey&) = delete;
+    PlonkVerifierKey& operator=(const PlonkVerifierKey&) = delete;
+    ~PlonkVerifierKey() { if (handle_) (void)uzk_vk_release(handle_); }
+    size_t n_pi() const { return n_pi_; }
+    size_t proof_bytes() const { return proof_bytes_; }
+    // cm_shuffle_public_key of the next game (12 commitments)
+    void set_public_key(const std::vector<G1Affine>& pk) {
+        if (pk.size() != 12) throw UzkgeException(UzkgeError::ParameterError, "twelve public-key commitments");
+        check(uzk_vk_set_public_key(handle_, pk.data()));
+    }
+    // proofs: m blobs of PlonkProof::to_bytes_be back to back; pi: m x n_pi public inputs; weights: one per proof, drawn by the
+    // caller AFTER it has the proofs (empty only for one proof: weight 1)
+    Folded fold(const std::vector<uint8_t>& proofs, const std::vector<Fr>& pi, const std::vector<Fr>& weights) const {
+        if (proof_bytes_ == 0 || proofs.size() % proof_bytes_ != 0) throw UzkgeException(UzkgeError::ParameterError, "a whole number of proof blobs");
+        const size_t m = proofs.size() / proof_bytes_;
+        if (pi.size() != m * n_pi_ || !(weights.size() == m || (weights.empty() && m <= 1)))
+            throw UzkgeException(UzkgeError::ParameterError, "n_pi public inputs and one weight per proof");
+        Folded out;
+        out.status.assign(std::max<size_t>(m, 1), 0);
+        check(uzk_verify_fold(handle_, proofs.data(), reinterpret_cast<const uint64_t*>(pi.data()), (uint32_t)m,
+                              weights.empty() ? nullptr : reinterpret_cast<const uint64_t*>(weights.data()), &out.left, &out.right, out.status.data(), nullptr));
+        out.status.resize(m);
+        return out;
+    }
+
+  private:
+    uint64_t handle_ = 0;
+    size_t n_pi_ = 0, proof_bytes_ = 0;
+};
+
 }  // namespace uzkge

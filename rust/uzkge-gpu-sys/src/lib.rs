@@ -267,6 +267,60 @@ impl Drop for Circuit {
     }
 }
 
+/// A verifier key resident on the device (`uzk_vk_create`), for batches of proofs: `fold` runs everything of the reference's verifier
+/// in front of its two pairings for m proofs at once and returns the two G1 points of the ONE check e(L, [tau] G2) = e(R, G2) that
+/// stands for all of them.  The pairing is the caller's (the library holds no G2).  Process-wide; released on drop.
+pub struct VerifierKey {
+    handle: u64,
+    n_pi: usize,
+    proof_bytes: usize,
+}
+impl VerifierKey {
+    /// `desc` and everything it points to are read before this returns.
+    pub fn create(desc: &uzk_vk_desc) -> Result<Self, Error> {
+        let mut handle = 0u64;
+        check(unsafe { uzk_vk_create(desc, &mut handle) })?;
+        let (mut cs, mut n_pi, mut bytes, mut dev) = (0u32, 0u32, 0u32, 0 as c_int);
+        if let Err(e) = check(unsafe { uzk_vk_info(handle, &mut cs, &mut n_pi, &mut bytes, &mut dev) }) {
+            unsafe { uzk_vk_release(handle) };
+            return Err(e);
+        }
+        Ok(VerifierKey { handle, n_pi: n_pi as usize, proof_bytes: bytes as usize })
+    }
+    /// The public-key commitments of the next game (`uzk_vk_set_public_key`).
+    pub fn set_public_key(&self, pk: &[uzk_g1_affine; 12]) -> Result<(), Error> {
+        check(unsafe { uzk_vk_set_public_key(self.handle, pk.as_ptr()) })
+    }
+    pub fn n_pi(&self) -> usize { self.n_pi }
+    pub fn proof_bytes(&self) -> usize { self.proof_bytes }
+    /// `proofs`: m blobs of `PlonkProof::to_bytes_be`, back to back; `pi`: m x n_pi public inputs; `weights`: one element per proof,
+    /// drawn by the caller AFTER it has the proofs (None only for one proof: weight 1).  Returns (L, R, status): status[i] != 0
+    /// means proof i was malformed (1 a non-canonical word, 2 a point off the curve) and is in neither sum.
+    pub fn fold(&self, proofs: &[u8], pi: &[Limbs], weights: Option<&[Limbs]>) -> Result<(uzk_g1_jac, uzk_g1_jac, Vec<u8>), Error> {
+        if self.proof_bytes == 0 || proofs.len() % self.proof_bytes != 0 {
+            return Err(Error::Parameter);
+        }
+        let m = proofs.len() / self.proof_bytes;
+        if pi.len() != m * self.n_pi || weights.map_or(m > 1, |w| w.len() != m) {
+            return Err(Error::Parameter);
+        }
+        let (mut left, mut right) = (uzk_g1_jac::default(), uzk_g1_jac::default());
+        let mut status = vec![0u8; m.max(1)];
+        let w_ptr = weights.map_or(std::ptr::null(), |w| w.as_ptr() as *const u64);
+        check(unsafe {
+            uzk_verify_fold(self.handle, proofs.as_ptr(), pi.as_ptr() as *const u64, m as u32, w_ptr, &mut left, &mut right, status.as_mut_ptr(),
+                            std::ptr::null_mut())
+        })?;
+        status.truncate(m);
+        Ok((left, right, status))
+    }
+}
+impl Drop for VerifierKey {
+    fn drop(&mut self) {
+        unsafe { uzk_vk_release(self.handle) };
+    }
+}
+
 /// How provers of ONE proof made from now on are shared between threads (`uzk_coalesce_config`): the library runs round calls of
 /// several threads that stand at the same round of proofs over the same circuit as one lockstep launch sequence.  On by default
 /// (at most 8 proofs per sequence, the provers at work spread over 4 sequences, 2000 us gathering wait -- include/uzkge_gpu.h; 0 = a default);

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Regenerates rust/uzkge-gpu.patch: applies the `gpu`-feature edits to copies of the reference's files (read from
 /root/reference, which exists only in the build container) and writes the unified diff.  The edits are small anchors
-(cfg-gated hooks); everything of substance lives in rust/uzkge-glue/{gpu.rs, gpu_prover.rs} and rust/uzkge-gpu-sys.
+(cfg-gated hooks); everything of substance lives in rust/uzkge-glue/{gpu.rs, gpu_prover.rs, gpu_verifier.rs} and rust/uzkge-gpu-sys.
 usage: python tools/make_rust_patch.py [--check]"""
 import difflib
 import os
@@ -35,7 +35,9 @@ EDITS = {
          '/// Module for help functions.\npub(crate) mod helpers;\n\n'
          '/// `prover_with_lagrange` with the proof\'s polynomials resident on the MI355X.\n#[cfg(feature = "gpu")]\nmod gpu_prover;\n'
          '#[cfg(feature = "gpu")]\npub use gpu_prover::{prove_batch as gpu_prove_batch, release_circuits};\n'
-         '#[cfg(all(feature = "gpu", feature = "shuffle"))]\npub use gpu_prover::refresh_public_key as gpu_refresh_public_key;\n'),
+         '#[cfg(all(feature = "gpu", feature = "shuffle"))]\npub use gpu_prover::refresh_public_key as gpu_refresh_public_key;\n'
+         '\n/// A batch of proofs under one verifier key folded on the MI355X into one pairing check.\n#[cfg(feature = "gpu")]\nmod gpu_verifier;\n'
+         '#[cfg(feature = "gpu")]\npub use gpu_verifier::{release_verifier_keys, verify_batch as gpu_verify_batch};\n'),
     ],
     "shuffle/Cargo.toml": [
         ('no_vk = []\n', 'no_vk = []\n# MI355X backend (uzkge/gpu): device-resident prover and the public-key refresh as one device call\ngpu = ["uzkge/gpu"]\n'),

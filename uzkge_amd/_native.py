@@ -104,6 +104,11 @@ PROTOTYPES = {
     "uzk_prove_round4": (_I, [_U64, _P, _P, _SZ]),
     "uzk_prove_round5": (_I, [_U64, _P, _SZ, _P, _P, _P]),
     "uzk_prover_buffer": (_I, [_U64, _I, ctypes.POINTER(_P), ctypes.POINTER(_U64)]),
+    "uzk_vk_create": (_I, [_P, ctypes.POINTER(_U64)]),
+    "uzk_vk_release": (_I, [_U64]),
+    "uzk_vk_info": (_I, [_U64, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(_I)]),
+    "uzk_vk_set_public_key": (_I, [_U64, _P]),
+    "uzk_verify_fold": (_I, [_U64, _P, _P, ctypes.c_uint32, _P, _P, _P, _P, _P]),
     "uzk_synth_points_arith": (_I, [_P, _SZ, _P]),
     "uzk_synth_points_random": (_I, [_P, _SZ, _U64]),
     "uzk_synth_scalars": (_I, [_P, _SZ, _U64]),
@@ -129,6 +134,7 @@ TEST_PROTOTYPES = {
     "uzk_test_circuit_truncate_t": (_I, [_U64, _I]),
     "uzk_test_l29_kat": (_I, [_I, _I, ctypes.c_uint32, _P, _P, _SZ]),
     "uzk_test_p29_kat": (_I, [_I, _P, _P, _SZ]),
+    "uzk_test_keccak256": (_I, [_P, _P, ctypes.c_uint32, _P]),
     "uzk_test_lanes": (_I, [_I, _P, _P, ctypes.c_uint32, _P, _P, _P, ctypes.c_uint32, _U64, _P, ctypes.POINTER(ctypes.c_int)]),
 }
 
@@ -199,4 +205,21 @@ class CircuitDesc(ctypes.Structure):
         ("group_gen", ctypes.c_uint64 * 4),
         ("polys", ctypes.c_void_p * CIRCUIT_SLOTS),
         ("poly_lens", ctypes.c_uint64 * CIRCUIT_SLOTS),
+    ]
+
+
+VERIFY_MAX_BATCH = 4096
+VERIFY_MAX_PI = 1024
+_G1 = ctypes.c_uint64 * 8
+
+
+class VkDesc(ctypes.Structure):
+    """uzk_vk_desc (include/uzkge_gpu.h)."""
+    _fields_ = [
+        ("cs_size", ctypes.c_uint32), ("n_pi", ctypes.c_uint32), ("shuffle", ctypes.c_uint32), ("transcript_prefix_len", ctypes.c_uint32),
+        ("transcript_prefix", ctypes.c_void_p), ("pi_root_powers", ctypes.c_void_p), ("pi_lagrange", ctypes.c_void_p),
+        ("cm_q", _G1 * 9), ("cm_s", _G1 * 5), ("cm_qb", _G1), ("cm_prk", _G1 * 4), ("cm_q_ecc", _G1),
+        ("cm_shuffle_public_key", _G1 * 12), ("cm_shuffle_generator", _G1 * 12), ("g1_0", _G1),
+        ("k", (ctypes.c_uint64 * 4) * 5),
+        ("anemoi_g", ctypes.c_uint64 * 4), ("anemoi_g_inv", ctypes.c_uint64 * 4), ("edwards_a", ctypes.c_uint64 * 4), ("root", ctypes.c_uint64 * 4),
     ]

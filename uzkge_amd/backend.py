@@ -718,6 +718,87 @@ class Circuit:
             self.handle = 0
 
 
+class VerifierKey:
+    """A verifier key resident on the device (uzk_vk_create).  Points are wire rows of 8 words ((0,0) = infinity), scalars rows of 4;
+    `prefix`: the caller's transcript bytes in front of transcript_init_plonk."""
+
+    def __init__(self, cs_size: int, cm_q, cm_s, cm_qb, cm_prk, g1_0, k, anemoi_g, anemoi_g_inv, edwards_a, root, pi_root_powers, pi_lagrange,
+                 prefix: bytes = b"", cm_q_ecc=None, cm_shuffle_public_key=None, cm_shuffle_generator=None, shuffle: bool = True):
+        d = N.VkDesc()
+        rp = np.ascontiguousarray(pi_root_powers, dtype=np.uint64).reshape(-1, 4)
+        lc = np.ascontiguousarray(pi_lagrange, dtype=np.uint64).reshape(-1, 4)
+        assert rp.shape == lc.shape
+        pre = np.frombuffer(bytes(prefix), dtype=np.uint8).copy()
+        d.cs_size, d.n_pi, d.shuffle, d.transcript_prefix_len = cs_size, rp.shape[0], int(shuffle), pre.size
+        d.transcript_prefix = pre.ctypes.data if pre.size else None
+        d.pi_root_powers, d.pi_lagrange = (rp.ctypes.data, lc.ctypes.data) if rp.shape[0] else (None, None)
+
+        def points(name, rows, count):
+            a = np.ascontiguousarray(rows, dtype=np.uint64).reshape(count, 8)
+            dst = getattr(d, name)
+            for i in range(count):
+                row = dst if count == 1 and not isinstance(dst[0], ctypes.Array) else dst[i]
+                for w in range(8):
+                    row[w] = int(a[i, w])
+        points("cm_q", cm_q, 9); points("cm_s", cm_s, 5); points("cm_qb", cm_qb, 1); points("cm_prk", cm_prk, 4); points("g1_0", g1_0, 1)
+        if shuffle:
+            points("cm_q_ecc", cm_q_ecc, 1); points("cm_shuffle_public_key", cm_shuffle_public_key, 12); points("cm_shuffle_generator", cm_shuffle_generator, 12)
+        kk = np.ascontiguousarray(k, dtype=np.uint64).reshape(5, 4)
+        for j in range(5):
+            for w in range(4):
+                d.k[j][w] = int(kk[j, w])
+        for name, val in (("anemoi_g", anemoi_g), ("anemoi_g_inv", anemoi_g_inv), ("edwards_a", edwards_a), ("root", root)):
+            v = np.ascontiguousarray(val, dtype=np.uint64).reshape(4)
+            for w in range(4):
+                getattr(d, name)[w] = int(v[w])
+        h = ctypes.c_uint64(0)
+        check(lib.uzk_vk_create(ctypes.byref(d), ctypes.byref(h)))
+        self.handle = h.value
+        self.cs_size, self.n_pi, self.proof_bytes, self.device = self.info()
+
+    def info(self):
+        """(cs_size, public inputs per proof, bytes per proof, device)."""
+        a, b, c, dv = ctypes.c_uint32(0), ctypes.c_uint32(0), ctypes.c_uint32(0), ctypes.c_int(0)
+        check(lib.uzk_vk_info(self.handle, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c), ctypes.byref(dv)))
+        return a.value, b.value, c.value, dv.value
+
+    def set_public_key(self, pk) -> None:
+        a = np.ascontiguousarray(pk, dtype=np.uint64).reshape(12, 8)
+        check(lib.uzk_vk_set_public_key(self.handle, _ptr(a)))
+
+    def fold(self, proofs, pis, weights=None, want_challenges: bool = False):
+        """uzk_verify_fold: proofs = m blobs (bytes, or a uint8 array [m, proof_bytes]), pis [m, n_pi, 4], weights [m, 4] or None
+        (m == 1 only).  Returns (left [12], right [12], status [m]) and, when asked, the challenges [m, 7, 4]."""
+        raw = np.frombuffer(bytes(proofs), dtype=np.uint8) if isinstance(proofs, (bytes, bytearray)) else np.ascontiguousarray(proofs, dtype=np.uint8)
+        assert raw.size % self.proof_bytes == 0, "proofs: a whole number of %d-byte blobs" % self.proof_bytes
+        m = raw.size // self.proof_bytes
+        pi = np.ascontiguousarray(pis, dtype=np.uint64).reshape(m, self.n_pi, 4)
+        w = None if weights is None else np.ascontiguousarray(weights, dtype=np.uint64).reshape(m, 4)
+        left, right = np.zeros(12, dtype=np.uint64), np.zeros(12, dtype=np.uint64)
+        status = np.zeros(max(m, 1), dtype=np.uint8)
+        ch = np.zeros((m, 7, 4), dtype=np.uint64) if want_challenges else None
+        vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+        check(lib.uzk_verify_fold(self.handle, vp(raw), vp(pi), m, None if w is None else _ptr(w), _ptr(left), _ptr(right), vp(status),
+                                  _ptr(ch) if want_challenges else None))
+        return (left, right, status[:m], ch) if want_challenges else (left, right, status[:m])
+
+    def release(self) -> None:
+        if self.handle:
+            check(lib.uzk_vk_release(self.handle))
+            self.handle = 0
+
+
+def keccak256_device(messages) -> list:
+    """uzk_test_keccak256 (test hook): the digests of the messages by the device's transcript sponge."""
+    offs = np.zeros(len(messages) + 1, dtype=np.uint64)
+    offs[1:] = np.cumsum([len(x) for x in messages])
+    blob = np.frombuffer(b"".join(messages) + b"\0", dtype=np.uint8).copy()
+    out = np.zeros((len(messages), 32), dtype=np.uint8)
+    vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+    check(lib.uzk_test_keccak256(vp(blob), vp(offs), len(messages), vp(out)))
+    return [bytes(r) for r in out]
+
+
 def preprocess_tables_device(srs: Srs, evals: np.ndarray, k1=None, want_coset: bool = False, want_commit: bool = True):
     """uzk_preprocess_tables: [count, n, 4] evaluation vectors -> (polys [count, n, 4], lens, coset [count, 6n, 4] | None,
     commitments [count, 12] | None).  Without commitments the SRS handle is not looked at (srs may be None)."""

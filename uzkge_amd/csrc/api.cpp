@@ -223,6 +223,7 @@ static void ctx_release(Ctx& c) {
     (void)hipStreamSynchronize(c.stream);
     ntt_free_plans(c);
     g1ntt_free(c);
+    c.verify_ws.release();
     msm_free(c);
     poly_free(c);
     c.ntt_scratch[0].release(); c.ntt_scratch[1].release(); c.ntt_io.release(); c.msm_scalars.release();
@@ -310,6 +311,7 @@ int uzk_shutdown(void) try {
     coalesce_release_all();                // shared provers, their workspaces and internal contexts
     sharded_release_all();                 // sharded SRSs: their chunks' contexts and registry entries
     prover_release_all();                  // circuits and provers own device memory (takes Shared::mu itself)
+    vf_release_all();                      // verifier keys
     std::lock_guard<std::mutex> lk(s.mu);
     if (!s.bound) return UZK_OK;
     ctx_release(default_ctx());
@@ -337,7 +339,7 @@ namespace uzk {
 static void copy_tuning(const Ctx& from, Ctx& to) {
     to.msm_window_bits = from.msm_window_bits;
     to.tune_no_precompute = from.tune_no_precompute; to.tune_ntt_tile = from.tune_ntt_tile; to.tune_ntt_two_pass = from.tune_ntt_two_pass; to.tune_small = from.tune_small;
-    to.tune_chunk_log = from.tune_chunk_log; to.tune_stream_log = from.tune_stream_log; to.tune_stream_min_log = from.tune_stream_min_log;
+    to.tune_chunk_log = from.tune_chunk_log; to.tune_verify_transcript = from.tune_verify_transcript; to.tune_stream_log = from.tune_stream_log; to.tune_stream_min_log = from.tune_stream_min_log;
     to.tune_seg_sort = from.tune_seg_sort; to.tune_arith29 = from.tune_arith29;
 }
 }  // namespace uzk
@@ -1036,6 +1038,64 @@ int uzk_srs_download(uint64_t handle, size_t offset, size_t n, uzk_g1_affine* ou
     return UZK_OK;
 } catch (...) { return uzk::on_exception("uzk_srs_download"); }
 
+/* ---- batch verification -------------------------------------------------------------------- */
+int uzk_vk_create(const uzk_vk_desc* desc, uint64_t* vk_out) try {
+    API_LOCK;
+    if (!desc || !vk_out) { set_error("uzk_vk_create: null pointer"); return UZK_ERR_PARAMETER; }
+    UZK_TRY(vf_key_check(desc));
+    UZK_TRY(require_ready());
+    return vf_key_create(ctx(), desc, vk_out);
+} catch (...) { return uzk::on_exception("uzk_vk_create"); }
+
+int uzk_vk_release(uint64_t vk) try {
+    API_LOCK;
+    return vf_key_release(vk);
+} catch (...) { return uzk::on_exception("uzk_vk_release"); }
+
+int uzk_vk_info(uint64_t vk, uint32_t* cs_size_out, uint32_t* n_pi_out, uint32_t* proof_bytes_out, int* device_out) try {
+    if (!vf_key_known(vk, cs_size_out, n_pi_out, proof_bytes_out, device_out)) { set_error("uzk_vk_info: unknown verifier key %llu", (unsigned long long)vk); return UZK_ERR_PARAMETER; }
+    return UZK_OK;
+} catch (...) { return uzk::on_exception("uzk_vk_info"); }
+
+int uzk_vk_set_public_key(uint64_t vk, const uzk_g1_affine pk[12]) try {
+    API_LOCK;
+    if (!pk) { set_error("uzk_vk_set_public_key: null pointer"); return UZK_ERR_PARAMETER; }
+    if (!vf_key_known(vk, nullptr, nullptr, nullptr, nullptr)) { set_error("uzk_vk_set_public_key: unknown verifier key %llu", (unsigned long long)vk); return UZK_ERR_PARAMETER; }
+    UZK_TRY(require_ready());
+    return vf_key_set_public_key(ctx(), vk, reinterpret_cast<const Affine*>(pk));
+} catch (...) { return uzk::on_exception("uzk_vk_set_public_key"); }
+
+int uzk_verify_fold(uint64_t vk, const uint8_t* proofs, const uint64_t* pi_mont, uint32_t m, const uint64_t* weights_mont, uzk_g1_jac* left_out,
+                    uzk_g1_jac* right_out, uint8_t* status_out, uint64_t* challenges_out) try {
+    API_LOCK;
+    if (m > UZK_VERIFY_MAX_BATCH) { set_error("uzk_verify_fold: %u proofs (at most %d per call)", m, UZK_VERIFY_MAX_BATCH); return UZK_ERR_PARAMETER; }
+    if (m > 1 && !weights_mont) { set_error("uzk_verify_fold: %u proofs need a weight each (unweighted sums let errors cancel)", m); return UZK_ERR_PARAMETER; }
+    if (!left_out || !right_out || (m > 0 && (!proofs || !status_out))) { set_error("uzk_verify_fold: null pointer"); return UZK_ERR_PARAMETER; }
+    uint32_t n_pi = 0;
+    if (!vf_key_known(vk, nullptr, &n_pi, nullptr, nullptr)) { set_error("uzk_verify_fold: unknown verifier key %llu", (unsigned long long)vk); return UZK_ERR_PARAMETER; }
+    if (m > 0 && n_pi > 0 && !pi_mont) { set_error("uzk_verify_fold: null public inputs"); return UZK_ERR_PARAMETER; }
+    Jac l = jac_inf(), r = jac_inf();
+    if (m > 0) {
+        UZK_TRY(require_ready());
+        UZK_TRY(vf_fold_run(ctx(), vk, proofs, as_fp(pi_mont), m, weights_mont ? as_fp(weights_mont) : nullptr, &l, &r, status_out,
+                            reinterpret_cast<Fp*>(challenges_out)));
+    }
+    std::memcpy(left_out, &l, sizeof l);
+    std::memcpy(right_out, &r, sizeof r);
+    return UZK_OK;
+} catch (...) { return uzk::on_exception("uzk_verify_fold"); }
+
+int uzk_test_keccak256(const uint8_t* msgs, const uint64_t* offsets, uint32_t count, uint8_t* digests_out) try {
+    API_LOCK;
+    if (!offsets || (count > 0 && !digests_out) || (count > 0 && offsets[count] > offsets[0] && !msgs)) { set_error("uzk_test_keccak256: null pointer"); return UZK_ERR_PARAMETER; }
+    for (uint32_t i = 0; i < count; ++i) {
+        if (offsets[i + 1] < offsets[i] || offsets[0] != 0) { set_error("uzk_test_keccak256: offsets must start at 0 and not decrease"); return UZK_ERR_PARAMETER; }
+    }
+    if (count == 0) return UZK_OK;
+    UZK_TRY(require_ready());
+    return vf_keccak_test(ctx(), msgs, offsets, count, digests_out);
+} catch (...) { return uzk::on_exception("uzk_test_keccak256"); }
+
 /* ---- polynomial helpers next to the hot path ------------------------------------------------ */
 int uzk_poly_eval_batch(const uint64_t* coefs, uint64_t n, uint32_t batch, const uint64_t* x_mont, uint64_t* out) try {
     API_LOCK;
@@ -1348,6 +1408,7 @@ int uzk_tune(const char* key, int value) try {
     else if (!std::strcmp(key, "ntt_tile")) c.tune_ntt_tile = (value == 1024 || value == 2048) ? value : 0;
     else if (!std::strcmp(key, "ntt_two_pass")) c.tune_ntt_two_pass = value ? 1 : 0;
     else if (!std::strcmp(key, "arith29")) c.tune_arith29 = value & 7;
+    else if (!std::strcmp(key, "verify_transcript")) c.tune_verify_transcript = (value == 1 || value == 2) ? value : 0;
     else { set_error("uzk_tune: unknown key %s", key); return UZK_ERR_PARAMETER; }
     return UZK_OK;
 } catch (...) { return uzk::on_exception("uzk_tune"); }

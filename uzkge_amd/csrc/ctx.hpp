@@ -137,6 +137,9 @@ struct Ctx {
     // conversion to affine, staging for the host-pointer API (grow-only)
     std::map<uint64_t, void*> g1ntt_plans;
     DevBuf g1ntt_work, g1ntt_prefix, g1ntt_io;
+    // verify.hip: one block carved into the arrays of a fold (proofs, decoded words, challenges, coefficients, the MSMs' inputs)
+    DevBuf verify_ws;
+    int tune_verify_transcript = 0;   // which transcript kernel a fold runs: 1 one proof per lane; 0 / 2 a proof's state spread over a half wave (the default)
     // an entry of the process-wide SRS registry
     struct Srs {
         Affine* d_points = nullptr;
@@ -230,6 +233,16 @@ void ntt_free_plans(Ctx& c);
 int g1ntt_run(Ctx& c, const Affine* d_in, Affine* d_out, uint64_t n, bool inverse);
 void g1ntt_op_count(uint64_t n, bool inverse, uint64_t* dbl_out, uint64_t* add_out);
 void g1ntt_free(Ctx& c);
+// verify.hip: verifier keys (process-wide handles) and the fold of a batch of proofs
+int vf_key_check(const uzk_vk_desc* d);
+int vf_key_create(Ctx& c, const uzk_vk_desc* d, uint64_t* out);
+bool vf_key_known(uint64_t h, uint32_t* cs_size, uint32_t* n_pi, uint32_t* proof_bytes, int* device);
+int vf_key_release(uint64_t h);
+void vf_release_all();
+int vf_key_set_public_key(Ctx& c, uint64_t h, const Affine* pk);
+int vf_fold_run(Ctx& c, uint64_t h, const uint8_t* proofs, const Fp* pi, uint32_t m, const Fp* weights, Jac* left_out, Jac* right_out,
+                uint8_t* status_out, Fp* challenges_out);
+int vf_keccak_test(Ctx& c, const uint8_t* msgs, const uint64_t* offsets, uint32_t count, uint8_t* out);
 void msm_plan_info(Ctx& c, size_t n, int* window_bits, int* windows);
 int msm_run(Ctx& c, const Affine* points, const ScalarView& scalars, size_t n, uint32_t batch, Jac* out_host, int pre_c,
             uint32_t pre_stride, uint32_t pre_off);

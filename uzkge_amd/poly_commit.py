@@ -418,6 +418,62 @@ def preprocess_tables(commit: ProverCommit, evals: np.ndarray, m: int, k1: np.nd
     return (coefs.cpu().numpy().view(np.uint64), coset.cpu().numpy().view(np.uint64), cms)
 
 
+def fq_from_int(x: int) -> np.ndarray:
+    return _to_wire(x % FQ_MODULUS, FQ_MODULUS)
+
+
+def g1_wire(point) -> np.ndarray:
+    """(x, y) as integers, or None for the point at infinity -> the 8-word wire row."""
+    if point is None:
+        return np.zeros(8, dtype=np.uint64)
+    return np.concatenate([fq_from_int(int(point[0])), fq_from_int(int(point[1]))])
+
+
+class PlonkVerifierKey:
+    """PlonkVerifierParams (uzkge/src/plonk/indexer.rs) resident on the device, for batches of proofs: `fold` runs everything of the
+    verifier (verifier.rs:17-164) in front of its two pairings for m proofs at once and returns the two G1 points of the ONE check
+        e(L, [tau] G2) = e(R, G2)
+    that stands for all of them.  The pairing is the caller's: this library holds no G2.
+
+    vk: the key as integers -- cm_q (9 points), cm_s (5), cm_qb, cm_prk (4), k (5), anemoi_g, anemoi_g_inv, edwards_a, root, cs_size,
+    pi_root_powers, pi_lagrange and, with the shuffle feature, cm_q_ecc, cm_shuffle_public_key (12), cm_shuffle_generator (12);
+    points are (x, y) or None.  g1_0: the SRS's first point (default: the generator, as in the reference's parameters).
+    prefix: the transcript bytes in front of transcript_init_plonk."""
+
+    def __init__(self, vk: dict, prefix: bytes = b"", g1_0=(1, 2), shuffle: bool = True):
+        pts = lambda rows: np.stack([g1_wire(p) for p in rows])
+        frs = lambda vals: np.stack([fr_from_int(int(v)) for v in vals]) if len(vals) else np.zeros((0, 4), dtype=np.uint64)
+        extra = dict(cm_q_ecc=g1_wire(vk["cm_q_ecc"]), cm_shuffle_public_key=pts(vk["cm_shuffle_public_key"]),
+                     cm_shuffle_generator=pts(vk["cm_shuffle_generator"])) if shuffle else {}
+        self.key = B.VerifierKey(int(vk["cs_size"]), pts(vk["cm_q"]), pts(vk["cm_s"]), g1_wire(vk["cm_qb"]), pts(vk["cm_prk"]), g1_wire(g1_0),
+                                 frs(vk["k"]), fr_from_int(vk["anemoi_g"]), fr_from_int(vk["anemoi_g_inv"]), fr_from_int(vk["edwards_a"]),
+                                 fr_from_int(vk["root"]), frs(vk["pi_root_powers"]), frs(vk["pi_lagrange"]), prefix=prefix, shuffle=shuffle, **extra)
+        self.n_pi, self.proof_bytes = self.key.n_pi, self.key.proof_bytes
+
+    def set_public_key(self, commitments) -> None:
+        """cm_shuffle_public_key of the next game (12 points)."""
+        self.key.set_public_key(np.stack([g1_wire(p) for p in commitments]))
+
+    def fold(self, proofs: Sequence[bytes], pis: Sequence[Sequence[int]], weights: Optional[Sequence[int]] = None):
+        """proofs: m blobs of PlonkProof::to_bytes_be; pis: m lists of n_pi integers; weights: m integers the CALLER draws after it has
+        the proofs (None only for one proof: weight 1).  Returns (L, R, status): two Jacobian wire points [12] and one byte per proof
+        (0 folded, 1 a non-canonical word, 2 a point off the curve -- such a proof is left out of both sums)."""
+        m = len(proofs)
+        if m != len(pis) or (weights is not None and len(weights) != m) or any(len(p) != self.proof_bytes for p in proofs):
+            raise UzkgeError(N.UZK_ERR_PARAMETER, "PlonkVerifierKey.fold: one proof blob, one list of public inputs and one weight per proof")
+        pi = np.zeros((m, self.n_pi, 4), dtype=np.uint64)
+        for i, row in enumerate(pis):
+            if len(row) != self.n_pi:
+                raise UzkgeError(N.UZK_ERR_PARAMETER, "PlonkVerifierKey.fold: %d public inputs per proof" % self.n_pi)
+            for j, v in enumerate(row):
+                pi[i, j] = fr_from_int(int(v))
+        w = None if weights is None else np.stack([fr_from_int(int(v)) for v in weights]) if m else np.zeros((0, 4), dtype=np.uint64)
+        return self.key.fold(b"".join(proofs), pi, w)
+
+    def release(self) -> None:
+        self.key.release()
+
+
 def hide_polynomial(polynomial: FpPolynomial, blinds: np.ndarray, zeroing_degree: int) -> FpPolynomial:
     """helpers.rs:139-158 with the random blinds given: adds (b_0 + b_1 X + ...) * (X^zeroing_degree - 1)."""
     b = np.ascontiguousarray(blinds, dtype=np.uint64).reshape(-1, 4)
