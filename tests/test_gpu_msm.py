@@ -230,11 +230,16 @@ def test_switches_do_not_change_the_result(gpu):
         srs.release()
 
 
-@pytest.mark.parametrize("n,stream_log", [(4096, 10), (5000, 10), (16384, 12), (100000, 14), (100000, 0)])
+@pytest.mark.parametrize("n,stream_log", [(4096, 10), (5000, 10), (16384, 12), (100000, 14), (100000, 0), (3 * 65536 + 5, 16)])
 def test_streamed_host_scalar_msm(gpu, n, stream_log):
     """uzk_msm_g1 on host scalars streams large general-mode MSMs in point chunks that share one bucket set (the chunk's
     bucket sums are added onto the previous ones, one reduction at the end).  With the thresholds lowered the same code runs
-    at sizes the oracle checks: uniform chunks, a ragged last chunk, and the graded default schedule."""
+    at sizes the oracle checks.  msm_run_streamed raises a chunk size of 2^1 .. 2^15 to 2^16, and its graded default schedule
+    (msm_stream_log 0) starts at 2^20 points, so the cases run:
+        (4096, 10), (5000, 10), (16384, 12)   one chunk
+        (100000, 0)                           one chunk
+        (100000, 14)                          two chunks, 65536 + 34464: the second one is added onto the first
+        (3 * 65536 + 5, 16)                   four chunks, three uniform ones and a ragged last one of five points"""
     wire, _ = load_srs("lagrange-srs-16384.bin")
     pts = np.concatenate([wire] * ((n + 16383) // 16384))[:n]
     srs = gpu.Srs.from_host(pts)
