@@ -244,6 +244,50 @@ int uzk_srs_download(uint64_t handle, size_t offset, size_t n, uzk_g1_affine* ou
 /* Group operations one transform of size n runs (doublings, additions), counted from its plan: tools/g1_ntt_shape.py. */
 int uzk_ntt_g1_plan_info(uint64_t n, int inverse, uint64_t* doublings_out, uint64_t* additions_out);
 
+/* ---- SRS validation: curve check and powers-of-tau fold ----------------------------------------------------------------------
+ * uzk_srs_register* copies 64-byte words and trusts them, as the reference does (from_unchecked_bytes, Validate::No,
+ * kzg_poly_commitment.rs:228-256).  An off-curve base does not fail an MSM: it runs through the addition formulas of another curve
+ * and gives a commitment that looks like any other; a base set that is not [tau^i] G makes commitments that bind to nothing.  These
+ * entry points are the check, on the device.  A handle of uzk_srs_register_sharded is not accepted (UZK_ERR_PARAMETER).
+ *
+ * uzk_srs_check_curve classifies the points P[offset .. offset + count) of a handle; every point falls into exactly one class,
+ * checked = infinity + non_canonical + off_curve + good ones.  BN254 G1 has cofactor 1: a point on the curve is in the group, no
+ * subgroup check is needed.  count = 0 is an empty report.
+ *
+ * uzk_srs_fold_powers folds the count - 1 equations P[i + 1] = tau P[i] of a run under random 128-bit weights into two points:
+ *   left = sum_{i < count-1} rho_i P[offset+i]      right = sum_{i < count-1} rho_i P[offset+i+1]
+ * and the run is a power sequence of tau  <=>  e(right, H) = e(left, [tau] H), except with probability 2^-128 over the seed.
+ * Draw the seed AFTER the points are fixed.  The library has no G2: the pairing check, whether H and [tau] H are good G2 points,
+ * and whether P[0] is the generator the caller expects stay with the caller.  Points at infinity inside a run contribute the
+ * identity, as in every MSM here (the curve report is where the caller sees them); run the curve check first -- the fold of a run
+ * with off-curve points means nothing.
+ *
+ * Weights: block j = Keccak-256 (padding byte 0x01, the transcript's sponge) of the 48-byte message seed || "uzksrsv1" || le64(j);
+ * rho_2j = digest bytes 0..15, rho_2j+1 = bytes 16..31, little-endian integers < 2^128.  The device expands the seed itself.
+ *
+ * Errors: unknown handle or one of another device, null pointer, count < 2 for a fold -> UZK_ERR_PARAMETER;
+ * offset + count > uzk_srs_len -> UZK_ERR_DEGREE; n not a size of uzk_ntt_g1_supported -> UZK_ERR_FFT. */
+typedef struct {
+    uint64_t checked;        /* points looked at (= count) */
+    uint64_t infinity;       /* encoded (0,0) */
+    uint64_t non_canonical;  /* a coordinate, read as a 256-bit integer, >= p */
+    uint64_t off_curve;      /* canonical, not (0,0), y^2 != x^3 + 3 */
+    uint64_t first_bad;      /* smallest index (relative to the handle, i.e. offset included) of a non-canonical
+                                or off-curve point; UINT64_MAX if there is none */
+} uzk_srs_curve_report;
+int uzk_srs_check_curve(uint64_t handle, size_t offset, size_t count, uzk_srs_curve_report* out);
+/* Host only, no device needed: weights first .. first + count - 1 of `seed`, Montgomery form, 4 limbs each (what the device
+ * derives for a fold; first + count must not exceed 2^64 - 1). */
+int uzk_srs_fold_weights(const uint8_t seed[32], uint64_t first, uint64_t count, uint64_t* out_mont);
+/* The run P[offset .. offset + count), count >= 2; left_out / right_out as above. */
+int uzk_srs_fold_powers(uint64_t handle, size_t offset, size_t count, const uint8_t seed[32], uzk_g1_jac* left_out,
+                        uzk_g1_jac* right_out);
+/* The same over M = the forward G1 transform of the first n points of a Lagrange handle (n: uzk_ntt_g1_supported, n >= 2), which
+ * must be a power sequence if the handle holds [L_i(tau)] G.  first_out = M[0] = sum_i L_i, which the caller compares with G.
+ * n > uzk_srs_len -> UZK_ERR_DEGREE. */
+int uzk_srs_fold_powers_lagrange(uint64_t lagrange_handle, uint64_t n, const uint8_t seed[32], uzk_g1_affine* first_out,
+                                 uzk_g1_jac* left_out, uzk_g1_jac* right_out);
+
 /* ---- polynomial helpers next to the hot path ------------------------ */
 /* out[b] = sum_j coefs[b*n + j] * x^j : FpPolynomial::eval (field_polynomial.rs:198-209) for a batch of
  * polynomials at one point (the prover's 19 + 20 openings at zeta / zeta*omega, prover.rs:246-273). */

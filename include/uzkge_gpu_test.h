@@ -55,6 +55,10 @@ int uzk_test_lanes(int op, const void* const* d_polys, const uint64_t* lane_stri
  * per message: message i is bytes [offsets[i], offsets[i + 1]) of msgs (count + 1 offsets), digests_out count x 32 bytes. */
 int uzk_test_keccak256(const uint8_t* msgs, const uint64_t* offsets, uint32_t count, uint8_t* digests_out);
 
+/* Weights 0 .. count - 1 of `seed` as the device kernel of uzk_srs_fold_powers writes them (csrc/srscheck.hip), copied back:
+ * count x 4 limbs, Montgomery form.  uzk_srs_fold_weights is the host's run of the same code. */
+int uzk_test_srs_weights_device(const uint8_t seed[32], uint64_t count, uint64_t* out_mont);
+
 /* ---- synthetic circuits ----
  * TEST / TIMING ONLY -- changes results.  Marks the circuit as synthetic (random polynomials no witness satisfies, the frozen
  * parity vectors and the timing chains): round 3 then takes t as its first 5 n - 2 + sum(hiding) coefficients, as

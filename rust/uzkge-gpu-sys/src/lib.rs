@@ -97,6 +97,21 @@ impl Srs {
         check(unsafe { uzk_srs_download(self.handle, offset, n, out.as_mut_ptr()) })?;
         Ok(out)
     }
+    /// Are the points `[offset, offset + count)` curve points?  (`uzk_srs_check_curve`; the reference loads its parameters with
+    /// `Validate::No`, kzg_poly_commitment.rs:228-256.)  BN254 G1 has cofactor 1: on the curve is in the group.
+    pub fn check_curve(&self, offset: usize, count: usize) -> Result<uzk_srs_curve_report, Error> {
+        let mut out = uzk_srs_curve_report::default();
+        check(unsafe { uzk_srs_check_curve(self.handle, offset, count, &mut out) })?;
+        Ok(out)
+    }
+    /// `(left, right)` of the run `[offset, offset + count)`, `count >= 2`, under the 128-bit weights of `seed` (drawn after the
+    /// points are fixed): the run is a power sequence of tau iff `e(right, H) == e(left, [tau] H)` -- the caller's pairing, over
+    /// G2 points the caller has checked (`uzk_srs_fold_powers`).
+    pub fn fold_powers(&self, offset: usize, count: usize, seed: &[u8; 32]) -> Result<(uzk_g1_jac, uzk_g1_jac), Error> {
+        let (mut left, mut right) = (uzk_g1_jac::default(), uzk_g1_jac::default());
+        check(unsafe { uzk_srs_fold_powers(self.handle, offset, count, seed.as_ptr(), &mut left, &mut right) })?;
+        Ok((left, right))
+    }
 }
 
 impl Srs {

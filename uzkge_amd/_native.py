@@ -70,6 +70,10 @@ PROTOTYPES = {
     "uzk_srs_to_lagrange": (_I, [_U64, _U64, ctypes.POINTER(_U64)]),
     "uzk_srs_download": (_I, [_U64, _SZ, _SZ, _P]),
     "uzk_ntt_g1_plan_info": (_I, [_U64, _I, ctypes.POINTER(_U64), ctypes.POINTER(_U64)]),
+    "uzk_srs_check_curve": (_I, [_U64, _SZ, _SZ, _P]),
+    "uzk_srs_fold_weights": (_I, [_P, _U64, _U64, _P]),
+    "uzk_srs_fold_powers": (_I, [_U64, _SZ, _SZ, _P, _P, _P]),
+    "uzk_srs_fold_powers_lagrange": (_I, [_U64, _U64, _P, _P, _P, _P]),
     "uzk_hide_polynomial_batch_device": (_I, [_P, _U64, _U64, ctypes.c_uint32, _P, ctypes.c_uint32, _U64]),
     "uzk_fold_blinds_batch_device": (_I, [_P, _U64, _P, _U64, ctypes.c_uint32, _P, _U64, _P, ctypes.c_uint32, _P]),
     "uzk_poly_trimmed_len_device": (_I, [_P, _U64, _P, ctypes.c_uint32, _P, _I]),
@@ -135,6 +139,7 @@ TEST_PROTOTYPES = {
     "uzk_test_l29_kat": (_I, [_I, _I, ctypes.c_uint32, _P, _P, _SZ]),
     "uzk_test_p29_kat": (_I, [_I, _P, _P, _SZ]),
     "uzk_test_keccak256": (_I, [_P, _P, ctypes.c_uint32, _P]),
+    "uzk_test_srs_weights_device": (_I, [_P, _U64, _P]),
     "uzk_test_lanes": (_I, [_I, _P, _P, ctypes.c_uint32, _P, _P, _P, ctypes.c_uint32, _U64, _P, ctypes.POINTER(ctypes.c_int)]),
 }
 
@@ -223,3 +228,9 @@ class VkDesc(ctypes.Structure):
         ("k", (ctypes.c_uint64 * 4) * 5),
         ("anemoi_g", ctypes.c_uint64 * 4), ("anemoi_g_inv", ctypes.c_uint64 * 4), ("edwards_a", ctypes.c_uint64 * 4), ("root", ctypes.c_uint64 * 4),
     ]
+
+
+class SrsCurveReport(ctypes.Structure):
+    """uzk_srs_curve_report (include/uzkge_gpu.h)."""
+    _fields_ = [("checked", ctypes.c_uint64), ("infinity", ctypes.c_uint64), ("non_canonical", ctypes.c_uint64), ("off_curve", ctypes.c_uint64),
+                ("first_bad", ctypes.c_uint64)]

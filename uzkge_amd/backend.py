@@ -146,10 +146,58 @@ class Srs:
         check(lib.uzk_srs_download(self.handle, offset, n, _ptr(out) if out.shape[0] else None))
         return out
 
+    def check_curve(self, offset: int = 0, count: Optional[int] = None) -> dict:
+        """uzk_srs_check_curve over points [offset, offset + count): {"checked", "infinity", "non_canonical", "off_curve",
+        "first_bad"}; first_bad is an index into the SRS, None when every point is on the curve or the identity."""
+        if count is None:
+            count = self.n - offset
+        r = N.SrsCurveReport()
+        check(lib.uzk_srs_check_curve(self.handle, offset, count, ctypes.byref(r)))
+        return {"checked": r.checked, "infinity": r.infinity, "non_canonical": r.non_canonical, "off_curve": r.off_curve,
+                "first_bad": None if r.first_bad == 2 ** 64 - 1 else r.first_bad}
+
+    def fold_powers(self, seed: bytes, offset: int = 0, count: Optional[int] = None):
+        """uzk_srs_fold_powers: (left [12], right [12]) of the run [offset, offset + count) under the weights of the 32-byte seed;
+        the run is a power sequence of tau iff e(right, H) = e(left, [tau] H) -- the caller's pairing."""
+        if count is None:
+            count = self.n - offset
+        left, right = np.zeros(12, dtype=np.uint64), np.zeros(12, dtype=np.uint64)
+        check(lib.uzk_srs_fold_powers(self.handle, offset, count, _seed(seed), _ptr(left), _ptr(right)))
+        return left, right
+
+    def fold_powers_lagrange(self, seed: bytes, n: int):
+        """uzk_srs_fold_powers_lagrange: (first [8], left [12], right [12]) over the forward G1 transform of the first n points of
+        this (Lagrange) SRS; first = sum_i L_i, the generator if the bases are what they claim to be."""
+        first, left, right = np.zeros(8, dtype=np.uint64), np.zeros(12, dtype=np.uint64), np.zeros(12, dtype=np.uint64)
+        check(lib.uzk_srs_fold_powers_lagrange(self.handle, n, _seed(seed), _ptr(first), _ptr(left), _ptr(right)))
+        return first, left, right
+
     def release(self) -> None:
         if self.handle:
             check(lib.uzk_srs_release(self.handle))
             self.handle = 0
+
+
+def _seed(seed: bytes):
+    s = bytes(seed)
+    if len(s) != 32:
+        from .errors import UzkgeError
+        raise UzkgeError(N.UZK_ERR_PARAMETER, "a fold seed is 32 bytes, got %d" % len(s))
+    return ctypes.c_char_p(s)
+
+
+def srs_fold_weights(seed: bytes, first: int, count: int) -> np.ndarray:
+    """uzk_srs_fold_weights (host only): weights first .. first + count - 1 of the seed, [count, 4] Montgomery limbs."""
+    out = np.zeros((count, 4), dtype=np.uint64)
+    check(lib.uzk_srs_fold_weights(_seed(seed), first, count, _ptr(out) if count else None))
+    return out
+
+
+def srs_fold_weights_device(seed: bytes, count: int) -> np.ndarray:
+    """uzk_test_srs_weights_device (test hook): weights 0 .. count - 1 as the device kernel writes them."""
+    out = np.zeros((count, 4), dtype=np.uint64)
+    check(lib.uzk_test_srs_weights_device(_seed(seed), count, _ptr(out) if count else None))
+    return out
 
 
 def msm(srs: Srs, scalars: np.ndarray, offset: int = 0) -> np.ndarray:

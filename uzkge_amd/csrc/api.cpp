@@ -223,6 +223,7 @@ static void ctx_release(Ctx& c) {
     (void)hipStreamSynchronize(c.stream);
     ntt_free_plans(c);
     g1ntt_free(c);
+    srscheck_free(c);
     c.verify_ws.release();
     msm_free(c);
     poly_free(c);
@@ -1037,6 +1038,116 @@ int uzk_srs_download(uint64_t handle, size_t offset, size_t n, uzk_g1_affine* ou
     UZK_HIP(hipStreamSynchronize(c.stream));
     return UZK_OK;
 } catch (...) { return uzk::on_exception("uzk_srs_download"); }
+
+/* ---- SRS validation: curve check and powers-of-tau fold -------------------------------------- */
+// the handle and the range P[offset .. offset + count) of a validation call; needs no device
+static int srs_range_checked(const char* who, uint64_t handle, size_t offset, size_t count, Ctx::Srs* s) {
+    if (!srs_lookup(handle, s)) { set_error("%s: unknown SRS handle %llu", who, (unsigned long long)handle); return UZK_ERR_PARAMETER; }
+    if (offset > s->n || count > s->n - offset) { set_error("%s: offset %zu + count %zu exceeds SRS length %zu", who, offset, count, s->n); return UZK_ERR_DEGREE; }
+    return UZK_OK;
+}
+static int srs_device_checked(const char* who, const Ctx::Srs& s, const Ctx& c) {
+    if (s.device != c.device) { set_error("%s: the SRS lives on device %d, the calling context on device %d", who, s.device, c.device); return UZK_ERR_PARAMETER; }
+    return UZK_OK;
+}
+
+int uzk_srs_check_curve(uint64_t handle, size_t offset, size_t count, uzk_srs_curve_report* out) try {
+    API_LOCK;
+    if (!out) { set_error("uzk_srs_check_curve: null pointer"); return UZK_ERR_PARAMETER; }
+    Ctx::Srs s;
+    UZK_TRY(srs_range_checked("uzk_srs_check_curve", handle, offset, count, &s));
+    UZK_TRY(require_ready());
+    Ctx& c = ctx();
+    UZK_TRY(srs_device_checked("uzk_srs_check_curve", s, c));
+    uzk_srs_curve_report r;
+    UZK_TRY(srs_curve_run(c, s.d_points + offset, count, &r));
+    if (r.first_bad != UINT64_MAX) r.first_bad += offset;
+    *out = r;
+    return UZK_OK;
+} catch (...) { return uzk::on_exception("uzk_srs_check_curve"); }
+
+int uzk_srs_fold_weights(const uint8_t seed[32], uint64_t first, uint64_t count, uint64_t* out_mont) try {
+    if (!seed || (count > 0 && !out_mont)) { set_error("uzk_srs_fold_weights: null pointer"); return UZK_ERR_PARAMETER; }
+    if (count > UINT64_MAX - first) { set_error("uzk_srs_fold_weights: first + count exceeds 2^64 - 1"); return UZK_ERR_PARAMETER; }
+    srs_weights_host(seed, first, count, reinterpret_cast<Fp*>(out_mont));
+    return UZK_OK;
+} catch (...) { return uzk::on_exception("uzk_srs_fold_weights"); }
+
+// left = sum_{i < count - 1} rho_i P[i], right = sum rho_i P[i + 1] over the device array P[0 .. count): the weights expanded into
+// the context's workspace, two MSMs over the one scalar vector (plain bases: the array is not a handle's, a window table would not
+// cover the shifted run)
+static int srs_fold_run(Ctx& c, const Affine* d_points, size_t count, const uint8_t seed[32], Jac* left, Jac* right) {
+    const size_t m = count - 1;
+    UZK_TRY(c.srs_weights.reserve(m * sizeof(Fp)));
+    Fp* d_w = c.srs_weights.as<Fp>();
+    UZK_TRY(srs_weights_run(c, seed, 0, m, d_w));
+    if (c.prof_on) UZK_HIP(hipStreamSynchronize(c.stream));        // so that the two host sections below time the MSMs alone
+    Ctx::Srs run;
+    run.d_points = const_cast<Affine*>(d_points);
+    run.n = count;
+    run.device = c.device;
+    {
+        HostScope hs(c, "host_srs_fold_msm_left");
+        UZK_TRY(msm_dispatch(run, 0, d_w, m, 1, left));
+    }
+    {
+        HostScope hs(c, "host_srs_fold_msm_right");
+        UZK_TRY(msm_dispatch(run, 1, d_w, m, 1, right));
+    }
+    return UZK_OK;
+}
+
+int uzk_srs_fold_powers(uint64_t handle, size_t offset, size_t count, const uint8_t seed[32], uzk_g1_jac* left_out, uzk_g1_jac* right_out) try {
+    API_LOCK;
+    if (!seed || !left_out || !right_out) { set_error("uzk_srs_fold_powers: null pointer"); return UZK_ERR_PARAMETER; }
+    if (count < 2) { set_error("uzk_srs_fold_powers: a run of %zu points holds no equation (count >= 2)", count); return UZK_ERR_PARAMETER; }
+    Ctx::Srs s;
+    UZK_TRY(srs_range_checked("uzk_srs_fold_powers", handle, offset, count, &s));
+    UZK_TRY(require_ready());
+    Ctx& c = ctx();
+    UZK_TRY(srs_device_checked("uzk_srs_fold_powers", s, c));
+    Jac l, r;
+    UZK_TRY(srs_fold_run(c, s.d_points + offset, count, seed, &l, &r));
+    std::memcpy(left_out, &l, sizeof l);
+    std::memcpy(right_out, &r, sizeof r);
+    return UZK_OK;
+} catch (...) { return uzk::on_exception("uzk_srs_fold_powers"); }
+
+int uzk_srs_fold_powers_lagrange(uint64_t lagrange_handle, uint64_t n, const uint8_t seed[32], uzk_g1_affine* first_out, uzk_g1_jac* left_out,
+                                 uzk_g1_jac* right_out) try {
+    API_LOCK;
+    if (!seed || !first_out || !left_out || !right_out) { set_error("uzk_srs_fold_powers_lagrange: null pointer"); return UZK_ERR_PARAMETER; }
+    UZK_TRY(g1_ntt_size_checked(n, "uzk_srs_fold_powers_lagrange"));
+    if (n < 2) { set_error("uzk_srs_fold_powers_lagrange: a run of %llu points holds no equation (n >= 2)", (unsigned long long)n); return UZK_ERR_PARAMETER; }
+    Ctx::Srs s;
+    UZK_TRY(srs_range_checked("uzk_srs_fold_powers_lagrange", lagrange_handle, 0, (size_t)n, &s));
+    UZK_TRY(require_ready());
+    Ctx& c = ctx();
+    UZK_TRY(srs_device_checked("uzk_srs_fold_powers_lagrange", s, c));
+    UZK_TRY(c.srs_points.reserve((size_t)n * sizeof(Affine)));
+    Affine* d_m = c.srs_points.as<Affine>();
+    UZK_TRY(g1ntt_run(c, s.d_points, d_m, n, false));
+    Jac l, r;
+    UZK_TRY(srs_fold_run(c, d_m, (size_t)n, seed, &l, &r));
+    UZK_HIP(hipMemcpyAsync(first_out, d_m, sizeof(Affine), hipMemcpyDeviceToHost, c.stream));
+    UZK_HIP(hipStreamSynchronize(c.stream));
+    std::memcpy(left_out, &l, sizeof l);
+    std::memcpy(right_out, &r, sizeof r);
+    return UZK_OK;
+} catch (...) { return uzk::on_exception("uzk_srs_fold_powers_lagrange"); }
+
+int uzk_test_srs_weights_device(const uint8_t seed[32], uint64_t count, uint64_t* out_mont) try {
+    API_LOCK;
+    if (!seed || (count > 0 && !out_mont)) { set_error("uzk_test_srs_weights_device: null pointer"); return UZK_ERR_PARAMETER; }
+    if (count == 0) return UZK_OK;
+    UZK_TRY(require_ready());
+    Ctx& c = ctx();
+    UZK_TRY(c.srs_weights.reserve((size_t)count * sizeof(Fp)));
+    UZK_TRY(srs_weights_run(c, seed, 0, count, c.srs_weights.as<Fp>()));
+    UZK_HIP(hipMemcpyAsync(out_mont, c.srs_weights.p, (size_t)count * sizeof(Fp), hipMemcpyDeviceToHost, c.stream));
+    UZK_HIP(hipStreamSynchronize(c.stream));
+    return UZK_OK;
+} catch (...) { return uzk::on_exception("uzk_test_srs_weights_device"); }
 
 /* ---- batch verification -------------------------------------------------------------------- */
 int uzk_vk_create(const uzk_vk_desc* desc, uint64_t* vk_out) try {

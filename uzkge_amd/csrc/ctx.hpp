@@ -139,6 +139,9 @@ struct Ctx {
     DevBuf g1ntt_work, g1ntt_prefix, g1ntt_io;
     // verify.hip: one block carved into the arrays of a fold (proofs, decoded words, challenges, coefficients, the MSMs' inputs)
     DevBuf verify_ws;
+    // srscheck.hip: one record per workgroup of the curve kernel, the weights of a fold, the forward transform of a Lagrange
+    // handle (grow-only)
+    DevBuf srs_records, srs_weights, srs_points;
     int tune_verify_transcript = 0;   // which transcript kernel a fold runs: 1 one proof per lane; 0 / 2 a proof's state spread over a half wave (the default)
     // an entry of the process-wide SRS registry
     struct Srs {
@@ -243,6 +246,12 @@ int vf_key_set_public_key(Ctx& c, uint64_t h, const Affine* pk);
 int vf_fold_run(Ctx& c, uint64_t h, const uint8_t* proofs, const Fp* pi, uint32_t m, const Fp* weights, Jac* left_out, Jac* right_out,
                 uint8_t* status_out, Fp* challenges_out);
 int vf_keccak_test(Ctx& c, const uint8_t* msgs, const uint64_t* offsets, uint32_t count, uint8_t* out);
+// srscheck.hip: the curve report of d_points[0 .. count) (first_bad relative to d_points), the fold weights of a seed on the
+// device and on the host (the same code)
+int srs_curve_run(Ctx& c, const Affine* d_points, uint64_t count, uzk_srs_curve_report* out);
+int srs_weights_run(Ctx& c, const uint8_t seed[32], uint64_t first, uint64_t count, Fp* d_out);
+void srs_weights_host(const uint8_t seed[32], uint64_t first, uint64_t count, Fp* out);
+void srscheck_free(Ctx& c);
 void msm_plan_info(Ctx& c, size_t n, int* window_bits, int* windows);
 int msm_run(Ctx& c, const Affine* points, const ScalarView& scalars, size_t n, uint32_t batch, Jac* out_host, int pre_c,
             uint32_t pre_stride, uint32_t pre_off);

@@ -13,6 +13,7 @@ Coefficients are numpy uint64 arrays [n, 4] in the wire format (Montgomery, 4 LE
 """
 from __future__ import annotations
 
+import os
 import struct
 from typing import List, Optional, Sequence
 
@@ -256,6 +257,19 @@ class KZGCommitmentSchemeBN254:
         out._srs = srs
         out.public_parameter_group_1 = srs.download()
         return out
+
+    def check(self, seed: Optional[bytes] = None, offset: int = 0, count: Optional[int] = None):
+        """Validates the powers [offset, offset + count) on the device -- what from_unchecked_bytes skips (Validate::No,
+        kzg_poly_commitment.rs:228-256).  Returns (report, left, right): the curve report of Srs.check_curve and the two points
+        of Srs.fold_powers; the run is a power sequence of tau iff e(right, H) = e(left, [tau] H), the caller's pairing over the
+        G2 part of the parameters.  ParameterError when a point is non-canonical or off the curve.  The seed of the fold is
+        drawn here (os.urandom) unless given: it must not be known before the points are fixed."""
+        report = self._srs.check_curve(offset, count)
+        if report["first_bad"] is not None:
+            raise UzkgeError(N.UZK_ERR_PARAMETER, "SRS point %d is not a curve point (%d non-canonical, %d off the curve)"
+                             % (report["first_bad"], report["non_canonical"], report["off_curve"]))
+        left, right = self._srs.fold_powers(os.urandom(32) if seed is None else seed, offset, count)
+        return report, left, right
 
     def release(self) -> None:
         self._srs.release()
