@@ -22,6 +22,16 @@ extern "C" {
  * and back by exact division by 2^10 (identity), 33 a lazy chain 4 a - b across every offset the types generate.
  * a, b, out: n elements (host memory). */
 int uzk_test_field_kat(int field, int op, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n);
+/* The same primitives on operands the COMPILER can see: every (op, form_a, form_b) accepted here is a kernel of its own in which the
+ * forms' fixed words are literals and only the rest is loaded from a / b (n elements each; the fixed words of the inputs are ignored).
+ * op: 0 mul, 1 mul_rx (then canon), 2 sqr, 3 add, 4 sub, 5 add_rx, 6 sub_rx (then canon), 7 dbl; on 9 x 29-bit limbs re-limbed from
+ * the loaded words, result through canon and to_fp: 8 mul(a, b), 9 sqr(a), 10 mul2(a, b, a, a), 11 mulc(a, w = b, wq_of(w)) (b
+ * canonical).  form: 0 all eight words loaded, 1 words 0..3 loaded and 4..7 literal zero, 2 word 0 loaded and the rest zero, 3 the
+ * literal R^2, 4 the literal (1, 0, .., 0), 5 zero(), 6 one(), 7 modulus() - 1; of the limbs: 8 limbs 0..4 loaded and 5..8 literal
+ * zero, 9 limb 0 loaded and the rest zero, 10 LzOps::one() (form 0: all nine limbs from the loaded words).  portable: 0 the assembly
+ * entry points, 1 mul_portable / add_portable / sub_portable / the _cpp products in the same shapes.  The accepted triples are the
+ * CO_CASES list of csrc/fieldops.hip (mirrored by tests/test_gpu_asm_constant_operands.py); any other is UZK_ERR_PARAMETER. */
+int uzk_test_const_operands(int field, int op, int form_a, int form_b, int portable, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n);
 /* op: 0 a + b (mixed add), 1 a + b (full XYZZ add), 2 2a, 3 a - b, 4 2(a + b); 5..7 the four-lane addition of the
  * small-MSM folds (ecquad.hpp): 5 a + b, 6 2(a + b) (its doubling branch), 7 (a + b) + (a - b); 8..10 the same three on the
  * 29-bit-limb form (ecquad29.hpp), 11 4(a + b) by two quad doublings, 12 2(a + b) by one, 13 4a; 14..17 the one-lane additions on

@@ -28,7 +28,7 @@ def emit_stmt(terms, lines):
         body.append(f"v_mad_u64_u32 %0, vcc, %{ix}, %{iy}, %0")
         body.append("v_addc_co_u32_e32 %1, vcc, 0, %1, vcc")
     text = "\\n\\t".join(body)
-    lines.append(f'    asm("{text}"\n        : "+v"(acc), "+v"(top)\n        : {", ".join(ops_in)}\n        : "vcc");')
+    lines.append(f'    asm("{text}"\n        : "+&v"(acc), "+&v"(top)\n        : {", ".join(ops_in)}\n        : "vcc");')
 
 
 def emit_terms(terms, lines):
@@ -94,7 +94,7 @@ def gen_addsub(marr="M", suf=""):
     body = ["v_add_co_u32_e32 %0, vcc, %0, %8"]
     for i in range(1, 8):
         body.append(f"v_addc_co_u32_e32 %{i}, vcc, %{i}, %{8 + i}, vcc")
-    outs = ", ".join(f'"+v"(r.v[{i}])' for i in range(8))
+    outs = ", ".join(f'"+&v"(r.v[{i}])' for i in range(8))      # word i is written before b's words above i are read
     ins = ", ".join(f'"v"(b.v[{i}])' for i in range(8))
     L.append('    asm("' + "\\n\\t".join(body) + '"\n        : ' + outs + "\n        : " + ins + '\n        : "vcc");')
     L.append(f"    fp_reduce_once{suf}_asm<C>(r);")
@@ -110,7 +110,7 @@ def gen_addsub(marr="M", suf=""):
     for i in range(1, 8):
         body.append(f"v_subb_co_u32_e32 %{i}, vcc, %{i}, %{9 + i}, vcc")
     body.append("v_cndmask_b32_e64 %8, 0, -1, vcc")
-    outs = ", ".join([f'"+v"(r.v[{i}])' for i in range(8)] + ['"=&v"(mask)'])
+    outs = ", ".join([f'"+&v"(r.v[{i}])' for i in range(8)] + ['"=&v"(mask)'])
     ins = ", ".join(f'"v"(b.v[{i}])' for i in range(8))
     L.append('    asm("' + "\\n\\t".join(body) + '"\n        : ' + outs + "\n        : " + ins + '\n        : "vcc");')
     body = [f"v_and_b32_e32 %{8 + i}, %{17 + i}, %16" for i in range(8)]

@@ -19,7 +19,7 @@ def stmt(terms):
         iy = len(ops) + 1; ops.append(f'"{"s" if ys else "v"}"({y})')
         body.append(f"v_mad_u64_u32 %0, vcc, %{ix}, %{iy}, %0")
     text = "\\n\\t".join(body)
-    return f'    asm("{text}" : "+v"(acc) : {", ".join(ops)} : "vcc");'
+    return f'    asm("{text}" : "+&v"(acc) : {", ".join(ops)} : "vcc");'
 
 
 def emit(terms, L):

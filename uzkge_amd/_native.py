@@ -134,6 +134,7 @@ PROTOTYPES = {
 # synthetic-circuit switch).  Not part of the drop-in ABI; bound here for tests/ and tools/ only.
 TEST_PROTOTYPES = {
     "uzk_test_field_kat": (_I, [_I, _I, _P, _P, _P, _SZ]),
+    "uzk_test_const_operands": (_I, [_I, _I, _I, _I, _I, _P, _P, _P, _SZ]),
     "uzk_test_g1_kat": (_I, [_I, _P, _P, _P, _SZ]),
     "uzk_test_circuit_truncate_t": (_I, [_U64, _I]),
     "uzk_test_l29_kat": (_I, [_I, _I, ctypes.c_uint32, _P, _P, _SZ]),

@@ -479,6 +479,16 @@ def field_op(field: str, op: int, a: np.ndarray, b: np.ndarray) -> np.ndarray:
     return out
 
 
+def const_operands(field: str, op: int, form_a: int, form_b: int, a: np.ndarray, b: np.ndarray, portable: bool = False) -> np.ndarray:
+    """uzk_test_const_operands: a device primitive in the kernel whose operands have the given forms (literal words fixed at compile
+    time, the rest loaded from a / b); include/uzkge_gpu_test.h lists ops and forms."""
+    x = np.ascontiguousarray(a, dtype=np.uint64).reshape(-1, 4)
+    y = np.ascontiguousarray(b, dtype=np.uint64).reshape(-1, 4)
+    out = np.zeros_like(x)
+    check(lib.uzk_test_const_operands(0 if field == "fq" else 1, op, form_a, form_b, int(portable), _ptr(x), _ptr(y), _ptr(out), x.shape[0]))
+    return out
+
+
 def field_elementwise(field: str, op: int, a: np.ndarray, b: np.ndarray) -> np.ndarray:
     """uzk_field_op_device, the PRODUCT entry point: mul 0, add 1, sub 2, sqr 4, neg 5, from_mont 6, to_mont 7 on host arrays."""
     x = np.ascontiguousarray(a, dtype=np.uint64).reshape(-1, 4)

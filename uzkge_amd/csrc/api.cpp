@@ -1404,6 +1404,16 @@ int uzk_test_field_kat(int field, int op, const uint64_t* a, const uint64_t* b, 
     UZK_TRY(require_ready());
     return field_op_device(ctx(), field, op, as_fp(a), as_fp(b), reinterpret_cast<Fp*>(out), n);
 } catch (...) { return uzk::on_exception("uzk_test_field_kat"); }
+int uzk_test_const_operands(int field, int op, int form_a, int form_b, int portable, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n) try {
+    API_LOCK;
+    if (n > 0 && (!a || !b || !out)) { set_error("uzk_test_const_operands: null pointer"); return UZK_ERR_PARAMETER; }
+    if (field < 0 || field > 1 || portable < 0 || portable > 1 || !const_operand_case_known(op, form_a, form_b)) {
+        set_error("uzk_test_const_operands: bad field, or no kernel of this (op, form, form)");
+        return UZK_ERR_PARAMETER;
+    }
+    UZK_TRY(require_ready());
+    return const_operand_device(ctx(), field, op, form_a, form_b, portable != 0, as_fp(a), as_fp(b), reinterpret_cast<Fp*>(out), n);
+} catch (...) { return uzk::on_exception("uzk_test_const_operands"); }
 int uzk_test_g1_kat(int op, const uzk_g1_affine* a, const uzk_g1_affine* b, uzk_g1_jac* out, size_t n) try {
     API_LOCK;
     if (n > 0 && (!a || !b || !out)) { set_error("uzk_test_g1_kat: null pointer"); return UZK_ERR_PARAMETER; }

@@ -320,6 +320,8 @@ int g1_op_device(Ctx& c, int op, const Affine* a, const Affine* b, Jac* out, siz
 // raw 9-limb known answers (fieldops.hip; include/uzkge_gpu_test.h uzk_test_l29_kat / uzk_test_p29_kat)
 bool l29_sig_runnable(int field, uint32_t idx);
 int l29_op_device(Ctx& c, int field, int op, uint32_t param, const uint32_t* in, uint32_t* out, size_t n);
+bool const_operand_case_known(int op, int form_a, int form_b);
+int const_operand_device(Ctx& c, int field, int op, int form_a, int form_b, bool portable, const Fp* a, const Fp* b, Fp* out, size_t n);
 int p29_op_device(Ctx& c, int op, const uint32_t* in, uint32_t* out, size_t n);
 // which lane kernel runs (rounds.hip): the launchers and the test hook uzk_test_lanes share the choice
 struct LaneKernel { bool a29, wide; };

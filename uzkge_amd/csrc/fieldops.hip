@@ -210,6 +210,138 @@ int field_op_device(Ctx& c, int field, int op, const Fp* a, const Fp* b, Fp* out
     return UZK_OK;
 }
 
+// ---- operands the compiler can see (uzk_test_const_operands) ----------------------------------------------------------------------
+// The known-answer kernel above loads every operand from memory.  Production code also multiplies by literals (to_mont, from_mont, a
+// zero Horner start, a 16-bit scalar): words the compiler KNOWS, which it may keep in one register with any other word of the same
+// value -- the zero-initialised carry word of an assembly statement among them, unless the statement's constraints forbid it.  Each
+// case here is one (operation, form of the first operand, form of the second) as template parameters and so a kernel of its own:
+// its register allocation is that of the shape alone.  A form fixes some words as literals and loads the rest.
+enum { CO_MUL, CO_MUL_RX, CO_SQR, CO_ADD, CO_SUB, CO_ADD_RX, CO_SUB_RX, CO_DBL, CO_L29_MUL, CO_L29_SQR, CO_L29_MUL2, CO_L29_MULC };
+// 8 x 32-bit words: all loaded | words 0..3 loaded, 4..7 zero | word 0 loaded, 1..7 zero | R^2 | (1, 0, .., 0) | 0 | one() | M - 1;
+// 9 x 29-bit limbs (of the loaded words): limbs 0..4 loaded, 5..8 zero | limb 0 loaded, 1..8 zero | LzOps::one()
+enum { CF_RT, CF_LO4, CF_W0, CF_R2, CF_E1, CF_ZERO, CF_ONE, CF_MM1, CF_L5, CF_L1, CF_ONE261 };
+
+#define CO_PRODUCT_CASES(X, OP) \
+    X(OP, CF_LO4, CF_R2) X(OP, CF_R2, CF_LO4) X(OP, CF_W0, CF_RT) X(OP, CF_RT, CF_W0) X(OP, CF_RT, CF_E1) X(OP, CF_RT, CF_ZERO) \
+    X(OP, CF_RT, CF_ONE) X(OP, CF_R2, CF_ONE) X(OP, CF_MM1, CF_MM1) X(OP, CF_LO4, CF_LO4)
+#define CO_SUM_CASES(X, OP) \
+    X(OP, CF_RT, CF_ZERO) X(OP, CF_RT, CF_ONE) X(OP, CF_RT, CF_MM1) X(OP, CF_ZERO, CF_RT) X(OP, CF_ONE, CF_RT) X(OP, CF_MM1, CF_RT)
+#define CO_CASES(X) \
+    CO_PRODUCT_CASES(X, CO_MUL) CO_PRODUCT_CASES(X, CO_MUL_RX) \
+    X(CO_SQR, CF_LO4, CF_LO4) X(CO_SQR, CF_W0, CF_W0) X(CO_SQR, CF_R2, CF_R2) X(CO_SQR, CF_MM1, CF_MM1) \
+    CO_SUM_CASES(X, CO_ADD) CO_SUM_CASES(X, CO_SUB) CO_SUM_CASES(X, CO_ADD_RX) CO_SUM_CASES(X, CO_SUB_RX) \
+    X(CO_DBL, CF_ZERO, CF_ZERO) X(CO_DBL, CF_ONE, CF_ONE) X(CO_DBL, CF_MM1, CF_MM1) X(CO_DBL, CF_LO4, CF_LO4) X(CO_DBL, CF_W0, CF_W0) \
+    X(CO_L29_MUL, CF_L5, CF_RT) X(CO_L29_MUL, CF_RT, CF_L5) X(CO_L29_MUL, CF_L1, CF_RT) X(CO_L29_MUL, CF_RT, CF_L1) \
+    X(CO_L29_MUL, CF_L5, CF_L5) X(CO_L29_MUL, CF_RT, CF_ONE261) X(CO_L29_MUL, CF_ONE261, CF_RT) X(CO_L29_MUL, CF_L1, CF_ONE261) \
+    X(CO_L29_SQR, CF_L5, CF_L5) X(CO_L29_SQR, CF_L1, CF_L1) X(CO_L29_SQR, CF_ONE261, CF_ONE261) \
+    X(CO_L29_MUL2, CF_L5, CF_RT) X(CO_L29_MUL2, CF_RT, CF_L5) X(CO_L29_MUL2, CF_L1, CF_RT) X(CO_L29_MUL2, CF_RT, CF_L1) \
+    X(CO_L29_MUL2, CF_RT, CF_ONE261) \
+    X(CO_L29_MULC, CF_L5, CF_RT) X(CO_L29_MULC, CF_L1, CF_RT) X(CO_L29_MULC, CF_RT, CF_L5) X(CO_L29_MULC, CF_RT, CF_L1) \
+    X(CO_L29_MULC, CF_RT, CF_ONE261)
+
+#if defined(__HIP_DEVICE_COMPILE__)
+template <class F> struct CoCfgOf;
+template <class C> struct CoCfgOf<Field<C>> { using type = C; };
+template <class F, int FORM>
+__device__ __forceinline__ Fp co_words(const Fp& x) {
+    using C = typename CoCfgOf<F>::type;
+    Fp r;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        if constexpr (FORM == CF_RT) r.v[k] = x.v[k];
+        else if constexpr (FORM == CF_LO4) r.v[k] = k < 4 ? x.v[k] : 0u;
+        else if constexpr (FORM == CF_W0) r.v[k] = k < 1 ? x.v[k] : 0u;
+        else if constexpr (FORM == CF_R2) r.v[k] = C::R2[k];
+        else if constexpr (FORM == CF_E1) r.v[k] = k == 0 ? 1u : 0u;
+        else if constexpr (FORM == CF_ZERO) r.v[k] = 0u;
+        else if constexpr (FORM == CF_ONE) r.v[k] = C::R1[k];
+        else r.v[k] = C::M[k] - (k == 0 ? 1u : 0u);                  // M is odd: no borrow
+    }
+    return r;
+}
+template <class F29, int FORM>
+__device__ __forceinline__ L29 co_limbs(const Fp& x) {
+    if constexpr (FORM == CF_ONE261) return F29::constant(F29::Cfg::ONE261);
+    L29 r = F29::from_fp(x);
+#pragma unroll
+    for (int k = 0; k < 9; ++k)
+        if ((FORM == CF_L5 && k >= 5) || (FORM == CF_L1 && k >= 1)) r.l[k] = 0u;
+    return r;
+}
+#endif
+
+template <class F, class F29, int OP, int FA, int FB, bool PORTABLE>
+__global__ __launch_bounds__(256) void const_operand_kernel(const Fp* __restrict__ a, const Fp* __restrict__ b, Fp* __restrict__ out, size_t n) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    // a grid-stride loop although the launch gives every lane one element: the literals are then set up outside the loop, as in the
+    // production kernels that loop after their product, and that is where the compiler was seen to merge them with the carry word
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    Fp r;
+    if constexpr (OP >= CO_L29_MUL) {
+        const L29 x = co_limbs<F29, FA>(a[i]), y = co_limbs<F29, FB>(b[i]);
+        L29 t;
+        if constexpr (OP == CO_L29_MUL) t = PORTABLE ? F29::mul_cpp(x, y) : F29::mul(x, y);
+        else if constexpr (OP == CO_L29_SQR) t = PORTABLE ? F29::sqr_cpp(x) : F29::sqr(x);
+        else if constexpr (OP == CO_L29_MUL2) t = PORTABLE ? F29::mul2_cpp(x, y, x, x) : F29::mul2(x, y, x, x);                // x y + x x
+        // the constant-operand product has no C++ form: x y as (x y 2^-261) 2^522 2^-261 by two C++ products
+        else t = PORTABLE ? F29::mul_cpp(F29::mul_cpp(x, y), F29::constant(F29::Cfg::R522)) : F29::mulc(x, y, F29::wq_of(y));
+        r = F29::to_fp(F29::canon(t));
+    } else {
+        const Fp x = co_words<F, FA>(a[i]), y = co_words<F, FB>(b[i]);
+        if constexpr (OP == CO_MUL) r = PORTABLE ? F::mul_portable(x, y) : F::mul(x, y);
+        else if constexpr (OP == CO_MUL_RX) r = PORTABLE ? F::mul_portable(x, y) : F::canon(F::mul_rx(x, y));
+        else if constexpr (OP == CO_SQR) r = PORTABLE ? F::mul_portable(x, x) : F::sqr(x);
+        else if constexpr (OP == CO_ADD) r = PORTABLE ? F::add_portable(x, y) : F::add(x, y);
+        else if constexpr (OP == CO_SUB) r = PORTABLE ? F::sub_portable(x, y) : F::sub(x, y);
+        else if constexpr (OP == CO_ADD_RX) r = PORTABLE ? F::add_portable(x, y) : F::canon(F::add_rx(x, y));
+        else if constexpr (OP == CO_SUB_RX) r = PORTABLE ? F::sub_portable(x, y) : F::canon(F::sub_rx(x, y));
+        else r = PORTABLE ? F::add_portable(x, x) : F::dbl(x);
+    }
+    out[i] = r;
+    }
+#endif
+}
+
+template <int OP, int FA, int FB>
+static void const_operand_launch(Ctx& c, int field, bool portable, const Fp* da, const Fp* db, Fp* dout, size_t n) {
+    const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+    if (field == 0 && !portable) hipLaunchKernelGGL((const_operand_kernel<Fq, Fq29, OP, FA, FB, false>), grid, block, 0, c.stream, da, db, dout, n);
+    else if (field == 0) hipLaunchKernelGGL((const_operand_kernel<Fq, Fq29, OP, FA, FB, true>), grid, block, 0, c.stream, da, db, dout, n);
+    else if (!portable) hipLaunchKernelGGL((const_operand_kernel<Fr, Fr29, OP, FA, FB, false>), grid, block, 0, c.stream, da, db, dout, n);
+    else hipLaunchKernelGGL((const_operand_kernel<Fr, Fr29, OP, FA, FB, true>), grid, block, 0, c.stream, da, db, dout, n);
+}
+
+bool const_operand_case_known(int op, int form_a, int form_b) {
+#define CO_KNOWN(o, fa, fb) if (op == o && form_a == fa && form_b == fb) return true;
+    CO_CASES(CO_KNOWN)
+#undef CO_KNOWN
+    return false;
+}
+
+int const_operand_device(Ctx& c, int field, int op, int form_a, int form_b, bool portable, const Fp* a, const Fp* b, Fp* out, size_t n) {
+    if (n == 0) return UZK_OK;
+    Fp *da = nullptr, *db = nullptr, *dout = nullptr;
+    const size_t bytes = n * sizeof(Fp);
+    UZK_HIP(hipMalloc(reinterpret_cast<void**>(&da), bytes));
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&db), bytes);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&dout), bytes);
+    if (e == hipSuccess) e = hipMemcpyAsync(da, a, bytes, hipMemcpyHostToDevice, c.stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(db, b, bytes, hipMemcpyHostToDevice, c.stream);
+    if (e == hipSuccess) {
+#define CO_RUN(o, fa, fb) if (op == o && form_a == fa && form_b == fb) const_operand_launch<o, fa, fb>(c, field, portable, da, db, dout, n);
+        CO_CASES(CO_RUN)
+#undef CO_RUN
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(out, dout, bytes, hipMemcpyDeviceToHost, c.stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c.stream);
+    if (da) (void)hipFree(da);
+    if (db) (void)hipFree(db);
+    if (dout) (void)hipFree(dout);
+    UZK_HIP(e);
+    return UZK_OK;
+}
+
 // ops 14..21: the additions of ec29l.hpp (lazy 29-bit limbs, operands re-limbed from the wire form, bounds in the types).
 // one lane per element: 14 a + b, 15 2(a + b) through the addition's doubling branch, 16 (a + b) + (a - b) (non-trivial ZZ on both
 // sides), 17 (a + b) - (a + b) = infinity (cancellation) ... then + a; four lanes per element: 18..21 the same four by quads.

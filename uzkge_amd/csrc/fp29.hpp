@@ -331,7 +331,7 @@ struct Field29 {
         L29 r;
 #pragma unroll
         for (int i = 0; i < 9; ++i) {
-            asm("v_mad_u64_u32 %0, vcc, %1, 1, %0\n\tv_mad_u64_u32 %0, vcc, %2, %3, %0" : "+v"(acc) : "v"(a.l[i]), "v"(q), "s"(C::MC[i]) : "vcc");
+            asm("v_mad_u64_u32 %0, vcc, %1, 1, %0\n\tv_mad_u64_u32 %0, vcc, %2, %3, %0" : "+&v"(acc) : "v"(a.l[i]), "v"(q), "s"(C::MC[i]) : "vcc");
             r.l[i] = (uint32_t)acc & MASK;
             acc >>= 29;
         }

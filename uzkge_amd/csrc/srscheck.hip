@@ -82,16 +82,6 @@ __global__ __launch_bounds__(kSrsBlock) void srs_curve_kernel(const Affine* __re
 struct SrsSeed { uint64_t w[4]; };                     // the 32 seed bytes as four little-endian lanes
 constexpr uint64_t kSrsDomain = 0x31767372736b7a75ull; // "uzksrsv1" read as a little-endian lane
 
-// A digest half (< 2^128) into Montgomery form, by the portable product.  The assembly product takes its operands as registers
-// without early-clobber marks; words the compiler knows to be zero may then share the register of the product's zero-initialised
-// carry word, which the first carry overwrites.  Operands loaded from memory never meet this, constants like these upper words do.
-UZK_HD Fp srs_to_mont(const Fp& a) {
-    Fp r2;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) r2.v[i] = FrCfg::R2[i];
-    return Fr::mul_portable(a, r2);
-}
-
 // Block j: the 48-byte message seed || "uzksrsv1" || le64(j) is six lanes of one rate block; byte 48 is the padding byte 0x01, the
 // block's last byte carries the closing bit.  Digest bytes 0..15 and 16..31 are the two weights (little endian, < 2^128).
 UZK_HD void srs_weight_pair(const SrsSeed& seed, uint64_t j, Fp& even, Fp& odd) {
@@ -107,8 +97,8 @@ UZK_HD void srs_weight_pair(const SrsSeed& seed, uint64_t j, Fp& even, Fp& odd) 
     Fp a = Fr::zero(), b = Fr::zero();
     a.v[0] = (uint32_t)s[0]; a.v[1] = (uint32_t)(s[0] >> 32); a.v[2] = (uint32_t)s[1]; a.v[3] = (uint32_t)(s[1] >> 32);
     b.v[0] = (uint32_t)s[2]; b.v[1] = (uint32_t)(s[2] >> 32); b.v[2] = (uint32_t)s[3]; b.v[3] = (uint32_t)(s[3] >> 32);
-    even = srs_to_mont(a);
-    odd = srs_to_mont(b);
+    even = Fr::to_mont(a);
+    odd = Fr::to_mont(b);
 }
 
 // out[k] = rho_(first + k), k < count: lane b of the grid takes block first / 2 + b
