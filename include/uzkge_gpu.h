@@ -296,12 +296,15 @@ int uzk_poly_eval_batch_device(const void* d_coefs, uint64_t n, uint32_t batch, 
 /* The permutation grand product z_poly (uzkge/src/plonk/helpers.rs:160-220), evaluations only:
  * z[0] = 1, z[i+1] = z[i] * prod_j (w[j*n+i] + beta*k[j]*group[i] + gamma)
  *                         / (w[j*n+i] + beta*k[perm/n]*group[perm%n] + gamma),  perm = perm[j*n+i].
- * w: n_wires*n elements, perm: n_wires*n indices < n_wires*n, group: n elements (omega^i), k: n_wires. */
+ * w: n_wires*n elements, perm: n_wires*n indices < n_wires*n, group: n elements (omega^i), k: n_wires.
+ * A perm value >= n_wires*n is refused (UZK_ERR_PARAMETER, the message names its index) before anything is launched; a zero
+ * denominator product is refused too ("a permutation denominator is zero"): the reference's batch_inversion has no value for it. */
 int uzk_z_poly(const uint64_t* w, const uint32_t* perm, const uint64_t* group, const uint64_t* k,
                const uint64_t* beta_mont, const uint64_t* gamma_mont, uint32_t n, uint32_t n_wires, uint64_t* z_out);
 
 /* The same on device-resident inputs (w, group: device Fr vectors; perm: device u32; k and the challenges on the
- * host), z written to d_z (n elements, device). */
+ * host), z written to d_z (n elements, device).  This entry point TRUSTS its caller: d_perm is not read back, and a value
+ * >= n_wires*n makes the kernel index past k and group. */
 int uzk_z_poly_device(const void* d_w, const uint32_t* d_perm, const void* d_group, const uint64_t* k,
                       const uint64_t* beta_mont, const uint64_t* gamma_mont, uint32_t n, uint32_t n_wires, void* d_z);
 
@@ -441,7 +444,7 @@ enum {
     UZK_CS_QECC = 45            /* q_ecc_poly */
 };
 typedef struct {
-    uint32_t n;                 /* cs.size(): a power of two, 16 <= n <= 2^20 */
+    uint32_t n;                 /* cs.size(): a power of two, 16 <= n <= 2^UZK_PROVER_MAX_LOG2 */
     uint32_t shuffle;           /* != 0: built with the "shuffle" feature -- all 46 slots; 0: slots 0..20 only (zmatchmaking) */
     uint32_t precompute;        /* window tables over the commit bases (uzk_srs_precompute): 0 none; 1 automatic -- two tables, 8-bit
                                    windows for provers of one proof (shortest chain of dependent additions) and 15-bit windows for
@@ -510,6 +513,10 @@ int uzk_circuit_info(uint64_t circuit, uint32_t* n_out, uint32_t* evals_per_proo
  * n = 2^14 with the defaults.  Sharing only pays where one proof leaves the chip idle, so provers of n > UZK_SHARED_MAX_N
  * (2^16) are never shared: they own their single lane as before -- the pool cannot grow past 8 x 4 x 315 MB = 10 GB. */
 #define UZK_SHARED_MAX_N (1u << 16)
+/* The largest circuit uzk_circuit_create and uzk_prover_create[_private] accept: n = 2^k, 4 <= k <= UZK_PROVER_MAX_LOG2.  The bound
+ * is the largest size at which the suite makes a whole proof and holds it to the oracle (tests/test_gpu_rounds_large.py); a
+ * larger n is refused at creation, never in a later round. */
+#define UZK_PROVER_MAX_LOG2 20
 int uzk_prover_create(uint32_t n, uint32_t batch, uint64_t* prover_out);
 /* The same, but the prover owns its lanes whatever `batch` and the sharing configuration are: its proofs run on the calling
  * context's stream, alone, and uzk_prover_buffer can show its buffers (tests, diagnostics, latency measurements). */

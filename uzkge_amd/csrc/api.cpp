@@ -1348,6 +1348,9 @@ int uzk_z_poly(const uint64_t* w, const uint32_t* perm, const uint64_t* group, c
     API_LOCK;
     if (!w || !perm || !group || !k || !beta_mont || !gamma_mont || !z_out) { set_error("uzk_z_poly: null pointer"); return UZK_ERR_PARAMETER; }
     if (n_wires == 0 || n_wires > 8 || (uint64_t)n * n_wires >= (1ull << 32)) { set_error("uzk_z_poly: bad shape"); return UZK_ERR_PARAMETER; }
+    // the kernel indexes k[perm / n] (eight entries) and group[perm % n] unchecked: refuse a foreign index before any launch
+    for (uint64_t i = 0, total = (uint64_t)n * n_wires; i < total; ++i)
+        if (perm[i] >= total) { set_error("uzk_z_poly: perm[%llu] = %u is not below n_wires * n = %llu", (unsigned long long)i, perm[i], (unsigned long long)total); return UZK_ERR_PARAMETER; }
     UZK_TRY(require_ready());
     return z_poly_run(ctx(), as_fp(w), perm, as_fp(group), as_fp(k), *as_fp(beta_mont), *as_fp(gamma_mont), n, n_wires,
                       reinterpret_cast<Fp*>(z_out));

@@ -330,8 +330,8 @@ int uzk_coalesce_stats(uint64_t out[16]) try {
 
 int uzk_prover_create(uint32_t n, uint32_t batch, uint64_t* prover_out) try {
     if (!prover_out) { set_error("uzk_prover_create: null pointer"); return UZK_ERR_PARAMETER; }
-    if (n < 16 || n > (1u << 20) || (n & (n - 1)) || batch == 0 || batch > kMaxBatch) {
-        set_error("uzk_prover_create: n must be a power of two in 16 .. 2^20 and 1 <= batch <= %u", kMaxBatch);
+    if (n < 16 || n > (1u << UZK_PROVER_MAX_LOG2) || (n & (n - 1)) || batch == 0 || batch > kMaxBatch) {
+        set_error("uzk_prover_create: n must be a power of two in 16 .. 2^%d and 1 <= batch <= %u", UZK_PROVER_MAX_LOG2, kMaxBatch);
         return UZK_ERR_PARAMETER;
     }
     State& s = st();
@@ -365,8 +365,8 @@ int uzk_prover_create(uint32_t n, uint32_t batch, uint64_t* prover_out) try {
 
 int uzk_prover_create_private(uint32_t n, uint32_t batch, uint64_t* prover_out) try {
     if (!prover_out) { set_error("uzk_prover_create_private: null pointer"); return UZK_ERR_PARAMETER; }
-    if (n < 16 || n > (1u << 20) || (n & (n - 1)) || batch == 0 || batch > kMaxBatch) {
-        set_error("uzk_prover_create_private: n must be a power of two in 16 .. 2^20 and 1 <= batch <= %u", kMaxBatch);
+    if (n < 16 || n > (1u << UZK_PROVER_MAX_LOG2) || (n & (n - 1)) || batch == 0 || batch > kMaxBatch) {
+        set_error("uzk_prover_create_private: n must be a power of two in 16 .. 2^%d and 1 <= batch <= %u", UZK_PROVER_MAX_LOG2, kMaxBatch);
         return UZK_ERR_PARAMETER;
     }
     return explicit_prover_create(n, batch, prover_out);

@@ -287,7 +287,9 @@ int poly_scatter_run(Ctx& c, Fp* d_dst, uint64_t dst_stride, const uint32_t* idx
 struct QuotientDev;
 int t_quotient_run(Ctx& c, const void* args_c_abi, Fp* d_out);
 int z_poly_device(Ctx& c, const Fp* d_w, const uint32_t* d_perm, const Fp* d_group, const Fp* k_host, const Fp& beta,
-                  const Fp& gamma, uint32_t n, uint32_t n_wires, Fp* d_z);
+                  const Fp& gamma, uint32_t n, uint32_t n_wires, Fp* d_z, bool* zero_den = nullptr);
+constexpr uint32_t kZPolyLanesMax = 1u << 16;       // the longest lane of z_poly_lanes
+constexpr uint64_t kEvalLanesMax = 1ull << 18;      // the longest polynomial of poly_eval_lanes (its lazy-limb contract)
 int z_poly_lanes(Ctx& c, ArgArena& args, const Fp* d_w, uint64_t w_lane_stride, const uint32_t* d_perm, const Fp* d_group, const Fp* k_host,
                  const Fp* d_bg, uint32_t n, uint32_t n_wires, uint32_t lanes, Fp* d_z, uint64_t z_lane_stride, uint8_t* lane_ok);
 int t_quotient_lanes(Ctx& c, const void* args_c_abi, uint64_t own_stride, const void* d_lanes, uint32_t lanes, Fp* d_out, uint64_t out_stride);

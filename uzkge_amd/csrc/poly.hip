@@ -21,6 +21,7 @@ namespace uzk {
 
 constexpr int kScanPer = 8;                    // elements per lane
 constexpr int kScanBlock = 256 * kScanPer;     // elements per workgroup
+static_assert(kZPolyLanesMax == 32u * kScanBlock, "z_poly_lanes scans one lane in one launch of at most 32 blocks");
 
 // Inclusive product scan of one block of `in` (reverse: from the right end), block totals out.
 __global__ __launch_bounds__(256) void fr_scan_block_kernel(const Fp* __restrict__ in, Fp* __restrict__ out,
@@ -411,9 +412,12 @@ __global__ __launch_bounds__(256) void z_poly_combine_kernel(const Fp* __restric
     z[i] = v;
 }
 
-// Device-resident core: d_w [n_wires][n], d_perm [n_wires][n], d_group [n]  ->  d_z [n].
+// Device-resident core: d_w [n_wires][n], d_perm [n_wires][n], d_group [n]  ->  d_z [n].  zero_den (optional): a zero
+// denominator product is reported there (d_z is left unwritten, the call succeeds) instead of being refused -- the prover's
+// round 2 fails that proof alone.
 int z_poly_device(Ctx& c, const Fp* d_w, const uint32_t* d_perm, const Fp* d_group, const Fp* k_host, const Fp& beta,
-                  const Fp& gamma, uint32_t n, uint32_t n_wires, Fp* d_z) {
+                  const Fp& gamma, uint32_t n, uint32_t n_wires, Fp* d_z, bool* zero_den) {
+    if (zero_den) *zero_den = false;
     if (n == 0) return UZK_OK;
     if (n_wires == 0 || n_wires > 8) { set_error("z_poly: n_wires must be 1..8"); return UZK_ERR_PARAMETER; }
     if (n == 1) {
@@ -450,6 +454,7 @@ int z_poly_device(Ctx& c, const Fp* d_w, const uint32_t* d_perm, const Fp* d_gro
     Fp total;
     UZK_HIP(hipMemcpyAsync(&total, d_S, sizeof(Fp), hipMemcpyDeviceToHost, c.stream));
     UZK_HIP(hipStreamSynchronize(c.stream));
+    if (Fr::is_zero(total) && zero_den) { *zero_den = true; return UZK_OK; }
     if (Fr::is_zero(total)) {
         // a zero denominator: the reference's batch_inversion leaves zeros in place; mirror it by
         // refusing rather than inventing a value (cannot happen for random beta, gamma)
@@ -468,10 +473,11 @@ int z_poly_device(Ctx& c, const Fp* d_w, const uint32_t* d_perm, const Fp* d_gro
 // The grand products of the `lanes` proofs of a lockstep batch (prover round 2): lane b's wires at d_w + b * w_lane_stride, its
 // beta / gamma at d_bg[2 b], d_bg[2 b + 1] (device memory), z to d_z + b * z_lane_stride.  Three launches, ONE synchronisation
 // and one host inversion (Montgomery's trick over the lanes' totals) for the whole batch; the inverses return to the device
-// through `args`.  lane_ok[b] = 0 marks a lane whose denominator product is zero (its z is not written).  n <= 2^16.
+// through `args`.  lane_ok[b] = 0 marks a lane whose denominator product is zero (its z is not written).  n <= 2^16
+// (kZPolyLanesMax: the one-launch scan; longer lanes go through z_poly_device one by one).
 int z_poly_lanes(Ctx& c, ArgArena& args, const Fp* d_w, uint64_t w_lane_stride, const uint32_t* d_perm, const Fp* d_group, const Fp* k_host,
                  const Fp* d_bg, uint32_t n, uint32_t n_wires, uint32_t lanes, Fp* d_z, uint64_t z_lane_stride, uint8_t* lane_ok) {
-    if (n < 2 || (uint64_t)n > 32ull * kScanBlock || n_wires == 0 || n_wires > 8 || lanes == 0) { set_error("z_poly_lanes: bad shape"); return UZK_ERR_PARAMETER; }
+    if (n < 2 || n > kZPolyLanesMax || n_wires == 0 || n_wires > 8 || lanes == 0) { set_error("z_poly_lanes: bad shape"); return UZK_ERR_PARAMETER; }
     UZK_TRY(c.zpoly_tmp.reserve(4 * (size_t)n * lanes * sizeof(Fp)));
     UZK_TRY(poly_host_reserve(c, (size_t)lanes * sizeof(Fp)));
     Fp* work = c.zpoly_tmp.as<Fp>();

@@ -463,7 +463,17 @@ int round2_lanes(Ctx& c, Prover& p, const Lane2* L, LaneStatus* st) {
     }
     ROUND_TRY(p.args.upload(c.stream));
     std::vector<uint8_t> ok(k, 1);
-    ROUND_TRY(z_poly_lanes(c, p.args, p.d_evals, (uint64_t)kProofSlots * n, cir.d_perm, cir.d_group, cir.k, d_bg, n, kWires, k, p.evals(0, z), (uint64_t)kProofSlots * n, ok.data()));
+    if (n <= kZPolyLanesMax) {
+        ROUND_TRY(z_poly_lanes(c, p.args, p.d_evals, (uint64_t)kProofSlots * n, cir.d_perm, cir.d_group, cir.k, d_bg, n, kWires, k, p.evals(0, z), (uint64_t)kProofSlots * n, ok.data()));
+    } else {
+        // past the one-launch scan of the lanes: every lane through the two-level scans of uzk_z_poly_device, one after the other
+        // (at these sizes one lane fills the chip)
+        for (uint32_t b = 0; b < k; ++b) {
+            bool zero_den = false;
+            ROUND_TRY(z_poly_device(c, p.evals(b, 0), cir.d_perm, cir.d_group, cir.k, p.beta[b], p.gamma[b], n, kWires, p.evals(b, z), &zero_den));
+            ok[b] = zero_den ? 0 : 1;
+        }
+    }
     for (uint32_t b = 0; b < k; ++b)
         if (!ok[b] && !p.dead[b]) LANE_FAIL(b, UZK_ERR_PARAMETER, "uzk_prove_round2: proof %u: a permutation denominator is zero", b);
     ROUND_TRY(ntt_run(c, p.evals(0, z), p.coefs(0, z), n, true, nullptr, k, (uint64_t)kProofSlots * n, (uint64_t)kProofSlots * m));
@@ -591,8 +601,14 @@ int round4_lanes(Ctx& c, Prover& p, const Lane4* L, LaneStatus* st) {
     uint32_t cnt = 0;
     uint64_t max_len = 1;
     const uint64_t own_stride = (uint64_t)kProofSlots * m;
-    auto own = [&](uint32_t slot, uint64_t l, uint32_t point) { eval_poly_fill(ep + (size_t)cnt++ * eb, p.coefs(0, slot), own_stride, l, point); max_len = std::max(max_len, l); };
-    auto cirp = [&](uint32_t slot) { eval_poly_fill(ep + (size_t)cnt++ * eb, tab.s[slot].poly, 0, tab.s[slot].len, 0); max_len = std::max(max_len, tab.s[slot].len); };
+    // the same list for the pointer-list path below: lane 0's address, the distance between lanes, length, point
+    std::vector<const Fp*> lp; std::vector<uint64_t> lstride, llen; std::vector<uint32_t> lpt;
+    auto note = [&](const Fp* q, uint64_t stride, uint64_t l, uint32_t point) {
+        eval_poly_fill(ep + (size_t)cnt++ * eb, q, stride, l, point); max_len = std::max(max_len, l);
+        lp.push_back(q); lstride.push_back(stride); llen.push_back(l); lpt.push_back(point);
+    };
+    auto own = [&](uint32_t slot, uint64_t l, uint32_t point) { note(p.coefs(0, slot), own_stride, l, point); };
+    auto cirp = [&](uint32_t slot) { note(tab.s[slot].poly, 0, tab.s[slot].len, 0); };
     for (uint32_t i = 0; i < kWires; ++i) own(i, n + p.hiding[i], 0);
     for (uint32_t i = 0; i < kWires - 1; ++i) cirp(UZK_CS_S + i);
     cirp(UZK_CS_QPRK + 2);
@@ -604,7 +620,17 @@ int round4_lanes(Ctx& c, Prover& p, const Lane4* L, LaneStatus* st) {
         for (uint32_t i = 0; i < kWsel; ++i) own(kWires + i, n + p.hiding[kWires + i], 0);
     }
     ROUND_TRY(p.args.upload(c.stream));
-    ROUND_TRY(poly_eval_lanes(c, d_ep, per, max_len, d_pts, k, p.d_counters, p.h_evals));
+    if (max_len <= kEvalLanesMax) {
+        ROUND_TRY(poly_eval_lanes(c, d_ep, per, max_len, d_pts, k, p.d_counters, p.h_evals));
+    } else {
+        // n + 3 coefficients are more than the lane kernel's lazy-limb sums were proven for: lane by lane through the
+        // pointer-list evaluation of uzk_poly_eval_ptrs_device (the table-driven kernel for the long polynomials)
+        std::vector<const void*> ptrs(cnt);
+        for (uint32_t b = 0; b < k; ++b) {
+            for (uint32_t j = 0; j < cnt; ++j) ptrs[j] = lp[j] + (uint64_t)b * lstride[j];
+            ROUND_TRY(poly_eval_ptrs(c, ptrs.data(), llen.data(), lpt.data(), cnt, pts + 2 * b, 2, p.h_evals + (size_t)b * per));
+        }
+    }
     ROUND_HIP(hipStreamSynchronize(c.stream));
     for (uint32_t b = 0; b < k; ++b) if (!p.dead[b]) std::memcpy(L[b].evals_out, p.h_evals + (size_t)b * per, per * sizeof(Fp));
     p.round = 4;
@@ -784,7 +810,7 @@ extern "C" {
 int uzk_circuit_create(const uzk_circuit_desc* desc, uint64_t* circuit_out) try {
     if (!desc || !circuit_out) { set_error("uzk_circuit_create: null pointer"); return UZK_ERR_PARAMETER; }
     const uint32_t n = desc->n;
-    if (n < 16 || n > (1u << 20) || (n & (n - 1))) { set_error("uzk_circuit_create: n must be a power of two in 16 .. 2^20 (n = %u)", n); return UZK_ERR_PARAMETER; }
+    if (n < 16 || n > (1u << UZK_PROVER_MAX_LOG2) || (n & (n - 1))) { set_error("uzk_circuit_create: n must be a power of two in 16 .. 2^%d (n = %u)", UZK_PROVER_MAX_LOG2, n); return UZK_ERR_PARAMETER; }
     if (!desc->lagrange_bases || !desc->blind_bases || !desc->permutation) { set_error("uzk_circuit_create: null pointer"); return UZK_ERR_PARAMETER; }
     if (desc->precompute && desc->precompute != 1 && (desc->precompute < 4 || desc->precompute > 24)) { set_error("uzk_circuit_create: precompute must be 0, 1 (automatic) or a window width 4 .. 24"); return UZK_ERR_PARAMETER; }
     const Fp omega = fr_root_of_unity(n);

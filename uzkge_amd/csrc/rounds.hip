@@ -237,7 +237,7 @@ LaneKernel poly_eval_lanes_kernel_of(const Ctx& c, uint32_t lanes, uint64_t max_
 // d_polys: `count` EvalPoly in device memory; d_counters: lanes * count zeroed words; out_host: pinned.  Asynchronous.
 int poly_eval_lanes(Ctx& c, const void* d_polys, uint32_t count, uint64_t max_len, const Fp* d_points, uint32_t lanes, uint32_t* d_counters, Fp* out_host_pinned) {
     if (count == 0 || lanes == 0) return UZK_OK;
-    if (max_len == 0 || max_len > (1ull << 18)) { set_error("poly_eval_lanes: lengths must be 1 .. 2^18"); return UZK_ERR_PARAMETER; }
+    if (max_len == 0 || max_len > kEvalLanesMax) { set_error("poly_eval_lanes: lengths must be 1 .. 2^18"); return UZK_ERR_PARAMETER; }
     const LaneKernel pick = poly_eval_lanes_kernel_of(c, lanes, max_len);
     const bool wide = pick.wide, a29 = pick.a29;
     const uint64_t per_block = wide ? 4096 : 1024, blocks = (max_len + per_block - 1) / per_block;
@@ -523,12 +523,14 @@ void div_pows_fill(void* host_entry, const Fp& z, int per) {
     for (int k = 0; k < 8; ++k) { pw.zb[k] = p; p = Fr::sqr(p); }
 }
 size_t div_pows_bytes() { return sizeof(DivPowsL); }
-int open_div_per(uint64_t n) { return n <= (1ull << 16) ? 4 : 16; }
+// The carry scan holds 256 blocks of 256 * PER coefficients: PER = 16 reaches 2^20, and the n + 3 coefficients of the largest
+// circuit (n = 2^20) take PER = 32 (tests/test_gpu_rounds_large.py divides them against the oracle).
+int open_div_per(uint64_t n) { return n <= (1ull << 16) ? 4 : n <= (1ull << 20) ? 16 : 32; }
 // q_v = h_v div (X - z_v) for `count` openings: h_v (n coefficients) at d_h + v * h_stride, q_v (n - 1 coefficients, then zeros
-// up to q_cap) at d_q + v * q_stride; d_pows: `count` entries of div_pows_fill(open_div_per(n)).  n <= 2^20.  Asynchronous.
+// up to q_cap) at d_q + v * q_stride; d_pows: `count` entries of div_pows_fill(open_div_per(n)).  n <= 2^21.  Asynchronous.
 int open_div_lanes(Ctx& c, const Fp* d_h, uint64_t h_stride, uint64_t n, const void* d_pows, uint32_t count, Fp* d_q, uint64_t q_stride, uint64_t q_cap) {
     if (count == 0) return UZK_OK;
-    if (n == 0 || n > (1ull << 20) || q_cap < n) { set_error("open_div_lanes: need 1 <= n <= 2^20 and q_cap >= n"); return UZK_ERR_PARAMETER; }
+    if (n == 0 || n > (1ull << 21) || q_cap < n) { set_error("open_div_lanes: need 1 <= n <= 2^21 and q_cap >= n"); return UZK_ERR_PARAMETER; }
     const int per = open_div_per(n);
     const uint32_t nblocks = (uint32_t)((n + 256ull * per - 1) / (256ull * per));
     // s[count][n] | block_first[count][256] | carry[count][256] | ztab[count][257]
@@ -540,9 +542,11 @@ int open_div_lanes(Ctx& c, const Fp* d_h, uint64_t h_stride, uint64_t n, const v
     const DivPowsL* pw = static_cast<const DivPowsL*>(d_pows);
     KernelScope ks(c, "open_quotient");
     if (per == 4) hipLaunchKernelGGL(open_div_block_lanes_kernel<4>, dim3(nblocks, count), dim3(256), 0, c.stream, d_h, h_stride, n, pw, d_s, d_first);
+    else if (per == 32) hipLaunchKernelGGL(open_div_block_lanes_kernel<32>, dim3(nblocks, count), dim3(256), 0, c.stream, d_h, h_stride, n, pw, d_s, d_first);
     else hipLaunchKernelGGL(open_div_block_lanes_kernel<16>, dim3(nblocks, count), dim3(256), 0, c.stream, d_h, h_stride, n, pw, d_s, d_first);
     hipLaunchKernelGGL(open_div_carry_lanes_kernel, dim3(count), dim3(512), 0, c.stream, d_first, nblocks, pw, d_carry, d_ztab);
     if (per == 4) hipLaunchKernelGGL(open_div_apply_lanes_kernel<4>, dim3((unsigned)((q_cap + 255) / 256), count), dim3(256), 0, c.stream, d_s, d_carry, d_ztab, pw, n, q_cap, d_q, q_stride);
+    else if (per == 32) hipLaunchKernelGGL(open_div_apply_lanes_kernel<32>, dim3((unsigned)((q_cap + 255) / 256), count), dim3(256), 0, c.stream, d_s, d_carry, d_ztab, pw, n, q_cap, d_q, q_stride);
     else hipLaunchKernelGGL(open_div_apply_lanes_kernel<16>, dim3((unsigned)((q_cap + 255) / 256), count), dim3(256), 0, c.stream, d_s, d_carry, d_ztab, pw, n, q_cap, d_q, q_stride);
     UZK_HIP(hipGetLastError());
     return UZK_OK;
