@@ -181,6 +181,28 @@ int uzk_g1_fold(const uzk_g1_jac* partials, size_t count, uzk_g1_jac* out);
 /* Host-side Jacobian -> affine (for comparing results). */
 int uzk_g1_to_affine(const uzk_g1_jac* p, uzk_g1_affine* out);
 
+/* ---- G2: the MSM over b_g2_query of a Groth16 prover (ark-groth16's B in G2) ------------------------- */
+/* BN254 G2 points over Fq2 = Fq[u] / (u^2 + 1): every coordinate is c0 then c1, each 4 x u64 LE Montgomery words (ark-bn254's
+ * Fq2 as it lies in memory).  Affine infinity is all zeros, Jacobian infinity has z = 0. */
+typedef struct { uint64_t x[2][4], y[2][4]; } uzk_g2_affine;
+typedef struct { uint64_t x[2][4], y[2][4], z[2][4]; } uzk_g2_jac;
+/* One call handles up to 2^UZK_MSM_G2_MAX_LOG2 points (point chunks of 2^15 folded inside); beyond: UZK_ERR_DEGREE. */
+#define UZK_MSM_G2_MAX_LOG2 20
+/* Uploads n affine points to the calling context's device; the handle is process-wide (like an SRS handle) and is used by
+ * contexts on that device.  uzk_shutdown releases what is left. */
+int uzk_g2_register(const uzk_g2_affine* points, size_t n, uint64_t* handle_out);
+int uzk_g2_release(uint64_t handle);
+int uzk_g2_len(uint64_t handle, size_t* n_out);
+/* out = sum_{i<n} scalars[i] * bases[offset + i].  n == 0 -> infinity.  offset + n > len -> UZK_ERR_DEGREE.  Zero scalars and
+ * infinity bases contribute the identity; equal and opposite bases are handled (the reference's b_g2_query has all three). */
+int uzk_msm_g2(uint64_t handle, size_t offset, const uint64_t* scalars_mont, size_t n, uzk_g2_jac* out);
+/* `batch` scalar vectors (scalars[b*n + i]) against the same bases in one launch sequence: the reveal proofs of one deck. */
+int uzk_msm_g2_batch(uint64_t handle, size_t offset, const uint64_t* scalars_mont, size_t n, uint32_t batch, uzk_g2_jac* out);
+int uzk_msm_g2_batch_device(uint64_t handle, size_t offset, const void* d_scalars_mont, size_t n, uint32_t batch, uzk_g2_jac* out);
+/* Host-side fold of partial sums and Jacobian -> affine (canonical words), as for G1. */
+int uzk_g2_fold(const uzk_g2_jac* partials, size_t count, uzk_g2_jac* out);
+int uzk_g2_to_affine(const uzk_g2_jac* p, uzk_g2_affine* out);
+
 /* ---- NTT: replaces EvaluationDomain::{fft, ifft} (field_polynomial.rs:585,595) --------- */
 /* The largest transforms this library runs: n = 2^k with k <= UZK_NTT_MAX_LOG2, n = 3 * 2^k with k <= UZK_NTT_MAX_LOG2_MIXED.
  * These are exactly the largest sizes the parity suite compares with the CPU oracle on the whole vector
@@ -257,7 +279,7 @@ int uzk_ntt_g1_plan_info(uint64_t n, int inverse, uint64_t* doublings_out, uint6
  * uzk_srs_fold_powers folds the count - 1 equations P[i + 1] = tau P[i] of a run under random 128-bit weights into two points:
  *   left = sum_{i < count-1} rho_i P[offset+i]      right = sum_{i < count-1} rho_i P[offset+i+1]
  * and the run is a power sequence of tau  <=>  e(right, H) = e(left, [tau] H), except with probability 2^-128 over the seed.
- * Draw the seed AFTER the points are fixed.  The library has no G2: the pairing check, whether H and [tau] H are good G2 points,
+ * Draw the seed AFTER the points are fixed.  The library computes no pairing: the pairing check, whether H and [tau] H are good G2 points,
  * and whether P[0] is the generator the caller expects stay with the caller.  Points at infinity inside a run contribute the
  * identity, as in every MSM here (the curve report is where the caller sees them); run the curve check first -- the fold of a run
  * with off-curve points means nothing.
@@ -599,7 +621,7 @@ int uzk_prover_buffer(uint64_t prover, int which, void** d_out, uint64_t* elems_
  * is data-parallel over proofs and runs on the device: decoding and checking the proof bytes, the M Keccak transcripts, the
  * verifier scalars, and two MSMs (R over 16 M + 45 points, L over 2 M).  The commitments of the key are shared by the batch:
  * their scalars are summed in Fr and each enters the MSM once.  The pairing stays with the caller (arkworks'
- * Bn254::multi_pairing): the library holds no G2. */
+ * Bn254::multi_pairing): the library computes no pairing. */
 #define UZK_VERIFY_MAX_BATCH 4096
 #define UZK_VERIFY_MAX_PI 1024
 /* What PlonkVerifierParams (indexer.rs) carries, in the wire forms above: points in Montgomery form with (0,0) as infinity,

@@ -39,6 +39,11 @@ int uzk_test_const_operands(int field, int op, int form_a, int form_b, int porta
  * 17 ((a + b) - (a + b)) + a + (b + infinity) (cancellation, infinity on either side); 18..21 the same four by quads.
  * Inputs affine (infinity = zeros), outputs Jacobian. */
 int uzk_test_g1_kat(int op, const uzk_g1_affine* a, const uzk_g1_affine* b, uzk_g1_jac* out, size_t n);
+/* The G2 primitives (csrc/fq2_29.hpp, g2_29.hpp).  op 0..5 on Fq2 elements (a, b, out: n x 8 words, c0 then c1): 0 mul (two dual
+ * products), 1 sqr, 2 add, 3 sub, 4 neg, 5 mul (Karatsuba).  op 10..14 on points (a, b: n affine points of 16 words, infinity =
+ * zeros; out: n Jacobian points of 24 words): 10 a + b by the accumulator's mixed addition (complete: doubling, cancellation,
+ * infinity on either side), 11 a + b by the full XYZZ addition, 12 2a, 13 a - b (mixed, negated operand), 14 2(a + b). */
+int uzk_test_g2_kat(int op, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n);
 
 /* ---- raw 9 x 29-bit limbs: the primitives of the hot loops (fp29.hpp) and the typed lazy operations (lz29.hpp) at their bounds ----
  * in: n records of four operands a, b, c, d, 9 limbs (uint32) each, taken EXACTLY as given; out: n x 9 words, the raw result (no

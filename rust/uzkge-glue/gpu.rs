@@ -18,7 +18,7 @@ use std::any::TypeId;
 use std::collections::HashMap;
 use std::sync::{Arc, Mutex};
 
-use ark_bn254::{Fq, Fr, G1Affine, G1Projective};
+use ark_bn254::{Fq, Fq2, Fr, G1Affine, G1Projective, G2Affine, G2Projective};
 use ark_ec::CurveGroup;
 use ark_ff::{BigInt, PrimeField};
 use ark_poly::EvaluationDomain;
@@ -215,6 +215,51 @@ pub fn commit_batch(public_parameter_group_1: &[G1Projective], polys: &[&[Fr]]) 
         Err(sys::Error::Device) => Ok(None),
         Err(e) => Err(map_err(e)),
     }
+}
+
+// ---- G2: the `b_g2_query` term of a Groth16 proof's B (ark-groth16 computes it with `G2Projective::msm`) ----
+#[inline]
+fn fq2_limbs(s: &Fq2) -> [[u64; 4]; 2] {
+    [fq_limbs(&s.c0), fq_limbs(&s.c1)]
+}
+#[inline]
+fn fq2_from_limbs(l: &[[u64; 4]; 2]) -> Fq2 {
+    Fq2::new(Fq::new_unchecked(BigInt(l[0])), Fq::new_unchecked(BigInt(l[1])))
+}
+pub fn g2_affine_to_wire(p: &G2Affine) -> sys::uzk_g2_affine {
+    if p.infinity {
+        sys::uzk_g2_affine::default() // infinity = (0, 0), never on the twist
+    } else {
+        sys::uzk_g2_affine { x: fq2_limbs(&p.x), y: fq2_limbs(&p.y) }
+    }
+}
+fn g2_jac_from_wire(j: &sys::uzk_g2_jac) -> G2Projective {
+    // z == 0 is the identity in arkworks' Jacobian representation too
+    G2Projective::new_unchecked(fq2_from_limbs(&j.x), fq2_from_limbs(&j.y), fq2_from_limbs(&j.z))
+}
+/// Uploads the G2 bases of a proving key once (`pk.b_g2_query` of ark-groth16); keep the result next to the key.
+pub fn g2_bases(points: &[G2Affine]) -> Result<sys::G2Bases, UzkgeError> {
+    let wire: Vec<sys::uzk_g2_affine> = points.iter().map(g2_affine_to_wire).collect();
+    sys::G2Bases::register(&wire).map_err(map_err)
+}
+/// sum_i scalars[i] * bases[i] over the first `scalars.len()` bases: arkworks' Montgomery limbs are the wire words, as for G1.
+pub fn msm_g2(bases: &sys::G2Bases, scalars: &[Fr]) -> Result<G2Projective, UzkgeError> {
+    let wire: Vec<[u64; 4]> = scalars.iter().map(fr_limbs).collect();
+    bases.msm_g2(0, &wire).map(|j| g2_jac_from_wire(&j)).map_err(map_err)
+}
+/// The same for several scalar vectors (the reveal proofs of one deck) in one launch sequence; shorter vectors are zero-padded.
+pub fn msm_g2_batch(bases: &sys::G2Bases, vectors: &[&[Fr]]) -> Result<Vec<G2Projective>, UzkgeError> {
+    let n = vectors.iter().map(|v| v.len()).max().unwrap_or(0);
+    if n == 0 {
+        return Ok(vec![G2Projective::default(); vectors.len()]);
+    }
+    let mut flat = vec![[0u64; 4]; n * vectors.len()];
+    for (b, v) in vectors.iter().enumerate() {
+        for (d, c) in flat[b * n..].iter_mut().zip(v.iter()) {
+            *d = fr_limbs(c);
+        }
+    }
+    bases.msm_g2_batch(0, &flat, n).map(|v| v.iter().map(g2_jac_from_wire).collect()).map_err(map_err)
 }
 
 /// Once per domain size: is arkworks' `group_gen` the generator the library transforms over (5^((r-1)/n))?  A fork with

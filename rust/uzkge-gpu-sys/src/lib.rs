@@ -143,6 +143,47 @@ impl Drop for Srs {
     }
 }
 
+/// Device-resident G2 bases (the `b_g2_query` of a Groth16 proving key); released on drop.
+pub struct G2Bases {
+    handle: u64,
+    len: usize,
+}
+
+impl G2Bases {
+    /// Copies `points` to HBM once (`uzk_g2_register`).
+    pub fn register(points: &[uzk_g2_affine]) -> Result<Self, Error> {
+        let mut handle = 0u64;
+        check(unsafe { uzk_g2_register(points.as_ptr(), points.len(), &mut handle) })?;
+        Ok(G2Bases { handle, len: points.len() })
+    }
+    pub fn len(&self) -> usize { self.len }
+    pub fn is_empty(&self) -> bool { self.len == 0 }
+    pub fn handle(&self) -> u64 { self.handle }
+
+    /// sum_i scalars[i] * bases[offset + i]  (the G2 term of a Groth16 proof's B).
+    pub fn msm_g2(&self, offset: usize, scalars_mont: &[[u64; 4]]) -> Result<uzk_g2_jac, Error> {
+        let mut out = uzk_g2_jac::default();
+        check(unsafe { uzk_msm_g2(self.handle, offset, scalars_mont.as_ptr() as *const u64, scalars_mont.len(), &mut out) })?;
+        Ok(out)
+    }
+    /// `batch` vectors of `n` scalars each against the same bases: the reveal proofs of one deck in one launch sequence.
+    pub fn msm_g2_batch(&self, offset: usize, scalars_mont: &[[u64; 4]], n: usize) -> Result<Vec<uzk_g2_jac>, Error> {
+        if n == 0 || scalars_mont.len() % n != 0 {
+            return Err(Error::Parameter);
+        }
+        let batch = scalars_mont.len() / n;
+        let mut out = vec![uzk_g2_jac::default(); batch];
+        check(unsafe { uzk_msm_g2_batch(self.handle, offset, scalars_mont.as_ptr() as *const u64, n, batch as u32, out.as_mut_ptr()) })?;
+        Ok(out)
+    }
+}
+
+impl Drop for G2Bases {
+    fn drop(&mut self) {
+        unsafe { uzk_g2_release(self.handle) };
+    }
+}
+
 /// An SRS cut into contiguous point chunks over the GPUs of a node, driven from this one process (`uzk_srs_register_sharded`):
 /// chunk i = [i n / N, (i + 1) n / N) lives on `devices[i]`; `msm` runs the chunks side by side and folds the 96-byte partial
 /// sums on the host -- north_star's "MSM shards by point-chunk across the 8 GPUs of one node" behind one call.
@@ -284,7 +325,7 @@ impl Drop for Circuit {
 
 /// A verifier key resident on the device (`uzk_vk_create`), for batches of proofs: `fold` runs everything of the reference's verifier
 /// in front of its two pairings for m proofs at once and returns the two G1 points of the ONE check e(L, [tau] G2) = e(R, G2) that
-/// stands for all of them.  The pairing is the caller's (the library holds no G2).  Process-wide; released on drop.
+/// stands for all of them.  The pairing is the caller's (the library computes no pairing).  Process-wide; released on drop.
 pub struct VerifierKey {
     handle: u64,
     n_pi: usize,

@@ -57,6 +57,14 @@ PROTOTYPES = {
     "uzk_msm_g1_raw": (_I, [_P, _P, _SZ, _P]),
     "uzk_g1_fold": (_I, [_P, _SZ, _P]),
     "uzk_g1_to_affine": (_I, [_P, _P]),
+    "uzk_g2_register": (_I, [_P, _SZ, ctypes.POINTER(_U64)]),
+    "uzk_g2_release": (_I, [_U64]),
+    "uzk_g2_len": (_I, [_U64, ctypes.POINTER(_SZ)]),
+    "uzk_msm_g2": (_I, [_U64, _SZ, _P, _SZ, _P]),
+    "uzk_msm_g2_batch": (_I, [_U64, _SZ, _P, _SZ, ctypes.c_uint32, _P]),
+    "uzk_msm_g2_batch_device": (_I, [_U64, _SZ, _P, _SZ, ctypes.c_uint32, _P]),
+    "uzk_g2_fold": (_I, [_P, _SZ, _P]),
+    "uzk_g2_to_affine": (_I, [_P, _P]),
     "uzk_domain_supported": (_I, [_U64]),
     "uzk_domain_group_gen": (_I, [_U64, _P]),
     "uzk_ntt_fr": (_I, [_P, _U64, _I, _P]),
@@ -136,6 +144,7 @@ TEST_PROTOTYPES = {
     "uzk_test_field_kat": (_I, [_I, _I, _P, _P, _P, _SZ]),
     "uzk_test_const_operands": (_I, [_I, _I, _I, _I, _I, _P, _P, _P, _SZ]),
     "uzk_test_g1_kat": (_I, [_I, _P, _P, _P, _SZ]),
+    "uzk_test_g2_kat": (_I, [_I, _P, _P, _P, _SZ]),
     "uzk_test_circuit_truncate_t": (_I, [_U64, _I]),
     "uzk_test_l29_kat": (_I, [_I, _I, ctypes.c_uint32, _P, _P, _SZ]),
     "uzk_test_p29_kat": (_I, [_I, _P, _P, _SZ]),

@@ -255,6 +255,68 @@ def g1_to_affine(jac: np.ndarray) -> np.ndarray:
     return out
 
 
+class G2Bases:
+    """Device-resident G2 bases (b_g2_query of a Groth16 proving key): points [n, 16] = x.c0, x.c1, y.c0, y.c1 in Montgomery words,
+    infinity = zeros."""
+
+    def __init__(self, handle: int, n: int):
+        self.handle, self.n = handle, n
+
+    @classmethod
+    def from_host(cls, points: np.ndarray) -> "G2Bases":
+        pts = np.ascontiguousarray(points, dtype=np.uint64).reshape(-1, 16)
+        h = ctypes.c_uint64(0)
+        check(lib.uzk_g2_register(_ptr(pts) if pts.shape[0] else None, pts.shape[0], ctypes.byref(h)))
+        return cls(h.value, pts.shape[0])
+
+    def len(self) -> int:
+        n = ctypes.c_size_t(0)
+        check(lib.uzk_g2_len(self.handle, ctypes.byref(n)))
+        return n.value
+
+    def release(self) -> None:
+        if self.handle:
+            check(lib.uzk_g2_release(self.handle))
+            self.handle = 0
+
+
+def msm_g2(bases: G2Bases, scalars: np.ndarray, offset: int = 0) -> np.ndarray:
+    """sum_i scalars[i] * bases[offset + i] -> Jacobian [24]"""
+    s = np.ascontiguousarray(scalars, dtype=np.uint64).reshape(-1, 4)
+    out = np.zeros(24, dtype=np.uint64)
+    check(lib.uzk_msm_g2(bases.handle, offset, _ptr(s) if s.shape[0] else None, s.shape[0], _ptr(out)))
+    return out
+
+
+def msm_g2_batch(bases: G2Bases, scalars: np.ndarray, offset: int = 0) -> np.ndarray:
+    """scalars [batch, n, 4] against the same bases -> [batch, 24] Jacobian results."""
+    s = np.ascontiguousarray(scalars, dtype=np.uint64)
+    assert s.ndim == 3 and s.shape[2] == 4
+    out = np.zeros((s.shape[0], 24), dtype=np.uint64)
+    check(lib.uzk_msm_g2_batch(bases.handle, offset, _ptr(s) if s.size else None, s.shape[1], s.shape[0], _ptr(out)))
+    return out
+
+
+def msm_g2_batch_device(bases: G2Bases, d_scalars: int, n: int, batch: int, offset: int = 0) -> np.ndarray:
+    out = np.zeros((batch, 24), dtype=np.uint64)
+    check(lib.uzk_msm_g2_batch_device(bases.handle, offset, ctypes.c_void_p(d_scalars), n, batch, _ptr(out)))
+    return out
+
+
+def g2_fold(partials: np.ndarray) -> np.ndarray:
+    p = np.ascontiguousarray(partials, dtype=np.uint64).reshape(-1, 24)
+    out = np.zeros(24, dtype=np.uint64)
+    check(lib.uzk_g2_fold(_ptr(p) if p.shape[0] else None, p.shape[0], _ptr(out)))
+    return out
+
+
+def g2_to_affine(jac: np.ndarray) -> np.ndarray:
+    j = np.ascontiguousarray(jac, dtype=np.uint64).reshape(24)
+    out = np.zeros(16, dtype=np.uint64)
+    check(lib.uzk_g2_to_affine(_ptr(j), _ptr(out)))
+    return out
+
+
 def domain_supported(n: int) -> bool:
     return bool(lib.uzk_domain_supported(n))
 
@@ -503,6 +565,16 @@ def g1_op(op: int, a: np.ndarray, b: np.ndarray) -> np.ndarray:
     y = np.ascontiguousarray(b, dtype=np.uint64).reshape(-1, 8)
     out = np.zeros((x.shape[0], 12), dtype=np.uint64)
     check(lib.uzk_test_g1_kat(op, _ptr(x), _ptr(y), _ptr(out), x.shape[0]))
+    return out
+
+
+def g2_op(op: int, a: np.ndarray, b: np.ndarray) -> np.ndarray:
+    """uzk_test_g2_kat: op 0..5 on Fq2 elements [n, 8] -> [n, 8]; op 10..14 on affine points [n, 16] -> Jacobian [n, 24]"""
+    w_in, w_out = (16, 24) if op >= 10 else (8, 8)
+    x = np.ascontiguousarray(a, dtype=np.uint64).reshape(-1, w_in)
+    y = np.ascontiguousarray(b, dtype=np.uint64).reshape(-1, w_in)
+    out = np.zeros((x.shape[0], w_out), dtype=np.uint64)
+    check(lib.uzk_test_g2_kat(op, _ptr(x), _ptr(y), _ptr(out), x.shape[0]))
     return out
 
 

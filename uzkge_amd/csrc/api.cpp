@@ -11,6 +11,7 @@
 #include <new>
 
 #include "ctx.hpp"
+#include "g2_29.hpp"
 #include "host_ec64.hpp"
 #include "host_math.hpp"
 
@@ -224,6 +225,7 @@ static void ctx_release(Ctx& c) {
     ntt_free_plans(c);
     g1ntt_free(c);
     srscheck_free(c);
+    g2_free(c);
     c.verify_ws.release();
     msm_free(c);
     poly_free(c);
@@ -313,6 +315,7 @@ int uzk_shutdown(void) try {
     sharded_release_all();                 // sharded SRSs: their chunks' contexts and registry entries
     prover_release_all();                  // circuits and provers own device memory (takes Shared::mu itself)
     vf_release_all();                      // verifier keys
+    g2_release_all();                      // G2 bases
     std::lock_guard<std::mutex> lk(s.mu);
     if (!s.bound) return UZK_OK;
     ctx_release(default_ctx());
@@ -883,6 +886,82 @@ int uzk_g1_to_affine(const uzk_g1_jac* p, uzk_g1_affine* out) try {
     return UZK_OK;
 } catch (...) { return uzk::on_exception("uzk_g1_to_affine"); }
 
+/* ---- G2: bases, MSM, fold, affine map ------------------------------------------------------- */
+static int g2_checked(const char* who, uint64_t handle, size_t offset, size_t n, const G2Affine** d_points) {
+    size_t len = 0;
+    int device = 0;
+    if (!g2_lookup(handle, d_points, &len, &device)) { set_error("%s: unknown G2 handle %llu", who, (unsigned long long)handle); return UZK_ERR_PARAMETER; }
+    if (offset > len || n > len - offset) { set_error("%s: offset %zu + n %zu exceeds the %zu registered points", who, offset, n, len); return UZK_ERR_DEGREE; }
+    if (n > ((size_t)1 << UZK_MSM_G2_MAX_LOG2)) { set_error("%s: n %zu exceeds 2^%d points", who, n, UZK_MSM_G2_MAX_LOG2); return UZK_ERR_DEGREE; }
+    if (device != ctx().device) { set_error("%s: the bases live on device %d, the calling context on device %d", who, device, ctx().device); return UZK_ERR_PARAMETER; }
+    return UZK_OK;
+}
+
+int uzk_g2_register(const uzk_g2_affine* points, size_t n, uint64_t* handle_out) try {
+    API_LOCK;
+    if (!handle_out || (n > 0 && !points)) { set_error("uzk_g2_register: null pointer"); return UZK_ERR_PARAMETER; }
+    UZK_TRY(require_ready());
+    return g2_register(ctx(), reinterpret_cast<const G2Affine*>(points), n, handle_out);
+} catch (...) { return uzk::on_exception("uzk_g2_register"); }
+
+// The caller makes sure no context still runs an MSM over this handle.
+int uzk_g2_release(uint64_t handle) try {
+    API_LOCK;
+    if (!g2_lookup(handle, nullptr, nullptr, nullptr)) { set_error("uzk_g2_release: unknown handle %llu", (unsigned long long)handle); return UZK_ERR_PARAMETER; }
+    Ctx& c = ctx();
+    if (c.ready) (void)hipStreamSynchronize(c.stream);
+    if (!g2_release(handle)) { set_error("uzk_g2_release: unknown handle %llu", (unsigned long long)handle); return UZK_ERR_PARAMETER; }
+    return UZK_OK;
+} catch (...) { return uzk::on_exception("uzk_g2_release"); }
+
+int uzk_g2_len(uint64_t handle, size_t* n_out) try {
+    if (!n_out || !g2_lookup(handle, nullptr, n_out, nullptr)) { set_error("uzk_g2_len: unknown handle"); return UZK_ERR_PARAMETER; }
+    return UZK_OK;
+} catch (...) { return uzk::on_exception("uzk_g2_len"); }
+
+int uzk_msm_g2_batch_device(uint64_t handle, size_t offset, const void* d_scalars_mont, size_t n, uint32_t batch, uzk_g2_jac* out) try {
+    API_LOCK;
+    if (batch > 0 && (!out || (n > 0 && !d_scalars_mont))) { set_error("uzk_msm_g2_batch_device: null pointer"); return UZK_ERR_PARAMETER; }
+    if (!g2_lookup(handle, nullptr, nullptr, nullptr)) { set_error("uzk_msm_g2_batch_device: unknown G2 handle %llu", (unsigned long long)handle); return UZK_ERR_PARAMETER; }
+    UZK_TRY(require_ready());
+    const G2Affine* pts = nullptr;
+    UZK_TRY(g2_checked("uzk_msm_g2_batch_device", handle, offset, n, &pts));
+    return g2_msm_run(ctx(), pts + offset, static_cast<const Fp*>(d_scalars_mont), n, batch, reinterpret_cast<G2Jac*>(out));
+} catch (...) { return uzk::on_exception("uzk_msm_g2_batch_device"); }
+
+int uzk_msm_g2_batch(uint64_t handle, size_t offset, const uint64_t* scalars_mont, size_t n, uint32_t batch, uzk_g2_jac* out) try {
+    API_LOCK;
+    if (batch > 0 && (!out || (n > 0 && !scalars_mont))) { set_error("uzk_msm_g2_batch: null pointer"); return UZK_ERR_PARAMETER; }
+    if (!g2_lookup(handle, nullptr, nullptr, nullptr)) { set_error("uzk_msm_g2_batch: unknown G2 handle %llu", (unsigned long long)handle); return UZK_ERR_PARAMETER; }
+    UZK_TRY(require_ready());
+    Ctx& c = ctx();
+    const G2Affine* pts = nullptr;
+    UZK_TRY(g2_checked("uzk_msm_g2_batch", handle, offset, n, &pts));
+    const size_t bytes = n * (size_t)batch * sizeof(Fp);
+    if (bytes > 0) {
+        UZK_TRY(c.msm_scalars.reserve(bytes));
+        UZK_HIP(hipMemcpyAsync(c.msm_scalars.p, scalars_mont, bytes, hipMemcpyHostToDevice, c.stream));
+    }
+    return g2_msm_run(c, pts + offset, c.msm_scalars.as<Fp>(), n, batch, reinterpret_cast<G2Jac*>(out));
+} catch (...) { return uzk::on_exception("uzk_msm_g2_batch"); }
+
+int uzk_msm_g2(uint64_t handle, size_t offset, const uint64_t* scalars_mont, size_t n, uzk_g2_jac* out) try {
+    if (!out) { set_error("uzk_msm_g2: null pointer"); return UZK_ERR_PARAMETER; }
+    return uzk_msm_g2_batch(handle, offset, scalars_mont, n, 1, out);
+} catch (...) { return uzk::on_exception("uzk_msm_g2"); }
+
+int uzk_g2_fold(const uzk_g2_jac* partials, size_t count, uzk_g2_jac* out) try {
+    if (!out || (count > 0 && !partials)) { set_error("uzk_g2_fold: null pointer"); return UZK_ERR_PARAMETER; }
+    g2_fold_host(reinterpret_cast<const G2Jac*>(partials), count, reinterpret_cast<G2Jac*>(out));
+    return UZK_OK;
+} catch (...) { return uzk::on_exception("uzk_g2_fold"); }
+
+int uzk_g2_to_affine(const uzk_g2_jac* p, uzk_g2_affine* out) try {
+    if (!p || !out) { set_error("uzk_g2_to_affine: null pointer"); return UZK_ERR_PARAMETER; }
+    g2_to_affine_host(reinterpret_cast<const G2Jac*>(p), reinterpret_cast<G2Affine*>(out));
+    return UZK_OK;
+} catch (...) { return uzk::on_exception("uzk_g2_to_affine"); }
+
 /* ---- NTT ---------------------------------------------------------------------------------- */
 int uzk_domain_supported(uint64_t n) try { return domain_supported(n) ? 1 : 0; } catch (...) { return uzk::on_exception("uzk_domain_supported"); }
 
@@ -1425,6 +1504,14 @@ int uzk_test_g1_kat(int op, const uzk_g1_affine* a, const uzk_g1_affine* b, uzk_
     return g1_op_device(ctx(), op, reinterpret_cast<const Affine*>(a), reinterpret_cast<const Affine*>(b),
                         reinterpret_cast<Jac*>(out), n);
 } catch (...) { return uzk::on_exception("uzk_test_g1_kat"); }
+
+int uzk_test_g2_kat(int op, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n) try {
+    API_LOCK;
+    if (n > 0 && (!a || !b || !out)) { set_error("uzk_test_g2_kat: null pointer"); return UZK_ERR_PARAMETER; }
+    if (op < 0 || (op > 5 && op < 10) || op > 14) { set_error("uzk_test_g2_kat: bad op"); return UZK_ERR_PARAMETER; }
+    UZK_TRY(require_ready());
+    return g2_op_device(ctx(), op, a, b, out, n);
+} catch (...) { return uzk::on_exception("uzk_test_g2_kat"); }
 
 int uzk_test_l29_kat(int field, int op, uint32_t param, const uint32_t* in, uint32_t* out, size_t n) try {
     API_LOCK;

@@ -142,6 +142,8 @@ struct Ctx {
     // srscheck.hip: one record per workgroup of the curve kernel, the weights of a fold, the forward transform of a Lagrange
     // handle (grow-only)
     DevBuf srs_records, srs_weights, srs_points;
+    // g2msm.hip: the workspaces of the G2 MSM (G2Work*, grow-only)
+    void* g2 = nullptr;
     int tune_verify_transcript = 0;   // which transcript kernel a fold runs: 1 one proof per lane; 0 / 2 a proof's state spread over a half wave (the default)
     // an entry of the process-wide SRS registry
     struct Srs {
@@ -252,6 +254,19 @@ int srs_curve_run(Ctx& c, const Affine* d_points, uint64_t count, uzk_srs_curve_
 int srs_weights_run(Ctx& c, const uint8_t seed[32], uint64_t first, uint64_t count, Fp* d_out);
 void srs_weights_host(const uint8_t seed[32], uint64_t first, uint64_t count, Fp* out);
 void srscheck_free(Ctx& c);
+// g2msm.hip: the G2 base registry (process-wide handles, like the SRS registry), the MSM over device bases and device scalars, the
+// host-side fold / affine map, the known-answer kernel
+struct G2Affine;
+struct G2Jac;
+int g2_register(Ctx& c, const G2Affine* points, size_t n, uint64_t* handle_out);
+bool g2_lookup(uint64_t handle, const G2Affine** d_points, size_t* n, int* device);
+bool g2_release(uint64_t handle);
+void g2_release_all();
+void g2_free(Ctx& c);
+int g2_msm_run(Ctx& c, const G2Affine* d_points, const Fp* d_scalars, size_t n, uint32_t batch, G2Jac* out_host);
+void g2_fold_host(const G2Jac* partials, size_t count, G2Jac* out);
+void g2_to_affine_host(const G2Jac* p, G2Affine* out);
+int g2_op_device(Ctx& c, int op, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n);
 void msm_plan_info(Ctx& c, size_t n, int* window_bits, int* windows);
 int msm_run(Ctx& c, const Affine* points, const ScalarView& scalars, size_t n, uint32_t batch, Jac* out_host, int pre_c,
             uint32_t pre_stride, uint32_t pre_off);

@@ -447,7 +447,7 @@ class PlonkVerifierKey:
     """PlonkVerifierParams (uzkge/src/plonk/indexer.rs) resident on the device, for batches of proofs: `fold` runs everything of the
     verifier (verifier.rs:17-164) in front of its two pairings for m proofs at once and returns the two G1 points of the ONE check
         e(L, [tau] G2) = e(R, G2)
-    that stands for all of them.  The pairing is the caller's: this library holds no G2.
+    that stands for all of them.  The pairing is the caller's: this library computes none.
 
     vk: the key as integers -- cm_q (9 points), cm_s (5), cm_qb, cm_prk (4), k (5), anemoi_g, anemoi_g_inv, edwards_a, root, cs_size,
     pi_root_powers, pi_lagrange and, with the shuffle feature, cm_q_ecc, cm_shuffle_public_key (12), cm_shuffle_generator (12);
