@@ -58,6 +58,14 @@ int uzk_test_l29_kat(int field, int op, uint32_t param, const uint32_t* in, uint
 /* The lazy XYZZ additions of ec29l.hpp on raw coordinate limbs: record i of in is two points a, b (x, y, zz, zzz; 9 limbs each, 72
  * words), out[i] the raw result (36 words).  op: 0 a + b (p29_add), 1 2a (p29_dbl), 2 / 3 the same by the four lanes of a quad. */
 int uzk_test_p29_kat(int op, const uint32_t* in, uint32_t* out, size_t n);
+/* The G2 group law of g2_29.hpp on raw limbs.  A point is 73 words: x, y, zz, zzz, each c0 then c1 of 9 limbs, taken EXACTLY as given
+ * (nothing re-limbed or reduced), then an infinity flag.  Record i of in is two points a, b and a flag word (147 words); out[i] is one
+ * point, raw.  op: 0 g2p_add(a, b) on two G2P (every coordinate in 2^261-form, value < 16 M); 1 g2p_dbl(a); 2 g2acc_madd(a, p, flag)
+ * with a an accumulator (x, y in 2^261-form < 16 M, zz, zzz in 2^266-form < 2 M) and p the wire affine point in b (x, y: eight
+ * canonical words in the first eight limbs of each component; all zero = infinity), flag = negate; 3 the wire words of a, through
+ * g2p_store (flag 0) or g2acc_store (flag 1): eight words per component, the ninth 0, out's flag = a's; 4 q2::is_zero of a's x
+ * taken as E2<1, 32> (normalized or carry-step limbs, value < 32 M): the answer in out's flag, the coordinates zero. */
+int uzk_test_g2_raw_kat(int op, const uint32_t* in, uint32_t* out, size_t n);
 /* The prover's lane kernels (rounds.hip) on device polynomials: polynomial k of lane b holds its coefficients (wire elements) at
  * d_polys[k] + b * lane_strides[k] elements.  op 0, linear combination: lens[lanes][count] lengths, args[lanes][count] scalars,
  * out[lanes][len] = sum_k args[b][k] p_k,b (len = out_len).  op 1, evaluation: lens[count] lengths (every lane's), pts[count]

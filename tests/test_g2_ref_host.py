@@ -120,7 +120,7 @@ def test_host_fold_and_to_affine_match_the_reference(cols):
 
 def test_entry_points_check_arguments_before_the_device_and_need_one():
     from uzkge_amd import UzkgeError, _native as N, backend as b
-    z = np.zeros(64, dtype=np.uint64)
+    z = np.zeros(128, dtype=np.uint64)                               # room for one record of any hook (the raw one: 147 words)
     p = z.ctypes.data_as(ctypes.c_void_p)
     h, n = ctypes.c_uint64(0), ctypes.c_size_t(0)
     E = N.UZK_ERR_PARAMETER
@@ -137,9 +137,12 @@ def test_entry_points_check_arguments_before_the_device_and_need_one():
     assert N.lib.uzk_g2_fold(None, 1, p) == E and N.lib.uzk_g2_fold(p, 1, None) == E
     assert N.lib.uzk_g2_to_affine(None, p) == E and N.lib.uzk_g2_to_affine(p, None) == E
     assert N.lib.uzk_test_g2_kat(0, None, p, p, 1) == E and N.lib.uzk_test_g2_kat(7, p, p, p, 1) == E
+    assert N.lib.uzk_test_g2_raw_kat(0, None, p, 1) == E and N.lib.uzk_test_g2_raw_kat(0, p, None, 1) == E
+    assert N.lib.uzk_test_g2_raw_kat(5, p, p, 1) == E and N.lib.uzk_test_g2_raw_kat(-1, p, p, 1) == E
     if b.device_count() == 0:
         assert N.lib.uzk_g2_register(p, 1, ctypes.byref(h)) == N.UZK_ERR_DEVICE
         assert N.lib.uzk_test_g2_kat(0, p, p, p, 1) == N.UZK_ERR_DEVICE
+        assert N.lib.uzk_test_g2_raw_kat(0, p, p, 1) == N.UZK_ERR_DEVICE
         with pytest.raises(UzkgeError) as e:
             b.G2Bases.from_host(np.zeros((2, 16), dtype=np.uint64))
         assert e.value.kind == "DeviceError"

@@ -3,6 +3,7 @@ AST and diffed, as test_rust_shim.py does for the bindings), no type states a va
 of the products' column loops is exact at the extremes of every inventoried product signature -- and wraps one step outside the limb
 contract, so the inputs of tests/test_gpu_lz29_bounds.py reach the overflow that LzOps::cols_fit guards against."""
 import os
+import re
 import subprocess
 import sys
 
@@ -116,3 +117,45 @@ def test_reduce_estimate_covers_32M():
                 continue
             r = _model_reduce(lc.limbs(v), fld)
             assert 0 <= r < 2 * mod, (fld, v // mod)
+
+
+def _reaches_lz29(path, seen):
+    """Does the file include lz29.hpp, directly or through the headers it includes?  (Quoted includes, resolved next to the includer.)"""
+    path = os.path.normpath(path)
+    if path in seen or not os.path.exists(path):
+        return False
+    seen.add(path)
+    for inc in re.findall(r'^\s*#\s*include\s+"([^"]+)"', open(path).read(), re.M):
+        if os.path.basename(inc) == "lz29.hpp" or _reaches_lz29(os.path.join(os.path.dirname(path), inc), seen):
+            return True
+    return False
+
+
+def test_inventory_sources_are_the_include_closure():
+    """Every kernel file that reaches lz29.hpp through any chain of headers (g2msm.hip: g2_29.hpp -> fq2_29.hpp -> lz29.hpp) is a
+    source of the committed inventory; fieldops.hip, the test hooks generated from it, is the one exception.  Computed here from the
+    #include lines, not from the tool's own list."""
+    reaching = sorted(n for n in os.listdir(lc.CSRC) if n.endswith(".hip") and _reaches_lz29(os.path.join(lc.CSRC, n), set()))
+    assert "g2msm.hip" in reaching and "fieldops.hip" in reaching and "ntt.hip" not in reaching, reaching
+    head = "".join(line for line in open(os.path.join(lc.CSRC, "lz29_sigs.inc")) if line.startswith("//"))
+    named = re.search(r"Sources: ([^\n]*)\.\n", head).group(1).split(", ")
+    assert "g2msm.hip" in named and "fieldops.hip" not in named, named
+    missing = [n for n in reaching if n != "fieldops.hip" and n not in named]
+    assert not missing, f"reach lz29.hpp but are not inventoried: {missing}"
+
+
+def test_regenerating_keeps_the_indices_of_committed_signatures():
+    """An entry's index names its hook in fieldops.hip and its GPU test: the tool keeps a committed signature in its place, closes up
+    over dropped ones and appends new ones in sorted order; and the committed file is such a fixed point of its own order."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("lz29_inventory", os.path.join(ROOT, "tools", "lz29_inventory.py"))
+    inv = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(inv)
+    a, b, c, d = (("FQ", "add", ((1, 2), (1, 2)), (2, 4)), ("FQ", "sub", ((1, 2), (1, 2)), (2, 4)),
+                  ("FR", "mul", ((1, 2), (1, 2)), (1, 2)), ("FQ", "mul", ((1, 4), (1, 4)), (1, 2)))
+    assert inv.keep_indices([a, b, c], []) == [a, b, c]
+    assert inv.keep_indices([a, d, b, c], [c, a]) == [c, a, d, b]            # kept in the committed order, new ones after, sorted
+    assert inv.keep_indices([a, d, c], [b, c, a]) == [c, a, d]               # a dropped entry closes up
+    old = inv.committed()
+    assert [(s["field"], s["op"], tuple(s["args"]), s["res"] or (0, 0)) for s in lc.signatures()] == old
+    assert inv.keep_indices(sorted(old), old) == old

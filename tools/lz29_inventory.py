@@ -1,16 +1,22 @@
 #!/usr/bin/env python3
 """Inventory of the typed lazy 29-bit signatures the product instantiates (lz29.hpp's LzOps).
 
-Every source under uzkge_amd/csrc that includes lz29.hpp or ec29l.hpp is parsed by clang (device side, -fsyntax-only) with its AST
+Every .hip translation unit under uzkge_amd/csrc that reaches lz29.hpp through its #include "..." lines -- directly or through any
+chain of headers (g2msm.hip gets there by g2_29.hpp -> fq2_29.hpp) -- is parsed by clang (device side, -fsyntax-only) with its AST
 dumped for LzOps; every used member instantiation of the operations below is one (field, operation, operand types, result type).
 fieldops.hip is left out: it holds the test hooks, whose typed KAT ops and signature checks are not product code (and the latter
-are generated from this very list).  The list is written as an X-macro next to lz29.hpp:
+are generated from this very list).  The .cpp files stay in the source set: the Makefile compiles them as HIP (-x hip), so one that
+reaches lz29.hpp (api.cpp, through g2_29.hpp for its wire structs) could instantiate LzOps the day it gains a kernel.  With the G2 group law (g2_29.hpp, fq2_29.hpp) the list
+holds every typed operation of the G2 MSM's accumulator and XYZZ additions, the dual products with an un-normalised K = 4 operand
+among them.  The list is written as an X-macro next to lz29.hpp:
 
     LZ29_SIG(index, field, op, arity, Ka, Va, Kb, Vb, Kc, Vc, Kd, Vd, Kr, Vr)
 
 unused operands are 0, 0; canon and to_wire return wire words (Kr = Vr = 0).  The test hook (fieldops.hip) instantiates the typed
 sub / to_wire / canon of every entry, tests/lz29_contract.py parses the same file, and tests/test_lz29_contract.py regenerates it and
-fails on any difference -- a new kernel cannot add a signature without a test of it.
+fails on any difference -- a new kernel cannot add a signature without a test of it.  Indices are stable: a signature already in
+the committed file keeps its place and new ones are appended in sorted order (field, operation, types), so the G2-only entries
+follow the 183 that the G1 and scalar kernels had before; written afresh, without a committed file, the list is simply sorted.
 
     python tools/lz29_inventory.py            # rewrite uzkge_amd/csrc/lz29_sigs.inc
     python tools/lz29_inventory.py --check    # exit 1 if the committed file differs
@@ -36,15 +42,25 @@ _TYPE = re.compile(r"E<([^<>]*)>")
 _SIG = re.compile(r"^(Fp|E<[^<>]*>) \((.*)\)$")
 
 
+_INCLUDE = re.compile(r'^\s*#\s*include\s+"([^"]+)"', re.M)
+
+
+def reaches(path, target="lz29.hpp", seen=None):
+    """Does the file include `target`, directly or through headers it includes (quoted includes, resolved next to the includer)?"""
+    seen = set() if seen is None else seen
+    path = os.path.normpath(path)
+    if path in seen or not os.path.exists(path):
+        return False
+    seen.add(path)
+    for inc in _INCLUDE.findall(open(path).read()):
+        if os.path.basename(inc) == target or reaches(os.path.join(os.path.dirname(path), inc), target, seen):
+            return True
+    return False
+
+
 def sources():
-    out = []
-    for name in sorted(os.listdir(CSRC)):
-        if not name.endswith((".hip", ".cpp")) or name in EXCLUDED:
-            continue
-        text = open(os.path.join(CSRC, name)).read()
-        if re.search(r'#include\s+"(lz29|ec29l)\.hpp"', text):
-            out.append(name)
-    return out
+    return [name for name in sorted(os.listdir(CSRC))
+            if name.endswith((".hip", ".cpp")) and name not in EXCLUDED and reaches(os.path.join(CSRC, name))]
 
 
 def _int(expr: str) -> int:
@@ -100,12 +116,35 @@ def collect():
     sigs = set()
     for name in sources():
         cmd = [HIPCC, "--offload-arch=gfx950", "-std=c++17", "-I", os.path.join(ROOT, "include"), "-I", CSRC, "--cuda-device-only",
-               "-fsyntax-only", "-Xclang", "-ast-dump", "-Xclang", "-ast-dump-filter", "-Xclang", "LzOps", os.path.join(CSRC, name)]
+               "-x", "hip", "-fsyntax-only", "-Xclang", "-ast-dump", "-Xclang", "-ast-dump-filter", "-Xclang", "LzOps", os.path.join(CSRC, name)]
         res = subprocess.run(cmd, capture_output=True, text=True)
         if res.returncode != 0:
             raise RuntimeError(f"{name}: clang failed\n{res.stderr[-2000:]}")
         sigs |= parse_ast(res.stdout)
     return sorted(sigs, key=lambda s: (s[0], OPS.index(s[1]), s[2], s[3]))
+
+
+_LINE = re.compile(r"^LZ29_SIG\((.*)\)\s*$", re.M)
+
+
+def committed():
+    """The signatures of the committed file, in its order (none if there is no file)."""
+    out = []
+    for body in _LINE.findall(open(OUT).read() if os.path.exists(OUT) else ""):
+        f = [t.strip() for t in body.split(",")]
+        arity, nums = int(f[3]), [int(t) for t in f[4:]]
+        pairs = [(nums[2 * i], nums[2 * i + 1]) for i in range(5)]
+        out.append((f[1], f[2], tuple(pairs[:arity]), pairs[4]))
+    return out
+
+
+def keep_indices(sigs, old):
+    """An entry's index is its name -- the hooks of fieldops.hip switch on it and the tests' ids carry it -- so a signature that the
+    committed file already holds keeps its place (the places of dropped ones close up), and new ones follow in sorted order."""
+    have = set(sigs)
+    kept = [s for s in old if s in have]
+    seen = set(kept)
+    return kept + [s for s in sigs if s not in seen]
 
 
 def render(sigs) -> str:
@@ -122,7 +161,7 @@ def render(sigs) -> str:
 
 
 def main(argv):
-    text = render(collect())
+    text = render(keep_indices(collect(), committed()))
     if "--check" in argv:
         cur = open(OUT).read() if os.path.exists(OUT) else ""
         if cur != text:

@@ -148,6 +148,7 @@ TEST_PROTOTYPES = {
     "uzk_test_circuit_truncate_t": (_I, [_U64, _I]),
     "uzk_test_l29_kat": (_I, [_I, _I, ctypes.c_uint32, _P, _P, _SZ]),
     "uzk_test_p29_kat": (_I, [_I, _P, _P, _SZ]),
+    "uzk_test_g2_raw_kat": (_I, [_I, _P, _P, _SZ]),
     "uzk_test_keccak256": (_I, [_P, _P, ctypes.c_uint32, _P]),
     "uzk_test_srs_weights_device": (_I, [_P, _U64, _P]),
     "uzk_test_lanes": (_I, [_I, _P, _P, ctypes.c_uint32, _P, _P, _P, ctypes.c_uint32, _U64, _P, ctypes.POINTER(ctypes.c_int)]),

@@ -578,6 +578,14 @@ def g2_op(op: int, a: np.ndarray, b: np.ndarray) -> np.ndarray:
     return out
 
 
+def g2_raw_op(op: int, records: np.ndarray) -> np.ndarray:
+    """uzk_test_g2_raw_kat: [n, 147] uint32 records (two raw points of 73 words and a flag) -> [n, 73] raw points"""
+    x = np.ascontiguousarray(records, dtype=np.uint32).reshape(-1, 147)
+    out = np.zeros((x.shape[0], 73), dtype=np.uint32)
+    check(lib.uzk_test_g2_raw_kat(op, x.ctypes.data_as(ctypes.c_void_p), out.ctypes.data_as(ctypes.c_void_p), x.shape[0]))
+    return out
+
+
 def profile_enable(on: bool) -> None:
     check(lib.uzk_profile_enable(int(on)))
 

@@ -267,6 +267,7 @@ int g2_msm_run(Ctx& c, const G2Affine* d_points, const Fp* d_scalars, size_t n, 
 void g2_fold_host(const G2Jac* partials, size_t count, G2Jac* out);
 void g2_to_affine_host(const G2Jac* p, G2Affine* out);
 int g2_op_device(Ctx& c, int op, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n);
+int g2_raw_op_device(Ctx& c, int op, const uint32_t* in, uint32_t* out, size_t n);
 void msm_plan_info(Ctx& c, size_t n, int* window_bits, int* windows);
 int msm_run(Ctx& c, const Affine* points, const ScalarView& scalars, size_t n, uint32_t batch, Jac* out_host, int pre_c,
             uint32_t pre_stride, uint32_t pre_off);

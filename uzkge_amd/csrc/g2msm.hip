@@ -1,5 +1,5 @@
 // Multi-scalar multiplication over BN254 G2 (the b_g2_query term of a Groth16 proof's B): kernels, pipeline, base registry and the
-// known-answer kernel of uzk_test_g2_kat.  Design: DESIGN.md, "G2 MSM".
+// known-answer kernels of uzk_test_g2_kat and uzk_test_g2_raw_kat.  Design: DESIGN.md, "G2 MSM".
 //
 // One pass (n <= 2^15 points, `batch` scalar vectors over the same bases, vectors and windows on grid axes):
 //   g2_digits      scalar (Montgomery) -> canonical -> + 0x80..80: byte w of the sum, minus 128, is the signed digit of window w
@@ -201,6 +201,91 @@ __global__ __launch_bounds__(64) void g2_kat_kernel(int op, const void* __restri
 #endif
 }
 
+// The group law on RAW limbs (uzk_test_g2_raw_kat): coordinates are taken exactly as given -- nothing is re-limbed or reduced on the way
+// in, nothing canonicalised on the way out -- so a test can put every coordinate at the edge of the bound g2_29.hpp carries for it.
+struct G2RawPt {
+    uint32_t c[4][2][9];               // x, y, zz, zzz; each c0 then c1, nine limbs (op 3 out, op 2 in.b: eight wire words, the ninth 0)
+    uint32_t inf;
+};
+struct G2RawIn {
+    G2RawPt a, b;
+    uint32_t flag;
+};
+
+#if defined(__HIP_DEVICE_COMPILE__)
+template <int V>
+__device__ __forceinline__ q2::E2<1, V> g2raw_e2(const uint32_t (&c)[2][9]) {
+    q2::E2<1, V> r;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) { r.a.v.l[i] = c[0][i]; r.b.v.l[i] = c[1][i]; }
+    return r;
+}
+template <int V>
+__device__ __forceinline__ void g2raw_put(uint32_t (&c)[2][9], const q2::E2<1, V>& x) {
+#pragma unroll
+    for (int i = 0; i < 9; ++i) { c[0][i] = x.a.v.l[i]; c[1][i] = x.b.v.l[i]; }
+}
+__device__ __forceinline__ Fq2w g2raw_wire(const uint32_t (&c)[2][9]) {
+    Fq2w w;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) { w.c0.v[i] = c[0][i]; w.c1.v[i] = c[1][i]; }
+    return w;
+}
+__device__ __forceinline__ void g2raw_put_wire(uint32_t (&c)[2][9], const Fq2w& w) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) { c[0][i] = w.c0.v[i]; c[1][i] = w.c1.v[i]; }
+    c[0][8] = 0; c[1][8] = 0;
+}
+__device__ __forceinline__ G2P g2raw_point(const G2RawPt& r) {
+    G2P p;
+    p.x = g2raw_e2<16>(r.c[0]); p.y = g2raw_e2<16>(r.c[1]); p.zz = g2raw_e2<16>(r.c[2]); p.zzz = g2raw_e2<16>(r.c[3]);
+    p.inf = r.inf != 0;
+    return p;
+}
+__device__ __forceinline__ G2Acc g2raw_acc(const G2RawPt& r) {
+    G2Acc a;
+    a.x = g2raw_e2<16>(r.c[0]); a.y = g2raw_e2<16>(r.c[1]); a.zz = g2raw_e2<2>(r.c[2]); a.zzz = g2raw_e2<2>(r.c[3]);
+    a.inf = r.inf != 0;
+    return a;
+}
+#endif
+
+// op 0 g2p_add(a, b), 1 g2p_dbl(a), 2 g2acc_madd(a as accumulator, b.x / b.y as wire words, flag = negate), 3 g2p_store(a) (flag 0) or
+// g2acc_store(a) (flag 1) as wire words, 4 q2::is_zero of a's x as E2<1, 32> (the answer in out.inf)
+__global__ __launch_bounds__(64) void g2_raw_kat_kernel(int op, const G2RawIn* __restrict__ in, G2RawPt* __restrict__ out, size_t n) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    const size_t i = (size_t)blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    const G2RawIn rec = in[i];
+    G2RawPt r;
+    for (int k = 0; k < 4; ++k)
+        for (int j = 0; j < 2; ++j)
+            for (int l = 0; l < 9; ++l) r.c[k][j][l] = 0;
+    r.inf = 0;
+    if (op == 0 || op == 1) {
+        G2P p = g2raw_point(rec.a);
+        if (op == 0) g2p_add(p, g2raw_point(rec.b));
+        else g2p_dbl(p);
+        g2raw_put(r.c[0], p.x); g2raw_put(r.c[1], p.y); g2raw_put(r.c[2], p.zz); g2raw_put(r.c[3], p.zzz);
+        r.inf = p.inf;
+    } else if (op == 2) {
+        G2Acc a = g2raw_acc(rec.a);
+        G2Affine q;
+        q.x = g2raw_wire(rec.b.c[0]); q.y = g2raw_wire(rec.b.c[1]);
+        g2acc_madd(a, q, rec.flag != 0);
+        g2raw_put(r.c[0], a.x); g2raw_put(r.c[1], a.y); g2raw_put(r.c[2], a.zz); g2raw_put(r.c[3], a.zzz);
+        r.inf = a.inf;
+    } else if (op == 3) {
+        const G2XYZZ w = rec.flag != 0 ? g2acc_store(g2raw_acc(rec.a)) : g2p_store(g2raw_point(rec.a));
+        g2raw_put_wire(r.c[0], w.x); g2raw_put_wire(r.c[1], w.y); g2raw_put_wire(r.c[2], w.zz); g2raw_put_wire(r.c[3], w.zzz);
+        r.inf = rec.a.inf != 0;
+    } else {
+        r.inf = q2::is_zero(g2raw_e2<32>(rec.a.c[0]));
+    }
+    out[i] = r;
+#endif
+}
+
 // ---- host -------------------------------------------------------------------------------------------------------------------
 
 static G2Work& work(Ctx& c) {
@@ -370,6 +455,27 @@ int g2_op_device(Ctx& c, int op, const uint64_t* a, const uint64_t* b, uint64_t*
         G2Jac* jo = reinterpret_cast<G2Jac*>(out);
         for (size_t i = 0; i < n; ++i) jo[i] = h64::j2_to(h64::j2_from_xyzz(xy[i]));
     }
+    return UZK_OK;
+}
+
+// n records of G2RawIn (147 words) -> n records of G2RawPt (73 words), both on the host
+int g2_raw_op_device(Ctx& c, int op, const uint32_t* in, uint32_t* out, size_t n) {
+    if (n == 0) return UZK_OK;
+    static_assert(sizeof(G2RawIn) == 147 * sizeof(uint32_t) && sizeof(G2RawPt) == 73 * sizeof(uint32_t), "records are packed words");
+    G2RawIn* din = nullptr;
+    G2RawPt* dout = nullptr;
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&din), n * sizeof(G2RawIn));
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&dout), n * sizeof(G2RawPt));
+    if (e == hipSuccess) e = hipMemcpyAsync(din, in, n * sizeof(G2RawIn), hipMemcpyHostToDevice, c.stream);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(g2_raw_kat_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, c.stream, op, din, dout, n);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(out, dout, n * sizeof(G2RawPt), hipMemcpyDeviceToHost, c.stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c.stream);
+    if (din) (void)hipFree(din);
+    if (dout) (void)hipFree(dout);
+    UZK_HIP(e);
     return UZK_OK;
 }
 
