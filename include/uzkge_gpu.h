@@ -203,6 +203,70 @@ int uzk_msm_g2_batch_device(uint64_t handle, size_t offset, const void* d_scalar
 int uzk_g2_fold(const uzk_g2_jac* partials, size_t count, uzk_g2_jac* out);
 int uzk_g2_to_affine(const uzk_g2_jac* p, uzk_g2_affine* out);
 
+/* ---- Groth16: the prover of a reveal proof on a resident key, batched over the proofs of a deck --------------------------------
+ * Groth16::<Bn254>::prove (shuffle/src/sdk.rs:288-303) behind one call: the witness map (ark-groth16's
+ * LibsnarkReduction::witness_map_from_matrices), the three G1 MSMs, the G2 MSM and the assembly of (A, B, C).  Everything a proof
+ * needs is uploaded once by uzk_g16_key_create; per proof the caller passes the full assignment z (z[0] = 1, then the public
+ * inputs, then the private witness: n_vars elements) and the two blinding scalars r, s it has drawn.
+ *
+ * The R1CS matrices A, B, C arrive in CSR: row_ptr[k] has n_constraints + 1 entries (row_ptr[k][0] = 0, non-decreasing), col[k] and
+ * val[k] have row_ptr[k][n_constraints] entries (col < n_vars; val: Fr, 4 Montgomery words each); k = 0, 1, 2 for A, B, C.
+ * The domain has n = the smallest power of two >= n_constraints + n_inputs points.  The witness map, with g = 5 (Fr::GENERATOR):
+ *   a[i] = <A_i, z>, b[i] = <B_i, z>, c[i] = <C_i, z> for i < n_constraints;  a[n_constraints + j] = z[j] for j < n_inputs; zero up to n
+ *   a, b, c: inverse transform over the domain, forward transform over the coset g H
+ *   t = (a o b - c) / (g^n - 1);  h = the inverse coset transform of t  (n coefficients; h[n - 1] = 0 for a satisfying assignment)
+ * An assignment that does not satisfy the constraints is not detected (as in the reference): its proof does not verify.
+ *
+ * The proof, with the key's fixed terms riding in the MSMs as extra bases:
+ *   A  = MSM(a_query || alpha_g1 || delta_g1;      z || 1 || r)
+ *   B1 = MSM(b_g1_query || beta_g1 || delta_g1;    z || 1 || s)
+ *   B  = MSM(b_g2_query || beta_g2 || delta_g2;    z || 1 || s)          (G2)
+ *   K  = MSM(l_query || h_query || delta_g1;       z[n_inputs ..] || h[0 .. n - 1) || -r s)
+ *   C  = s A + r B1 + K
+ * The host does the two scalar multiplications and the two additions of C and the affine maps; z, a, b, c, h and the scalar rows stay
+ * on the device. */
+typedef struct {
+    uint32_t n_vars;            /* m: variables including the constant one; 1 <= n_inputs <= n_vars, n_vars + 2 <= 2^UZK_MSM_G2_MAX_LOG2 */
+    uint32_t n_inputs;          /* l: instance variables including the constant one */
+    uint32_t n_constraints;     /* rows of A, B, C; >= 1 */
+    uint32_t reserved;
+    uint64_t l_query_len;       /* must be n_vars - n_inputs */
+    uint64_t h_query_len;       /* must be n - 1 */
+    uzk_g1_affine alpha_g1, beta_g1, delta_g1;
+    uzk_g2_affine beta_g2, delta_g2;
+    const uzk_g1_affine* a_query;       /* n_vars points; infinity is all zeros (the reference's columns hold hundreds) */
+    const uzk_g1_affine* b_g1_query;    /* n_vars */
+    const uzk_g1_affine* l_query;       /* n_vars - n_inputs */
+    const uzk_g1_affine* h_query;       /* n - 1 */
+    const uzk_g2_affine* b_g2_query;    /* n_vars */
+    const uint64_t* row_ptr[3];
+    const uint32_t* col[3];
+    const uint64_t* val[3];
+} uzk_g16_key_desc;
+typedef struct { uzk_g1_affine a; uzk_g2_affine b; uzk_g1_affine c; } uzk_g16_proof;
+/* Proofs of one launch sequence; a larger batch runs as groups of this many. */
+#define UZK_G16_GROUP 128
+/* Checks the descriptor on the host (null pointers, 1 <= n_inputs <= n_vars, the two lengths, row pointers, col < n_vars:
+ * UZK_ERR_PARAMETER; uzk_domain_supported(n) == 0 or n_vars + 2 > 2^UZK_MSM_G2_MAX_LOG2: UZK_ERR_DEGREE) before the device is touched,
+ * then uploads everything to the calling context's device.  The handle is process-wide (like an SRS or G2 handle) and is used by
+ * contexts on that device; uzk_shutdown releases what is left. */
+int uzk_g16_key_create(const uzk_g16_key_desc* desc, uint64_t* key_out);
+/* The caller makes sure no context still proves with this key. */
+int uzk_g16_key_release(uint64_t key);
+/* n_vars, n_inputs, n_constraints, the domain size n and the device the key lives on; every output optional (NULL). */
+int uzk_g16_key_info(uint64_t key, uint32_t* n_vars_out, uint32_t* n_inputs_out, uint32_t* n_constraints_out, uint64_t* domain_out,
+                     int* device_out);
+/* The witness map alone: d_z = batch assignments of n_vars elements each (device), d_h = batch x n coefficients of h (device).
+ * The result is complete when the call returns. */
+int uzk_g16_h_device(uint64_t key, const void* d_z, uint32_t batch, void* d_h);
+/* batch proofs: z = batch x n_vars elements, r and s = batch elements each (host), out = batch proofs as affine points in the wire
+ * format (Montgomery words, fully reduced; infinity all zeros).  batch == 0 and an assignment with z[0] != 1 are UZK_ERR_PARAMETER. */
+int uzk_g16_prove_batch(uint64_t key, const uint64_t* z_mont, const uint64_t* r_mont, const uint64_t* s_mont, uint32_t batch,
+                        uzk_g16_proof* out);
+/* The same with the assignments already in device memory (a witness produced there); z[0] is not read back. */
+int uzk_g16_prove_batch_device(uint64_t key, const void* d_z_mont, const uint64_t* r_mont, const uint64_t* s_mont, uint32_t batch,
+                               uzk_g16_proof* out);
+
 /* ---- NTT: replaces EvaluationDomain::{fft, ifft} (field_polynomial.rs:585,595) --------- */
 /* The largest transforms this library runs: n = 2^k with k <= UZK_NTT_MAX_LOG2, n = 3 * 2^k with k <= UZK_NTT_MAX_LOG2_MIXED.
  * These are exactly the largest sizes the parity suite compares with the CPU oracle on the whole vector

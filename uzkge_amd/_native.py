@@ -65,6 +65,13 @@ PROTOTYPES = {
     "uzk_msm_g2_batch_device": (_I, [_U64, _SZ, _P, _SZ, ctypes.c_uint32, _P]),
     "uzk_g2_fold": (_I, [_P, _SZ, _P]),
     "uzk_g2_to_affine": (_I, [_P, _P]),
+    "uzk_g16_key_create": (_I, [_P, ctypes.POINTER(_U64)]),
+    "uzk_g16_key_release": (_I, [_U64]),
+    "uzk_g16_key_info": (_I, [_U64, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(_U64),
+                             ctypes.POINTER(_I)]),
+    "uzk_g16_h_device": (_I, [_U64, _P, ctypes.c_uint32, _P]),
+    "uzk_g16_prove_batch": (_I, [_U64, _P, _P, _P, ctypes.c_uint32, _P]),
+    "uzk_g16_prove_batch_device": (_I, [_U64, _P, _P, _P, ctypes.c_uint32, _P]),
     "uzk_domain_supported": (_I, [_U64]),
     "uzk_domain_group_gen": (_I, [_U64, _P]),
     "uzk_ntt_fr": (_I, [_P, _U64, _I, _P]),
@@ -238,6 +245,22 @@ class VkDesc(ctypes.Structure):
         ("cm_shuffle_public_key", _G1 * 12), ("cm_shuffle_generator", _G1 * 12), ("g1_0", _G1),
         ("k", (ctypes.c_uint64 * 4) * 5),
         ("anemoi_g", ctypes.c_uint64 * 4), ("anemoi_g_inv", ctypes.c_uint64 * 4), ("edwards_a", ctypes.c_uint64 * 4), ("root", ctypes.c_uint64 * 4),
+    ]
+
+
+G16_GROUP = 128
+_G2 = ctypes.c_uint64 * 16
+
+
+class G16KeyDesc(ctypes.Structure):
+    """uzk_g16_key_desc (include/uzkge_gpu.h)."""
+    _fields_ = [
+        ("n_vars", ctypes.c_uint32), ("n_inputs", ctypes.c_uint32), ("n_constraints", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
+        ("l_query_len", ctypes.c_uint64), ("h_query_len", ctypes.c_uint64),
+        ("alpha_g1", _G1), ("beta_g1", _G1), ("delta_g1", _G1), ("beta_g2", _G2), ("delta_g2", _G2),
+        ("a_query", ctypes.c_void_p), ("b_g1_query", ctypes.c_void_p), ("l_query", ctypes.c_void_p), ("h_query", ctypes.c_void_p),
+        ("b_g2_query", ctypes.c_void_p),
+        ("row_ptr", ctypes.c_void_p * 3), ("col", ctypes.c_void_p * 3), ("val", ctypes.c_void_p * 3),
     ]
 
 

@@ -317,6 +317,106 @@ def g2_to_affine(jac: np.ndarray) -> np.ndarray:
     return out
 
 
+class Groth16Key:
+    """A Groth16 proving key and its R1CS resident on the device (uzk_g16_key_create).  Points travel in the wire format: G1
+    [n, 8], G2 [n, 16], infinity = zeros; field elements [n, 4] Montgomery words.  `matrices` = three (row_ptr, col, val) triples in
+    CSR for A, B, C.  Use as a context manager, or release() it."""
+
+    def __init__(self, handle: int):
+        self.handle = handle
+        m, l, nc, n = ctypes.c_uint32(0), ctypes.c_uint32(0), ctypes.c_uint32(0), ctypes.c_uint64(0)
+        check(lib.uzk_g16_key_info(handle, ctypes.byref(m), ctypes.byref(l), ctypes.byref(nc), ctypes.byref(n), None))
+        self.n_vars, self.n_inputs, self.n_constraints, self.domain = m.value, l.value, nc.value, n.value
+
+    @staticmethod
+    def describe(n_vars: int, n_inputs: int, n_constraints: int, alpha_g1, beta_g1, delta_g1, beta_g2, delta_g2, a_query, b_g1_query,
+                 l_query, h_query, b_g2_query, matrices):
+        """(descriptor, the arrays it points into): what from_arrays hands to uzk_g16_key_create"""
+        d = N.G16KeyDesc()
+        keep = []
+
+        def arr(a, dtype, width):
+            a = np.ascontiguousarray(a, dtype=dtype)
+            if width:
+                a = a.reshape(-1, width)
+            keep.append(a)
+            return a
+
+        d.n_vars, d.n_inputs, d.n_constraints = n_vars, n_inputs, n_constraints
+        for name, v, width in (("alpha_g1", alpha_g1, 8), ("beta_g1", beta_g1, 8), ("delta_g1", delta_g1, 8), ("beta_g2", beta_g2, 16),
+                               ("delta_g2", delta_g2, 16)):
+            w = np.ascontiguousarray(v, dtype=np.uint64).reshape(width)
+            setattr(d, name, (ctypes.c_uint64 * width)(*[int(x) for x in w]))
+        for name, v, width in (("a_query", a_query, 8), ("b_g1_query", b_g1_query, 8), ("l_query", l_query, 8), ("h_query", h_query, 8),
+                               ("b_g2_query", b_g2_query, 16)):
+            a = arr(v, np.uint64, width)
+            setattr(d, name, a.ctypes.data if a.size else None)
+            if name in ("l_query", "h_query"):
+                setattr(d, name + "_len", a.shape[0])
+        for k, (row_ptr, col, val) in enumerate(matrices):
+            rp, cl, vl = arr(row_ptr, np.uint64, 0), arr(col, np.uint32, 0), arr(val, np.uint64, 4)
+            d.row_ptr[k] = rp.ctypes.data if rp.size else None
+            d.col[k] = cl.ctypes.data if cl.size else None
+            d.val[k] = vl.ctypes.data if vl.size else None
+        return d, keep
+
+    @classmethod
+    def from_arrays(cls, *args, **kwargs) -> "Groth16Key":
+        d, keep = cls.describe(*args, **kwargs)
+        h = ctypes.c_uint64(0)
+        check(lib.uzk_g16_key_create(ctypes.byref(d), ctypes.byref(h)))
+        del keep
+        return cls(h.value)
+
+    def h_device(self, d_z: int, batch: int, d_h: int) -> None:
+        """the witness map on device-resident assignments (batch x n_vars) -> batch x domain coefficients at d_h"""
+        check(lib.uzk_g16_h_device(self.handle, ctypes.c_void_p(d_z), batch, ctypes.c_void_p(d_h)))
+
+    def h(self, z: np.ndarray) -> np.ndarray:
+        """z [batch, n_vars, 4] -> h [batch, domain, 4]"""
+        z = np.ascontiguousarray(z, dtype=np.uint64).reshape(-1, self.n_vars, 4)
+        batch = z.shape[0]
+        d_z, d_h = dev_alloc(max(z.nbytes, 32)), dev_alloc(max(batch * self.domain * 32, 32))
+        try:
+            dev_upload(d_z, z)
+            self.h_device(d_z, batch, d_h)
+            return dev_download(d_h, (batch, self.domain, 4))
+        finally:
+            dev_free(d_z)
+            dev_free(d_h)
+
+    def prove(self, z: np.ndarray, r: np.ndarray, s: np.ndarray) -> np.ndarray:
+        """z [batch, n_vars, 4], r and s [batch, 4] -> proofs [batch, 32]: A (8 words), B (16), C (8), affine, infinity = zeros"""
+        z = np.ascontiguousarray(z, dtype=np.uint64).reshape(-1, self.n_vars, 4)
+        r = np.ascontiguousarray(r, dtype=np.uint64).reshape(-1, 4)
+        s = np.ascontiguousarray(s, dtype=np.uint64).reshape(-1, 4)
+        assert r.shape[0] == z.shape[0] and s.shape[0] == z.shape[0]
+        out = np.zeros((z.shape[0], 32), dtype=np.uint64)
+        check(lib.uzk_g16_prove_batch(self.handle, _ptr(z) if z.size else None, _ptr(r) if r.size else None, _ptr(s) if s.size else None,
+                                      z.shape[0], _ptr(out)))
+        return out
+
+    def prove_device(self, d_z: int, r: np.ndarray, s: np.ndarray) -> np.ndarray:
+        r = np.ascontiguousarray(r, dtype=np.uint64).reshape(-1, 4)
+        s = np.ascontiguousarray(s, dtype=np.uint64).reshape(-1, 4)
+        assert r.shape[0] == s.shape[0]
+        out = np.zeros((r.shape[0], 32), dtype=np.uint64)
+        check(lib.uzk_g16_prove_batch_device(self.handle, ctypes.c_void_p(d_z), _ptr(r) if r.size else None, _ptr(s) if s.size else None,
+                                             r.shape[0], _ptr(out)))
+        return out
+
+    def release(self) -> None:
+        if self.handle:
+            check(lib.uzk_g16_key_release(self.handle))
+            self.handle = 0
+
+    def __enter__(self) -> "Groth16Key":
+        return self
+
+    def __exit__(self, *exc) -> None:
+        self.release()
+
+
 def domain_supported(n: int) -> bool:
     return bool(lib.uzk_domain_supported(n))
 

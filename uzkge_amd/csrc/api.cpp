@@ -226,6 +226,7 @@ static void ctx_release(Ctx& c) {
     g1ntt_free(c);
     srscheck_free(c);
     g2_free(c);
+    g16_free(c);
     c.verify_ws.release();
     msm_free(c);
     poly_free(c);
@@ -316,6 +317,7 @@ int uzk_shutdown(void) try {
     prover_release_all();                  // circuits and provers own device memory (takes Shared::mu itself)
     vf_release_all();                      // verifier keys
     g2_release_all();                      // G2 bases
+    g16_release_all();                     // Groth16 proving keys
     std::lock_guard<std::mutex> lk(s.mu);
     if (!s.bound) return UZK_OK;
     ctx_release(default_ctx());
@@ -961,6 +963,68 @@ int uzk_g2_to_affine(const uzk_g2_jac* p, uzk_g2_affine* out) try {
     g2_to_affine_host(reinterpret_cast<const G2Jac*>(p), reinterpret_cast<G2Affine*>(out));
     return UZK_OK;
 } catch (...) { return uzk::on_exception("uzk_g2_to_affine"); }
+
+/* ---- Groth16: proving keys, the witness map, the batched prover ----------------------------- */
+int uzk_g16_key_create(const uzk_g16_key_desc* desc, uint64_t* key_out) try {
+    uint64_t domain = 0;
+    if (!key_out) { set_error("uzk_g16_key_create: null pointer"); return UZK_ERR_PARAMETER; }
+    UZK_TRY(g16_key_check(desc, &domain));            // host-only: before the device is touched
+    API_LOCK;
+    UZK_TRY(require_ready());
+    return g16_key_create(ctx(), desc, key_out);
+} catch (...) { return uzk::on_exception("uzk_g16_key_create"); }
+
+int uzk_g16_key_release(uint64_t key) try {
+    API_LOCK;
+    if (!g16_key_known(key, nullptr, nullptr, nullptr, nullptr, nullptr)) { set_error("uzk_g16_key_release: unknown handle %llu", (unsigned long long)key); return UZK_ERR_PARAMETER; }
+    Ctx& c = ctx();
+    if (c.ready) (void)hipStreamSynchronize(c.stream);
+    if (!g16_key_release(key)) { set_error("uzk_g16_key_release: unknown handle %llu", (unsigned long long)key); return UZK_ERR_PARAMETER; }
+    return UZK_OK;
+} catch (...) { return uzk::on_exception("uzk_g16_key_release"); }
+
+int uzk_g16_key_info(uint64_t key, uint32_t* n_vars_out, uint32_t* n_inputs_out, uint32_t* n_constraints_out, uint64_t* domain_out, int* device_out) try {
+    if (!g16_key_known(key, n_vars_out, n_inputs_out, n_constraints_out, domain_out, device_out)) { set_error("uzk_g16_key_info: unknown handle %llu", (unsigned long long)key); return UZK_ERR_PARAMETER; }
+    return UZK_OK;
+} catch (...) { return uzk::on_exception("uzk_g16_key_info"); }
+
+static int g16_checked(const char* who, uint64_t key) {
+    int device = 0;
+    if (!g16_key_known(key, nullptr, nullptr, nullptr, nullptr, &device)) { set_error("%s: unknown key handle %llu", who, (unsigned long long)key); return UZK_ERR_PARAMETER; }
+    UZK_TRY(require_ready());
+    if (device != ctx().device) { set_error("%s: the key lives on device %d, the calling context on device %d", who, device, ctx().device); return UZK_ERR_PARAMETER; }
+    return UZK_OK;
+}
+
+int uzk_g16_h_device(uint64_t key, const void* d_z, uint32_t batch, void* d_h) try {
+    API_LOCK;
+    if (batch == 0) { set_error("uzk_g16_h_device: batch is 0"); return UZK_ERR_PARAMETER; }
+    if (!d_z || !d_h) { set_error("uzk_g16_h_device: null pointer"); return UZK_ERR_PARAMETER; }
+    UZK_TRY(g16_checked("uzk_g16_h_device", key));
+    return g16_h_run(ctx(), key, static_cast<const Fp*>(d_z), batch, static_cast<Fp*>(d_h));
+} catch (...) { return uzk::on_exception("uzk_g16_h_device"); }
+
+static int g16_prove_common(const char* who, uint64_t key, const void* z, bool on_device, const uint64_t* r, const uint64_t* s, uint32_t batch, uzk_g16_proof* out) {
+    if (batch == 0) { set_error("%s: batch is 0", who); return UZK_ERR_PARAMETER; }
+    if (!z || !r || !s || !out) { set_error("%s: null pointer", who); return UZK_ERR_PARAMETER; }
+    uint32_t m = 0;
+    if (!g16_key_known(key, &m, nullptr, nullptr, nullptr, nullptr)) { set_error("%s: unknown key handle %llu", who, (unsigned long long)key); return UZK_ERR_PARAMETER; }
+    if (!on_device) {
+        const Fp one = Fr::one();
+        for (uint32_t b = 0; b < batch; ++b)
+            if (std::memcmp(static_cast<const Fp*>(z) + (size_t)b * m, &one, sizeof one) != 0) { set_error("%s: assignment %u does not start with the constant one", who, b); return UZK_ERR_PARAMETER; }
+    }
+    UZK_TRY(g16_checked(who, key));
+    return g16_prove_run(ctx(), key, static_cast<const Fp*>(z), on_device, as_fp(r), as_fp(s), batch, out);
+}
+int uzk_g16_prove_batch(uint64_t key, const uint64_t* z_mont, const uint64_t* r_mont, const uint64_t* s_mont, uint32_t batch, uzk_g16_proof* out) try {
+    API_LOCK;
+    return g16_prove_common("uzk_g16_prove_batch", key, z_mont, false, r_mont, s_mont, batch, out);
+} catch (...) { return uzk::on_exception("uzk_g16_prove_batch"); }
+int uzk_g16_prove_batch_device(uint64_t key, const void* d_z_mont, const uint64_t* r_mont, const uint64_t* s_mont, uint32_t batch, uzk_g16_proof* out) try {
+    API_LOCK;
+    return g16_prove_common("uzk_g16_prove_batch_device", key, d_z_mont, true, r_mont, s_mont, batch, out);
+} catch (...) { return uzk::on_exception("uzk_g16_prove_batch_device"); }
 
 /* ---- NTT ---------------------------------------------------------------------------------- */
 int uzk_domain_supported(uint64_t n) try { return domain_supported(n) ? 1 : 0; } catch (...) { return uzk::on_exception("uzk_domain_supported"); }

@@ -144,6 +144,8 @@ struct Ctx {
     DevBuf srs_records, srs_weights, srs_points;
     // g2msm.hip: the workspaces of the G2 MSM (G2Work*, grow-only)
     void* g2 = nullptr;
+    // groth16.hip: the workspaces of the Groth16 prover (G16Work*, grow-only)
+    void* g16 = nullptr;
     int tune_verify_transcript = 0;   // which transcript kernel a fold runs: 1 one proof per lane; 0 / 2 a proof's state spread over a half wave (the default)
     // an entry of the process-wide SRS registry
     struct Srs {
@@ -268,6 +270,15 @@ void g2_fold_host(const G2Jac* partials, size_t count, G2Jac* out);
 void g2_to_affine_host(const G2Jac* p, G2Affine* out);
 int g2_op_device(Ctx& c, int op, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n);
 int g2_raw_op_device(Ctx& c, int op, const uint32_t* in, uint32_t* out, size_t n);
+// groth16.hip: Groth16 proving keys (process-wide handles), the witness map and the batched prover
+int g16_key_check(const uzk_g16_key_desc* d, uint64_t* domain_out);
+int g16_key_create(Ctx& c, const uzk_g16_key_desc* d, uint64_t* out);
+bool g16_key_known(uint64_t h, uint32_t* n_vars, uint32_t* n_inputs, uint32_t* n_constraints, uint64_t* domain, int* device);
+bool g16_key_release(uint64_t h);
+void g16_release_all();
+void g16_free(Ctx& c);
+int g16_h_run(Ctx& c, uint64_t h, const Fp* d_z, uint32_t batch, Fp* d_h);
+int g16_prove_run(Ctx& c, uint64_t h, const Fp* z, bool z_on_device, const Fp* r_host, const Fp* s_host, uint32_t batch, uzk_g16_proof* out);
 void msm_plan_info(Ctx& c, size_t n, int* window_bits, int* windows);
 int msm_run(Ctx& c, const Affine* points, const ScalarView& scalars, size_t n, uint32_t batch, Jac* out_host, int pre_c,
             uint32_t pre_stride, uint32_t pre_off);

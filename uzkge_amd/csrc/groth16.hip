@@ -1,0 +1,420 @@
+// Groth16 prover on a resident proving key (uzk_g16_*): key registry, the witness map (sparse products, transforms, the pointwise
+// quotient), the scalar rows of the four MSMs and the host finish.  Design: DESIGN.md, "Groth16 prover".
+//
+// One group of up to UZK_G16_GROUP proofs (`nb` assignments z of m elements each, on the device):
+//   g16_transpose     zT[i * nb + w] = z[w * m + i]: the gathers below read nb consecutive elements per column
+//   g16_spmv_slices   one lane per (slice, witness): the rows of A, B, C (one matrix of 3 n_constraints rows) are cut into slices of at
+//                     most kSlice entries on the host when the key is made -- a bit-decomposition row of 254 entries becomes 8 slices,
+//                     so no lane walks a fat row while its wave waits; partial sums to HBM
+//   g16_spmv_rows     one lane per (matrix, domain point, witness): the sum of the row's partials, the input-consistency rows of a
+//                     (a[n_constraints + j] = z[j]) and the zero padding, written straight into the transform buffers
+//   ntt_run           3 nb inverse transforms, 3 nb forward transforms over the coset 5 H
+//   g16_pointwise     t = (a o b - c) / (5^n - 1)
+//   ntt_run           nb inverse coset transforms: h
+//   g16_scalar_rows   the scalar vectors of the MSMs: the tail (1, r) of A, z || 1 || s for B in G1 and G2,
+//                     z[l ..] || h[0 .. n - 1) || -r s for K
+//   msm_dispatch_view (A, B1, K) and g2_msm_run (B), then on the host C = s A + r B1 + K and the affine maps.
+#include <algorithm>
+#include <cstring>
+
+#include "ctx.hpp"
+#include "g2_29.hpp"
+#include "host_ec64.hpp"
+#include "host_g2.hpp"
+#include "host_math.hpp"
+
+namespace uzk {
+
+namespace {
+constexpr uint32_t kSlice = 32;                 // entries of a row one lane multiplies
+constexpr uint32_t kGroup = UZK_G16_GROUP;      // the G2 MSM's group: proofs of one launch sequence
+constexpr uint64_t kGroupElems = 1ull << 21;    // domain points of one group at most (bounds the transform buffers: 3 x 64 MiB)
+
+struct Slice {
+    uint32_t start, len;                        // entries [start, start + len) of the concatenated col / val arrays
+};
+
+struct G16Key {
+    uint32_t m = 0, l = 0, nc = 0, n_slices = 0;
+    uint64_t n = 0, nnz = 0;
+    int device = 0;
+    Affine *ga = nullptr, *gb1 = nullptr, *gk = nullptr;
+    G2Affine* gb2 = nullptr;
+    uint32_t *col = nullptr, *row_slice = nullptr;      // row_slice[3 nc + 1]: first slice of a row
+    Fp* val = nullptr;
+    Slice* slices = nullptr;
+    Fp shift, shift_inv, zh_inv;                        // 5, 1 / 5, 1 / (5^n - 1)
+};
+
+struct G16Work {
+    DevBuf z_in, zT, part, abc, tail_a, row_b, row_k, rs;
+};
+
+std::mutex g_mu;
+std::map<uint64_t, G16Key> g_reg;
+uint64_t g_next = 1;
+constexpr uint64_t kHandleTag = 1ull << 58;
+static_assert(sizeof(uzk_g16_key_desc) == 592 && sizeof(uzk_g16_proof) == 256, "the layouts the Python and Rust bindings mirror");
+
+void key_free(G16Key& k) {
+    (void)hipSetDevice(k.device);
+    void* ptrs[] = {k.ga, k.gb1, k.gk, k.gb2, k.col, k.row_slice, k.val, k.slices};
+    for (void* p : ptrs)
+        if (p) (void)hipFree(p);
+}
+}  // namespace
+
+// ---- kernels ----------------------------------------------------------------------------------------------------------------
+
+__global__ __launch_bounds__(256) void g16_transpose_kernel(const Fp* __restrict__ z, Fp* __restrict__ zT, uint32_t m, uint32_t nb) {
+    const uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= (uint64_t)m * nb) return;
+    const uint32_t w = (uint32_t)(t % nb), i = (uint32_t)(t / nb);
+    zT[t] = z[(uint64_t)w * m + i];
+}
+
+// part[s * nb + w] = sum over slice s of val[k] * z_w[col[k]]
+__global__ __launch_bounds__(256) void g16_spmv_slices_kernel(const Slice* __restrict__ slices, const uint32_t* __restrict__ col, const Fp* __restrict__ val,
+                                                              const Fp* __restrict__ zT, Fp* __restrict__ part, uint32_t n_slices, uint32_t nb) {
+    const uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= (uint64_t)n_slices * nb) return;
+    const uint32_t w = (uint32_t)(t % nb);
+    const Slice s = slices[t / nb];
+    Fp acc = Fr::zero();
+    for (uint32_t k = s.start; k < s.start + s.len; ++k) acc = Fr::add(acc, Fr::mul(val[k], zT[(uint64_t)col[k] * nb + w]));
+    part[t] = acc;
+}
+
+// abc[(mat * nb + w) * n + i]: row i of matrix `mat` times z_w for i < nc; z_w[i - nc] for the l input-consistency rows of a; zero beyond
+__global__ __launch_bounds__(256) void g16_spmv_rows_kernel(const uint32_t* __restrict__ row_slice, const Fp* __restrict__ part, const Fp* __restrict__ zT,
+                                                            Fp* __restrict__ abc, uint32_t nc, uint32_t l, uint64_t n, uint32_t nb) {
+    const uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= 3 * n * nb) return;
+    const uint32_t w = (uint32_t)(t % nb);
+    const uint64_t r = t / nb, i = r % n;
+    const uint32_t mat = (uint32_t)(r / n);
+    Fp acc = Fr::zero();
+    if (i < nc) {
+        const uint32_t row = mat * nc + (uint32_t)i;
+        for (uint32_t s = row_slice[row]; s < row_slice[row + 1]; ++s) acc = Fr::add(acc, part[(uint64_t)s * nb + w]);
+    } else if (mat == 0 && i < (uint64_t)nc + l) {
+        acc = zT[(i - nc) * nb + w];
+    }
+    abc[((uint64_t)mat * nb + w) * n + i] = acc;
+}
+
+// a[i] = (a[i] b[i] - c[i]) zh_inv over the `count` points of a group; b and c follow a at distance `count`
+__global__ __launch_bounds__(256) void g16_pointwise_kernel(Fp* __restrict__ abc, uint64_t count, Fp zh_inv) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= count) return;
+    abc[i] = Fr::mul(Fr::sub(Fr::mul(abc[i], abc[count + i]), abc[2 * count + i]), zh_inv);
+}
+
+// proof b = blockIdx.y:  tail_a = (1, r);  row_b = z || 1 || s;  row_k = z[l ..] || h[0 .. n - 1) || -r s
+__global__ __launch_bounds__(256) void g16_scalar_rows_kernel(const Fp* __restrict__ z, const Fp* __restrict__ h, const Fp* __restrict__ rs, Fp* __restrict__ tail_a,
+                                                              Fp* __restrict__ row_b, Fp* __restrict__ row_k, uint32_t m, uint32_t l, uint64_t n, uint32_t nb) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    const uint32_t b = blockIdx.y;
+    const uint64_t len_b = (uint64_t)m + 2, len_k = (uint64_t)(m - l) + n;
+    const Fp r = rs[b], s = rs[nb + b];
+    if (i < m) row_b[b * len_b + i] = z[(uint64_t)b * m + i];
+    else if (i == m) { row_b[b * len_b + i] = Fr::one(); tail_a[2 * b] = Fr::one(); }
+    else if (i == (uint64_t)m + 1) { row_b[b * len_b + i] = s; tail_a[2 * b + 1] = r; }
+    if (i < m - l) row_k[b * len_k + i] = z[(uint64_t)b * m + l + i];
+    else if (i < len_k - 1) row_k[b * len_k + i] = h[(uint64_t)b * n + (i - (m - l))];
+    else if (i == len_k - 1) row_k[b * len_k + i] = Fr::neg(Fr::mul(r, s));
+}
+
+// ---- keys -------------------------------------------------------------------------------------------------------------------
+
+// Everything that can be said about a descriptor without a device; *domain_out = n.
+int g16_key_check(const uzk_g16_key_desc* d, uint64_t* domain_out) {
+    if (!d) { set_error("uzk_g16_key_create: null descriptor"); return UZK_ERR_PARAMETER; }
+    const uint64_t m = d->n_vars, l = d->n_inputs, nc = d->n_constraints;
+    if (l < 1 || l > m) { set_error("uzk_g16_key_create: n_inputs %llu must be in 1 .. n_vars %llu", (unsigned long long)l, (unsigned long long)m); return UZK_ERR_PARAMETER; }
+    if (nc < 1) { set_error("uzk_g16_key_create: no constraints"); return UZK_ERR_PARAMETER; }
+    uint64_t n = 1;
+    while (n < nc + l) n <<= 1;
+    if (!domain_supported(n)) { set_error("uzk_g16_key_create: no evaluation domain of size %llu", (unsigned long long)n); return UZK_ERR_DEGREE; }
+    if (m + 2 > (1ull << UZK_MSM_G2_MAX_LOG2)) { set_error("uzk_g16_key_create: n_vars %llu exceeds the G2 MSM's 2^%d points", (unsigned long long)m, UZK_MSM_G2_MAX_LOG2); return UZK_ERR_DEGREE; }
+    if (d->l_query_len != m - l) { set_error("uzk_g16_key_create: l_query has %llu entries, n_vars - n_inputs = %llu", (unsigned long long)d->l_query_len, (unsigned long long)(m - l)); return UZK_ERR_PARAMETER; }
+    if (d->h_query_len != n - 1) { set_error("uzk_g16_key_create: h_query has %llu entries, the domain has %llu points", (unsigned long long)d->h_query_len, (unsigned long long)n); return UZK_ERR_PARAMETER; }
+    if (!d->a_query || !d->b_g1_query || !d->b_g2_query || (m > l && !d->l_query) || (n > 1 && !d->h_query)) { set_error("uzk_g16_key_create: null query column"); return UZK_ERR_PARAMETER; }
+    uint64_t total = 0;
+    for (int k = 0; k < 3; ++k) {
+        const uint64_t* rp = d->row_ptr[k];
+        if (!rp) { set_error("uzk_g16_key_create: null row pointers of matrix %d", k); return UZK_ERR_PARAMETER; }
+        if (rp[0] != 0) { set_error("uzk_g16_key_create: row_ptr[%d][0] is not 0", k); return UZK_ERR_PARAMETER; }
+        for (uint64_t i = 0; i < nc; ++i)
+            if (rp[i + 1] < rp[i]) { set_error("uzk_g16_key_create: row pointers of matrix %d decrease at row %llu", k, (unsigned long long)i); return UZK_ERR_PARAMETER; }
+        const uint64_t nnz = rp[nc];
+        if (nnz > 0 && (!d->col[k] || !d->val[k])) { set_error("uzk_g16_key_create: null entries of matrix %d", k); return UZK_ERR_PARAMETER; }
+        total += nnz;
+        if (total >= (1ull << 32)) { set_error("uzk_g16_key_create: more than 2^32 - 1 matrix entries"); return UZK_ERR_PARAMETER; }
+        for (uint64_t e = 0; e < nnz; ++e)
+            if (d->col[k][e] >= m) { set_error("uzk_g16_key_create: matrix %d, entry %llu: column %u >= n_vars %llu", k, (unsigned long long)e, d->col[k][e], (unsigned long long)m); return UZK_ERR_PARAMETER; }
+    }
+    *domain_out = n;
+    return UZK_OK;
+}
+
+template <class T>
+static int upload(Ctx& c, T** d_out, const std::vector<T>& v) {
+    *d_out = nullptr;
+    if (v.empty()) return UZK_OK;
+    UZK_HIP(hipMalloc(reinterpret_cast<void**>(d_out), v.size() * sizeof(T)));
+    UZK_HIP(hipMemcpyAsync(*d_out, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, c.stream));
+    return UZK_OK;
+}
+
+static int key_upload(Ctx& c, const uzk_g16_key_desc* d, G16Key& k) {
+    const uint32_t m = k.m, l = k.l, nc = k.nc;
+    const Affine *aq = reinterpret_cast<const Affine*>(d->a_query), *bq = reinterpret_cast<const Affine*>(d->b_g1_query),
+                 *lq = reinterpret_cast<const Affine*>(d->l_query), *hq = reinterpret_cast<const Affine*>(d->h_query);
+    Affine alpha, beta, delta;
+    std::memcpy(&alpha, &d->alpha_g1, sizeof alpha); std::memcpy(&beta, &d->beta_g1, sizeof beta); std::memcpy(&delta, &d->delta_g1, sizeof delta);
+    std::vector<Affine> ga(aq, aq + m), gb1(bq, bq + m), gk;
+    ga.push_back(alpha); ga.push_back(delta);
+    gb1.push_back(beta); gb1.push_back(delta);
+    gk.reserve((size_t)(m - l) + k.n);
+    if (m > l) gk.insert(gk.end(), lq, lq + (m - l));
+    if (k.n > 1) gk.insert(gk.end(), hq, hq + (k.n - 1));
+    gk.push_back(delta);
+    const G2Affine* b2 = reinterpret_cast<const G2Affine*>(d->b_g2_query);
+    std::vector<G2Affine> gb2(b2, b2 + m);
+    G2Affine beta2, delta2;
+    std::memcpy(&beta2, &d->beta_g2, sizeof beta2); std::memcpy(&delta2, &d->delta_g2, sizeof delta2);
+    gb2.push_back(beta2); gb2.push_back(delta2);
+    // the three matrices as one of 3 nc rows; every row cut into slices of at most kSlice entries
+    std::vector<uint32_t> col, row_slice((size_t)3 * nc + 1);
+    std::vector<Fp> val;
+    std::vector<Slice> slices;
+    col.reserve(k.nnz); val.reserve(k.nnz);
+    for (int mat = 0; mat < 3; ++mat) {
+        const uint64_t* rp = d->row_ptr[mat];
+        const uint32_t base = (uint32_t)col.size();
+        if (rp[nc] > 0) {
+            col.insert(col.end(), d->col[mat], d->col[mat] + rp[nc]);
+            const Fp* v = reinterpret_cast<const Fp*>(d->val[mat]);
+            val.insert(val.end(), v, v + rp[nc]);
+        }
+        for (uint32_t i = 0; i < nc; ++i) {
+            row_slice[(size_t)mat * nc + i] = (uint32_t)slices.size();
+            for (uint64_t lo = rp[i]; lo < rp[i + 1]; lo += kSlice)
+                slices.push_back(Slice{base + (uint32_t)lo, (uint32_t)std::min<uint64_t>(kSlice, rp[i + 1] - lo)});
+        }
+    }
+    row_slice[(size_t)3 * nc] = (uint32_t)slices.size();
+    k.n_slices = (uint32_t)slices.size();
+    UZK_TRY(upload(c, &k.ga, ga));
+    UZK_TRY(upload(c, &k.gb1, gb1));
+    UZK_TRY(upload(c, &k.gk, gk));
+    UZK_TRY(upload(c, &k.gb2, gb2));
+    UZK_TRY(upload(c, &k.col, col));
+    UZK_TRY(upload(c, &k.val, val));
+    UZK_TRY(upload(c, &k.slices, slices));
+    UZK_TRY(upload(c, &k.row_slice, row_slice));
+    UZK_HIP(hipStreamSynchronize(c.stream));          // the host vectors go out of scope
+    return UZK_OK;
+}
+
+int g16_key_create(Ctx& c, const uzk_g16_key_desc* d, uint64_t* out) {
+    G16Key k;
+    UZK_TRY(g16_key_check(d, &k.n));
+    k.m = d->n_vars; k.l = d->n_inputs; k.nc = d->n_constraints;
+    k.nnz = d->row_ptr[0][k.nc] + d->row_ptr[1][k.nc] + d->row_ptr[2][k.nc];
+    k.device = c.device;
+    k.shift = fr_from_u64(5);
+    k.shift_inv = fr_inv(k.shift);
+    k.zh_inv = fr_inv(Fr::sub(f_pow_u64<Fr>(k.shift, k.n), Fr::one()));
+    const int rc = key_upload(c, d, k);
+    if (rc != UZK_OK) { (void)hipStreamSynchronize(c.stream); key_free(k); return rc; }
+    std::lock_guard<std::mutex> lk(g_mu);
+    const uint64_t h = kHandleTag | g_next++;
+    g_reg[h] = k;
+    *out = h;
+    return UZK_OK;
+}
+
+static bool key_lookup(uint64_t h, G16Key* out) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    auto it = g_reg.find(h);
+    if (it == g_reg.end()) return false;
+    *out = it->second;
+    return true;
+}
+bool g16_key_known(uint64_t h, uint32_t* n_vars, uint32_t* n_inputs, uint32_t* n_constraints, uint64_t* domain, int* device) {
+    G16Key k;
+    if (!key_lookup(h, &k)) return false;
+    if (n_vars) *n_vars = k.m;
+    if (n_inputs) *n_inputs = k.l;
+    if (n_constraints) *n_constraints = k.nc;
+    if (domain) *domain = k.n;
+    if (device) *device = k.device;
+    return true;
+}
+bool g16_key_release(uint64_t h) {
+    G16Key k;
+    {
+        std::lock_guard<std::mutex> lk(g_mu);
+        auto it = g_reg.find(h);
+        if (it == g_reg.end()) return false;
+        k = it->second;
+        g_reg.erase(it);
+    }
+    key_free(k);
+    return true;
+}
+void g16_release_all() {
+    std::lock_guard<std::mutex> lk(g_mu);
+    for (auto& kv : g_reg) key_free(kv.second);
+    g_reg.clear();
+}
+
+// ---- the prover -------------------------------------------------------------------------------------------------------------
+
+static G16Work& work(Ctx& c) {
+    if (!c.g16) c.g16 = new G16Work();
+    return *static_cast<G16Work*>(c.g16);
+}
+void g16_free(Ctx& c) {
+    if (!c.g16) return;
+    G16Work* w = static_cast<G16Work*>(c.g16);
+    w->z_in.release(); w->zT.release(); w->part.release(); w->abc.release(); w->tail_a.release(); w->row_b.release(); w->row_k.release(); w->rs.release();
+    delete w;
+    c.g16 = nullptr;
+}
+
+static uint32_t group_of(const G16Key& k) { return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(kGroup, kGroupElems / k.n)); }
+static unsigned blocks(uint64_t threads) { return (unsigned)((threads + 255) / 256); }
+
+// h of nb <= group_of(k) assignments: left in the first nb * n elements of the work buffer `abc`
+static int h_group(Ctx& c, const G16Key& k, const Fp* d_z, uint32_t nb) {
+    G16Work& w = work(c);
+    const uint64_t n = k.n;
+    UZK_TRY(w.zT.reserve((size_t)k.m * nb * sizeof(Fp)));
+    UZK_TRY(w.part.reserve(std::max<size_t>(1, (size_t)k.n_slices * nb) * sizeof(Fp)));
+    UZK_TRY(w.abc.reserve((size_t)3 * n * nb * sizeof(Fp)));
+    Fp* abc = w.abc.as<Fp>();
+    c.cur_stream = c.stream;
+    {
+        KernelScope ks(c, "g16_transpose");
+        hipLaunchKernelGGL(g16_transpose_kernel, dim3(blocks((uint64_t)k.m * nb)), dim3(256), 0, c.stream, d_z, w.zT.as<Fp>(), k.m, nb);
+    }
+    if (k.n_slices > 0) {
+        KernelScope ks(c, "g16_spmv_slices");
+        hipLaunchKernelGGL(g16_spmv_slices_kernel, dim3(blocks((uint64_t)k.n_slices * nb)), dim3(256), 0, c.stream, k.slices, k.col, k.val, w.zT.as<Fp>(),
+                           w.part.as<Fp>(), k.n_slices, nb);
+    }
+    {
+        KernelScope ks(c, "g16_spmv_rows");
+        hipLaunchKernelGGL(g16_spmv_rows_kernel, dim3(blocks(3 * n * nb)), dim3(256), 0, c.stream, k.row_slice, w.part.as<Fp>(), w.zT.as<Fp>(), abc, k.nc, k.l, n, nb);
+    }
+    UZK_HIP(hipGetLastError());
+    UZK_TRY(ntt_run(c, abc, abc, n, true, nullptr, 3 * nb));
+    UZK_TRY(ntt_run(c, abc, abc, n, false, &k.shift, 3 * nb));
+    {
+        KernelScope ks(c, "g16_pointwise");
+        hipLaunchKernelGGL(g16_pointwise_kernel, dim3(blocks(n * nb)), dim3(256), 0, c.stream, abc, n * nb, k.zh_inv);
+    }
+    UZK_HIP(hipGetLastError());
+    UZK_TRY(ntt_run(c, abc, abc, n, true, &k.shift_inv, nb));
+    return UZK_OK;
+}
+
+int g16_h_run(Ctx& c, uint64_t h, const Fp* d_z, uint32_t batch, Fp* d_h) {
+    G16Key k;
+    if (!key_lookup(h, &k)) { set_error("uzk_g16_h_device: unknown key handle %llu", (unsigned long long)h); return UZK_ERR_PARAMETER; }
+    const uint32_t group = group_of(k);
+    for (uint32_t b0 = 0; b0 < batch; b0 += group) {
+        const uint32_t nb = std::min(group, batch - b0);
+        UZK_TRY(h_group(c, k, d_z + (size_t)b0 * k.m, nb));
+        UZK_HIP(hipMemcpyAsync(d_h + (size_t)b0 * k.n, work(c).abc.p, (size_t)nb * k.n * sizeof(Fp), hipMemcpyDeviceToDevice, c.stream));
+    }
+    UZK_HIP(hipStreamSynchronize(c.stream));
+    return UZK_OK;
+}
+
+// k P by double-and-add over the 254 bits of the canonical scalar
+static h64::J j_scalar_mul(const h64::J& p, const Fp& k_mont) {
+    const Fp k = Fr::from_mont(k_mont);
+    h64::J acc = h64::j_inf();
+    for (int bit = 253; bit >= 0; --bit) {
+        acc = h64::j_dbl(acc);
+        if ((k.v[bit >> 5] >> (bit & 31)) & 1) acc = h64::j_add(acc, p);
+    }
+    return acc;
+}
+
+int g16_prove_run(Ctx& c, uint64_t h, const Fp* z, bool z_on_device, const Fp* r_host, const Fp* s_host, uint32_t batch, uzk_g16_proof* out) {
+    G16Key k;
+    if (!key_lookup(h, &k)) { set_error("uzk_g16_prove_batch: unknown key handle %llu", (unsigned long long)h); return UZK_ERR_PARAMETER; }
+    G16Work& w = work(c);
+    const uint32_t group = group_of(k), m = k.m;
+    const uint64_t n = k.n, len_b = (uint64_t)m + 2, len_k = (uint64_t)(m - k.l) + n;
+    Ctx::Srs ga, gb1, gk;
+    ga.d_points = k.ga; ga.n = len_b; ga.device = k.device;
+    gb1.d_points = k.gb1; gb1.n = len_b; gb1.device = k.device;
+    gk.d_points = k.gk; gk.n = len_k; gk.device = k.device;
+    std::vector<Jac> ja(group), jb1(group), jk(group);
+    std::vector<G2Jac> jb2(group);
+    for (uint32_t b0 = 0; b0 < batch; b0 += group) {
+        const uint32_t nb = std::min(group, batch - b0);
+        const Fp* d_z = z + (size_t)b0 * m;
+        if (!z_on_device) {
+            UZK_TRY(w.z_in.reserve((size_t)nb * m * sizeof(Fp)));
+            UZK_HIP(hipMemcpyAsync(w.z_in.p, z + (size_t)b0 * m, (size_t)nb * m * sizeof(Fp), hipMemcpyHostToDevice, c.stream));
+            d_z = w.z_in.as<Fp>();
+        }
+        UZK_TRY(w.rs.reserve((size_t)2 * group * sizeof(Fp)));
+        UZK_HIP(hipMemcpyAsync(w.rs.p, r_host + b0, (size_t)nb * sizeof(Fp), hipMemcpyHostToDevice, c.stream));
+        UZK_HIP(hipMemcpyAsync(w.rs.as<Fp>() + nb, s_host + b0, (size_t)nb * sizeof(Fp), hipMemcpyHostToDevice, c.stream));
+        {
+            HostScope hs(c, "host_g16_h");
+            UZK_TRY(h_group(c, k, d_z, nb));
+            UZK_TRY(w.tail_a.reserve((size_t)2 * nb * sizeof(Fp)));
+            UZK_TRY(w.row_b.reserve((size_t)len_b * nb * sizeof(Fp)));
+            UZK_TRY(w.row_k.reserve((size_t)len_k * nb * sizeof(Fp)));
+            {
+                KernelScope ks(c, "g16_scalar_rows");
+                hipLaunchKernelGGL(g16_scalar_rows_kernel, dim3(blocks(std::max(len_b, len_k)), nb), dim3(256), 0, c.stream, d_z, w.abc.as<Fp>(), w.rs.as<Fp>(),
+                                   w.tail_a.as<Fp>(), w.row_b.as<Fp>(), w.row_k.as<Fp>(), m, k.l, n, nb);
+            }
+            UZK_HIP(hipGetLastError());
+            if (c.prof_on) UZK_HIP(hipStreamSynchronize(c.stream));     // so that the stage timers below hold one stage each
+        }
+        {
+            HostScope hs(c, "host_g16_msm_a");
+            ScalarView sv;                                              // z where it lies, the tail (1, r) behind it
+            sv.main = d_z; sv.stride = m; sv.n_main = m;
+            sv.tail = w.tail_a.as<Fp>(); sv.tail_n = 2;
+            UZK_TRY(msm_dispatch_view(ga, 0, sv, len_b, nb, ja.data()));
+        }
+        {
+            HostScope hs(c, "host_g16_msm_b1");
+            UZK_TRY(msm_dispatch_view(gb1, 0, ScalarView::dense(w.row_b.as<Fp>(), len_b), len_b, nb, jb1.data()));
+        }
+        {
+            HostScope hs(c, "host_g16_msm_k");
+            UZK_TRY(msm_dispatch_view(gk, 0, ScalarView::dense(w.row_k.as<Fp>(), len_k), len_k, nb, jk.data()));
+        }
+        {
+            HostScope hs(c, "host_g16_msm_g2");
+            UZK_TRY(g2_msm_run(c, k.gb2, w.row_b.as<Fp>(), len_b, nb, jb2.data()));
+        }
+        HostScope hs(c, "host_g16_finish");
+        for (uint32_t b = 0; b < nb; ++b) {
+            const h64::J A = h64::j_from(ja[b]), B1 = h64::j_from(jb1[b]);
+            const h64::J C = h64::j_add(h64::j_add(j_scalar_mul(A, s_host[b0 + b]), j_scalar_mul(B1, r_host[b0 + b])), h64::j_from(jk[b]));
+            const Affine a = jac_to_affine_host(ja[b]), cc = jac_to_affine_host(h64::j_to(C));
+            const G2Affine bb = h64::j2_to_affine(h64::j2_from(jb2[b]));
+            uzk_g16_proof& p = out[b0 + b];
+            std::memcpy(&p.a, &a, sizeof a);
+            std::memcpy(&p.b, &bb, sizeof bb);
+            std::memcpy(&p.c, &cc, sizeof cc);
+        }
+    }
+    return UZK_OK;
+}
+
+}  // namespace uzk
