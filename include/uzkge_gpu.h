@@ -730,6 +730,50 @@ int uzk_vk_set_public_key(uint64_t vk, const uzk_g1_affine pk[12]);
 int uzk_verify_fold(uint64_t vk, const uint8_t* proofs, const uint64_t* pi_mont, uint32_t m, const uint64_t* weights_mont,
                     uzk_g1_jac* left_out, uzk_g1_jac* right_out, uint8_t* status_out, uint64_t* challenges_out);
 
+/* ---- batch Groth16 verification: M reveal proofs folded into one pairing check -----------------------------------------------------
+ * A Groth16 proof (A, B, C) with public inputs x_1 .. x_(l-1) (x_0 = 1) is valid iff
+ *     e(A, B) = e(alpha, beta) e(X, gamma) e(C, delta),      X = sum_j x_j IC_j      (Groth16Verifier.sol verifyProof)
+ * With one weight rho_i per proof, M such equations collapse into ONE product of M + 3 Miller loops and one final exponentiation:
+ *     prod_i e(rho_i A_i, B_i) . e(-(sum rho) alpha, beta) . e(-sum rho_i X_i, gamma) . e(-sum rho_i C_i, delta) = 1,
+ *     sum rho_i X_i = (sum rho) IC_0 + sum_j (sum_i rho_i x_ij) IC_j.
+ * Everything in front of the pairings runs on the device: decoding and checking the proof bytes, the subgroup check of B, the M
+ * scalar multiplications rho_i A_i (normalised to affine), the l dot products in Fr and two MSMs (X over the key's l points, C over
+ * the M fresh ones).  The pairings stay with the caller: the library computes no pairing. */
+#define UZK_G16_VERIFY_MAX_BATCH 4096
+#define UZK_G16_VERIFY_MAX_INPUTS 1024
+#define UZK_G16_PROOF_BYTES 256
+typedef struct {
+    uint32_t n_inputs;                 /* l, the constant one included; 1 <= l <= UZK_G16_VERIFY_MAX_INPUTS */
+    uint32_t reserved;
+    uzk_g1_affine alpha_g1;
+    uzk_g2_affine beta_g2, gamma_g2, delta_g2;   /* the caller's side of the pairing; not used on the device */
+    const uzk_g1_affine* gamma_abc_g1; /* l points; infinity = all zeros */
+} uzk_g16_vk_desc;
+/* Checks the descriptor on the host (null pointers, n_inputs: UZK_ERR_PARAMETER) before the device is touched, then makes alpha_g1 and
+ * gamma_abc_g1 resident on the calling context's device.  The handle is process-wide; uzk_shutdown releases what is left. */
+int uzk_g16_vk_create(const uzk_g16_vk_desc* desc, uint64_t* vk_out);
+/* No fold over the key may still be running. */
+int uzk_g16_vk_release(uint64_t vk);
+/* l and the device the key lives on; every output optional. */
+int uzk_g16_vk_info(uint64_t vk, uint32_t* n_inputs_out, int* device_out);
+/* proofs       m blobs of UZK_G16_PROOF_BYTES: eight 32-byte big-endian words in the EVM order a.x, a.y, b.x.c1, b.x.c0, b.y.c1,
+ *              b.y.c0, c.x, c.y (shuffle/src/sdk.rs:306-319); all-zero coordinates are the point at infinity
+ * public_mont  m x (l - 1) elements of Fr; the leading one is implied
+ * weights_mont m elements of Fr drawn by the CALLER after it has seen the proofs (128 random bits suffice; any element is
+ *              accepted).  NULL only with m == 1: weight 1.  NULL with m > 1 is UZK_ERR_PARAMETER -- unweighted sums let errors cancel
+ * status_out   m bytes, the first check that fails: 0 = decoded and folded; 1 = a coordinate word is >= p; 2 = A or C is not on
+ *              y^2 = x^3 + 3, or B is not on the twist; 3 = B is on the twist but [r] B != O (the subgroup check of EIP-197's
+ *              precompile and of ark's Validate::Yes).  A proof with a nonzero status contributes NOTHING to any sum, its a_out and
+ *              b_out are zeros; the call still returns UZK_OK and the caller decides what a bad proof means
+ * a_out        m points: rho_i A_i, canonical affine words
+ * b_out        m points: B_i in the wire form of uzk_g2_affine
+ * alpha_out = (sum rho) alpha, x_out = sum rho_i X_i, c_out = sum rho_i C_i, the sums over the proofs with status 0.
+ * m == 0: three points at infinity.  m > UZK_G16_VERIFY_MAX_BATCH: UZK_ERR_PARAMETER.
+ * With m == 1 and weight 1 the three sums are alpha, X and C themselves. */
+int uzk_g16_verify_fold(uint64_t vk, const uint8_t* proofs, const uint64_t* public_mont, uint32_t m, const uint64_t* weights_mont,
+                        uzk_g1_affine* a_out, uzk_g2_affine* b_out, uzk_g1_jac* alpha_out, uzk_g1_jac* x_out, uzk_g1_jac* c_out,
+                        uint8_t* status_out);
+
 /* ---- synthetic workloads (bench / tests; generated on device, nothing uploaded) -------- */
 /* d_points[i] = (i + 1) * Q with Q = seed_scalar * G: n distinct valid G1 points whose discrete
  * logs relative to Q are known, so MSM(points, s) == (sum_i s_i (i+1)) * Q for any size. */

@@ -19,7 +19,7 @@ use std::collections::HashMap;
 use std::sync::{Arc, Mutex};
 
 use ark_bn254::{Fq, Fq2, Fr, G1Affine, G1Projective, G2Affine, G2Projective};
-use ark_ec::CurveGroup;
+use ark_ec::{AffineRepr, CurveGroup};
 use ark_ff::{BigInt, PrimeField};
 use ark_poly::EvaluationDomain;
 use lazy_static::lazy_static;
@@ -232,6 +232,15 @@ pub fn g2_affine_to_wire(p: &G2Affine) -> sys::uzk_g2_affine {
     } else {
         sys::uzk_g2_affine { x: fq2_limbs(&p.x), y: fq2_limbs(&p.y) }
     }
+}
+pub(crate) fn g2_affine_from_wire(p: &sys::uzk_g2_affine) -> G2Affine {
+    if p.x == [[0u64; 4]; 2] && p.y == [[0u64; 4]; 2] {
+        return G2Affine::identity(); // (0, 0) is the wire's point at infinity
+    }
+    G2Affine::new_unchecked(fq2_from_limbs(&p.x), fq2_from_limbs(&p.y))
+}
+pub(crate) fn g1_affine_from_wire(p: &sys::uzk_g1_affine) -> G1Affine {
+    affine_from_wire(p).into_affine()
 }
 fn g2_jac_from_wire(j: &sys::uzk_g2_jac) -> G2Projective {
     // z == 0 is the identity in arkworks' Jacobian representation too

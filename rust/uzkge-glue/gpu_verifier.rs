@@ -12,9 +12,9 @@
 use std::collections::HashMap;
 use std::sync::{Arc, Mutex};
 
-use ark_bn254::{Bn254, Fr, G1Projective};
+use ark_bn254::{Bn254, Fq, Fr, G1Affine, G1Projective, G2Affine};
 use ark_ec::{pairing::Pairing, CurveGroup};
-use ark_ff::{One, UniformRand};
+use ark_ff::{BigInteger, One, PrimeField, UniformRand};
 use ark_std::rand::{CryptoRng, RngCore};
 use lazy_static::lazy_static;
 use uzkge_gpu_sys as sys;
@@ -25,7 +25,7 @@ use super::{
     verifier::verifier,
 };
 use crate::{
-    gpu::{affine_to_wire, fr_limbs, jac_from_wire},
+    gpu::{affine_to_wire, fr_limbs, g1_affine_from_wire, g2_affine_from_wire, g2_affine_to_wire, jac_from_wire},
     poly_commit::{field_polynomial::FpPolynomial, kzg_poly_commitment::{KZGCommitment, KZGCommitmentSchemeBN254}, pcs::ToBytes},
     utils::transcript::Transcript,
 };
@@ -203,4 +203,90 @@ pub fn verify_batch<R: CryptoRng + RngCore, CS: ConstraintSystem<Fr>>(
         }
     }
     Some(Err(bad))
+}
+
+// ---- Groth16 reveal proofs: M proofs under one verifying key, M + 3 Miller loops, one final exponentiation ----------------------
+
+/// A Groth16 verifying key as the fold needs it (ark-groth16's `VerifyingKey<Bn254>`, field by field).
+pub struct RevealVerifyingKey<'a> {
+    pub alpha_g1: &'a G1Affine,
+    pub beta_g2: &'a G2Affine,
+    pub gamma_g2: &'a G2Affine,
+    pub delta_g2: &'a G2Affine,
+    pub gamma_abc_g1: &'a [G1Affine],
+}
+
+fn word(out: &mut Vec<u8>, c: &Fq) {
+    out.extend(c.into_bigint().to_bytes_be());
+}
+/// The 256-byte blob of a proof: a.x, a.y, b.x.c1, b.x.c0, b.y.c1, b.y.c0, c.x, c.y as 32-byte big-endian words (the order in
+/// which shuffle/src/sdk.rs:306-319 emits them for the contract); the point at infinity is zeros.
+pub fn reveal_proof_bytes(a: &G1Affine, b: &G2Affine, c: &G1Affine) -> Vec<u8> {
+    let mut out = Vec::with_capacity(sys::UZK_G16_PROOF_BYTES as usize);
+    let zero = Fq::from(0u64);
+    let g1 = |out: &mut Vec<u8>, p: &G1Affine| {
+        if p.infinity { word(out, &zero); word(out, &zero); } else { word(out, &p.x); word(out, &p.y); }
+    };
+    g1(&mut out, a);
+    if b.infinity {
+        for _ in 0..4 { word(&mut out, &zero); }
+    } else {
+        word(&mut out, &b.x.c1); word(&mut out, &b.x.c0); word(&mut out, &b.y.c1); word(&mut out, &b.y.c0);
+    }
+    g1(&mut out, c);
+    out
+}
+
+/// Checks `batch` = [(public inputs without the leading one, (A, B, C))] under `vk` with ONE product of pairings: the weights are
+/// drawn here, after every proof of the batch is fixed; `uzk_g16_verify_fold` decodes and checks the points (B's subgroup included),
+/// computes rho_i A_i and the three sums on the device; the M + 3 Miller loops and the final exponentiation are arkworks'.
+///   Some(Ok(()))        every proof is accepted
+///   Some(Err(indices))  malformed proofs (a nonzero status), or -- an empty list -- a well-formed batch whose product is not one:
+///                       the caller then checks proof by proof to name the wrong ones
+///   None                the device could not serve the call: nothing was decided
+pub fn fold_reveals<R: CryptoRng + RngCore>(prng: &mut R, vk: &RevealVerifyingKey, batch: &[(&[Fr], (G1Affine, G2Affine, G1Affine))]) -> Option<Result<(), Vec<usize>>> {
+    if batch.is_empty() {
+        return Some(Ok(()));
+    }
+    let l = vk.gamma_abc_g1.len();
+    if batch.len() > sys::UZK_G16_VERIFY_MAX_BATCH as usize || l == 0 || l > sys::UZK_G16_VERIFY_MAX_INPUTS as usize {
+        return None;
+    }
+    let ic: Vec<sys::uzk_g1_affine> = vk.gamma_abc_g1.iter().map(affine_to_wire).collect();
+    let desc = sys::uzk_g16_vk_desc {
+        n_inputs: l as u32,
+        reserved: 0,
+        alpha_g1: affine_to_wire(vk.alpha_g1),
+        beta_g2: g2_affine_to_wire(vk.beta_g2),
+        gamma_g2: g2_affine_to_wire(vk.gamma_g2),
+        delta_g2: g2_affine_to_wire(vk.delta_g2),
+        gamma_abc_g1: ic.as_ptr(),
+    };
+    let key = sys::Groth16Vk::create(&desc).ok()?;
+    let mut proofs = Vec::with_capacity(batch.len() * sys::UZK_G16_PROOF_BYTES as usize);
+    let mut public: Vec<Limbs> = Vec::with_capacity(batch.len() * (l - 1));
+    for (inputs, (a, b, c)) in batch {
+        if inputs.len() != l - 1 {
+            return None;
+        }
+        proofs.extend(reveal_proof_bytes(a, b, c));
+        public.extend(inputs.iter().map(fr_limbs));
+    }
+    let weights: Vec<Limbs> = if batch.len() == 1 { vec![fr_limbs(&Fr::one())] } else { (0..batch.len()).map(|_| fr_limbs(&Fr::rand(prng))).collect() };
+    let fold = key.fold(&proofs, &public, Some(&weights)).ok()?;
+    let malformed: Vec<usize> = fold.status.iter().enumerate().filter(|(_, s)| **s != 0).map(|(i, _)| i).collect();
+    if !malformed.is_empty() {
+        return Some(Err(malformed));
+    }
+    let mut g1: Vec<G1Affine> = fold.a.iter().map(g1_affine_from_wire).collect();
+    let mut g2: Vec<G2Affine> = fold.b.iter().map(g2_affine_from_wire).collect();
+    for (sum, q) in [(&fold.alpha, vk.beta_g2), (&fold.x, vk.gamma_g2), (&fold.c, vk.delta_g2)] {
+        g1.push((-jac_from_wire(sum)).into_affine());
+        g2.push(*q);
+    }
+    if Bn254::multi_pairing(g1, g2).0 == <Bn254 as Pairing>::TargetField::one() {
+        Some(Ok(()))
+    } else {
+        Some(Err(Vec::new()))
+    }
 }

@@ -377,6 +377,76 @@ impl Drop for VerifierKey {
     }
 }
 
+/// What `Groth16Vk::fold` returns: the G1 arguments of the ONE product of m + 3 Miller loops that stands for m proofs.
+pub struct Groth16Fold {
+    /// rho_i A_i, canonical affine words (zeros for a proof with a nonzero status)
+    pub a: Vec<uzk_g1_affine>,
+    /// B_i in the wire form (zeros for a proof with a nonzero status)
+    pub b: Vec<uzk_g2_affine>,
+    /// (sum rho) alpha, sum rho_i X_i, sum rho_i C_i over the proofs with status 0
+    pub alpha: uzk_g1_jac,
+    pub x: uzk_g1_jac,
+    pub c: uzk_g1_jac,
+    /// 0 folded; 1 a word >= p; 2 a point off its curve; 3 B outside the subgroup
+    pub status: Vec<u8>,
+}
+
+/// A Groth16 verifying key resident on the device (`uzk_g16_vk_create`), for batches of proofs.  The pairings are the caller's
+/// (the library computes no pairing).  Process-wide; released on drop.
+pub struct Groth16Vk {
+    handle: u64,
+    n_inputs: usize,
+}
+impl Groth16Vk {
+    /// `desc` and everything it points to are read before this returns.
+    pub fn create(desc: &uzk_g16_vk_desc) -> Result<Self, Error> {
+        let mut handle = 0u64;
+        check(unsafe { uzk_g16_vk_create(desc, &mut handle) })?;
+        let (mut l, mut dev) = (0u32, 0 as c_int);
+        if let Err(e) = check(unsafe { uzk_g16_vk_info(handle, &mut l, &mut dev) }) {
+            unsafe { uzk_g16_vk_release(handle) };
+            return Err(e);
+        }
+        Ok(Groth16Vk { handle, n_inputs: l as usize })
+    }
+    /// l, the constant one included.
+    pub fn n_inputs(&self) -> usize { self.n_inputs }
+    /// `proofs`: m blobs of `UZK_G16_PROOF_BYTES`, back to back; `public`: m x (l - 1) inputs; `weights`: one element per proof,
+    /// drawn by the caller AFTER it has the proofs (None only for one proof: weight 1).
+    pub fn fold(&self, proofs: &[u8], public: &[Limbs], weights: Option<&[Limbs]>) -> Result<Groth16Fold, Error> {
+        let blob = UZK_G16_PROOF_BYTES as usize;
+        if proofs.len() % blob != 0 {
+            return Err(Error::Parameter);
+        }
+        let m = proofs.len() / blob;
+        if public.len() != m * (self.n_inputs - 1) || weights.map_or(m > 1, |w| w.len() != m) {
+            return Err(Error::Parameter);
+        }
+        let mut out = Groth16Fold {
+            a: vec![uzk_g1_affine::default(); m.max(1)],
+            b: vec![uzk_g2_affine::default(); m.max(1)],
+            alpha: uzk_g1_jac::default(),
+            x: uzk_g1_jac::default(),
+            c: uzk_g1_jac::default(),
+            status: vec![0u8; m.max(1)],
+        };
+        let w_ptr = weights.map_or(std::ptr::null(), |w| w.as_ptr() as *const u64);
+        check(unsafe {
+            uzk_g16_verify_fold(self.handle, proofs.as_ptr(), public.as_ptr() as *const u64, m as u32, w_ptr, out.a.as_mut_ptr(), out.b.as_mut_ptr(),
+                                &mut out.alpha, &mut out.x, &mut out.c, out.status.as_mut_ptr())
+        })?;
+        out.a.truncate(m);
+        out.b.truncate(m);
+        out.status.truncate(m);
+        Ok(out)
+    }
+}
+impl Drop for Groth16Vk {
+    fn drop(&mut self) {
+        unsafe { uzk_g16_vk_release(self.handle) };
+    }
+}
+
 /// How provers of ONE proof made from now on are shared between threads (`uzk_coalesce_config`): the library runs round calls of
 /// several threads that stand at the same round of proofs over the same circuit as one lockstep launch sequence.  On by default
 /// (at most 8 proofs per sequence, the provers at work spread over 4 sequences, 2000 us gathering wait -- include/uzkge_gpu.h; 0 = a default);

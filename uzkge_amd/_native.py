@@ -128,6 +128,10 @@ PROTOTYPES = {
     "uzk_vk_info": (_I, [_U64, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(_I)]),
     "uzk_vk_set_public_key": (_I, [_U64, _P]),
     "uzk_verify_fold": (_I, [_U64, _P, _P, ctypes.c_uint32, _P, _P, _P, _P, _P]),
+    "uzk_g16_vk_create": (_I, [_P, ctypes.POINTER(_U64)]),
+    "uzk_g16_vk_release": (_I, [_U64]),
+    "uzk_g16_vk_info": (_I, [_U64, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(_I)]),
+    "uzk_g16_verify_fold": (_I, [_U64, _P, _P, ctypes.c_uint32, _P, _P, _P, _P, _P, _P, _P]),
     "uzk_synth_points_arith": (_I, [_P, _SZ, _P]),
     "uzk_synth_points_random": (_I, [_P, _SZ, _U64]),
     "uzk_synth_scalars": (_I, [_P, _SZ, _U64]),
@@ -261,6 +265,20 @@ class G16KeyDesc(ctypes.Structure):
         ("a_query", ctypes.c_void_p), ("b_g1_query", ctypes.c_void_p), ("l_query", ctypes.c_void_p), ("h_query", ctypes.c_void_p),
         ("b_g2_query", ctypes.c_void_p),
         ("row_ptr", ctypes.c_void_p * 3), ("col", ctypes.c_void_p * 3), ("val", ctypes.c_void_p * 3),
+    ]
+
+
+G16_VERIFY_MAX_BATCH = 4096
+G16_VERIFY_MAX_INPUTS = 1024
+G16_PROOF_BYTES = 256
+
+
+class G16VkDesc(ctypes.Structure):
+    """uzk_g16_vk_desc (include/uzkge_gpu.h)."""
+    _fields_ = [
+        ("n_inputs", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
+        ("alpha_g1", _G1), ("beta_g2", _G2), ("gamma_g2", _G2), ("delta_g2", _G2),
+        ("gamma_abc_g1", ctypes.c_void_p),
     ]
 
 

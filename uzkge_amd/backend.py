@@ -1026,6 +1026,54 @@ class VerifierKey:
             self.handle = 0
 
 
+class Groth16VerifierKey:
+    """A Groth16 verifying key resident on the device (uzk_g16_vk_create).  alpha_g1: a wire row of 8 words, the G2 points rows of 16,
+    gamma_abc_g1 [l, 8] ((0, 0) = infinity).  The G2 points are the caller's side of the pairing; they are kept here as given."""
+
+    def __init__(self, alpha_g1, beta_g2, gamma_g2, delta_g2, gamma_abc_g1):
+        ic = np.ascontiguousarray(gamma_abc_g1, dtype=np.uint64).reshape(-1, 8)
+        d = N.G16VkDesc()
+        d.n_inputs = ic.shape[0]
+        for name, val, words in (("alpha_g1", alpha_g1, 8), ("beta_g2", beta_g2, 16), ("gamma_g2", gamma_g2, 16), ("delta_g2", delta_g2, 16)):
+            v = np.ascontiguousarray(val, dtype=np.uint64).reshape(words)
+            dst = getattr(d, name)
+            for w in range(words):
+                dst[w] = int(v[w])
+        d.gamma_abc_g1 = ic.ctypes.data if ic.shape[0] else None
+        h = ctypes.c_uint64(0)
+        check(lib.uzk_g16_vk_create(ctypes.byref(d), ctypes.byref(h)))
+        self.handle = h.value
+        self.beta_g2, self.gamma_g2, self.delta_g2 = (np.array(v, dtype=np.uint64).reshape(16) for v in (beta_g2, gamma_g2, delta_g2))
+        self.n_inputs, self.device = self.info()
+
+    def info(self):
+        """(l, the constant one included; device)."""
+        a, dv = ctypes.c_uint32(0), ctypes.c_int(0)
+        check(lib.uzk_g16_vk_info(self.handle, ctypes.byref(a), ctypes.byref(dv)))
+        return a.value, dv.value
+
+    def fold(self, proofs, publics, weights=None):
+        """uzk_g16_verify_fold: proofs = m blobs of 256 bytes (bytes, or a uint8 array), publics [m, l - 1, 4], weights [m, 4] or None
+        (m == 1 only).  Returns (a [m, 8], b [m, 16], alpha [12], x [12], c [12], status [m])."""
+        raw = np.frombuffer(bytes(proofs), dtype=np.uint8) if isinstance(proofs, (bytes, bytearray)) else np.ascontiguousarray(proofs, dtype=np.uint8)
+        assert raw.size % N.G16_PROOF_BYTES == 0, "proofs: a whole number of %d-byte blobs" % N.G16_PROOF_BYTES
+        m = raw.size // N.G16_PROOF_BYTES
+        pub = np.ascontiguousarray(publics, dtype=np.uint64).reshape(m, self.n_inputs - 1, 4)
+        w = None if weights is None else np.ascontiguousarray(weights, dtype=np.uint64).reshape(m, 4)
+        a, b = np.zeros((max(m, 1), 8), dtype=np.uint64), np.zeros((max(m, 1), 16), dtype=np.uint64)
+        alpha, x, c = (np.zeros(12, dtype=np.uint64) for _ in range(3))
+        status = np.zeros(max(m, 1), dtype=np.uint8)
+        vp = lambda arr: arr.ctypes.data_as(ctypes.c_void_p)
+        check(lib.uzk_g16_verify_fold(self.handle, vp(raw), vp(pub), m, None if w is None else _ptr(w), _ptr(a), _ptr(b), _ptr(alpha), _ptr(x), _ptr(c),
+                                      vp(status)))
+        return a[:m], b[:m], alpha, x, c, status[:m]
+
+    def release(self) -> None:
+        if self.handle:
+            check(lib.uzk_g16_vk_release(self.handle))
+            self.handle = 0
+
+
 def keccak256_device(messages) -> list:
     """uzk_test_keccak256 (test hook): the digests of the messages by the device's transcript sponge."""
     offs = np.zeros(len(messages) + 1, dtype=np.uint64)

@@ -228,6 +228,7 @@ static void ctx_release(Ctx& c) {
     g2_free(c);
     g16_free(c);
     c.verify_ws.release();
+    c.g16v_ws.release();
     msm_free(c);
     poly_free(c);
     c.ntt_scratch[0].release(); c.ntt_scratch[1].release(); c.ntt_io.release(); c.msm_scalars.release();
@@ -318,6 +319,7 @@ int uzk_shutdown(void) try {
     vf_release_all();                      // verifier keys
     g2_release_all();                      // G2 bases
     g16_release_all();                     // Groth16 proving keys
+    g16v_release_all();                    // Groth16 verifying keys
     std::lock_guard<std::mutex> lk(s.mu);
     if (!s.bound) return UZK_OK;
     ctx_release(default_ctx());
@@ -1338,6 +1340,46 @@ int uzk_verify_fold(uint64_t vk, const uint8_t* proofs, const uint64_t* pi_mont,
     std::memcpy(right_out, &r, sizeof r);
     return UZK_OK;
 } catch (...) { return uzk::on_exception("uzk_verify_fold"); }
+
+/* ---- batch Groth16 verification ------------------------------------------------------------ */
+int uzk_g16_vk_create(const uzk_g16_vk_desc* desc, uint64_t* vk_out) try {
+    API_LOCK;
+    if (!desc || !vk_out) { set_error("uzk_g16_vk_create: null pointer"); return UZK_ERR_PARAMETER; }
+    UZK_TRY(g16v_key_check(desc));
+    UZK_TRY(require_ready());
+    return g16v_key_create(ctx(), desc, vk_out);
+} catch (...) { return uzk::on_exception("uzk_g16_vk_create"); }
+
+int uzk_g16_vk_release(uint64_t vk) try {
+    API_LOCK;
+    return g16v_key_release(vk);
+} catch (...) { return uzk::on_exception("uzk_g16_vk_release"); }
+
+int uzk_g16_vk_info(uint64_t vk, uint32_t* n_inputs_out, int* device_out) try {
+    if (!g16v_key_known(vk, n_inputs_out, device_out)) { set_error("uzk_g16_vk_info: unknown verifying key %llu", (unsigned long long)vk); return UZK_ERR_PARAMETER; }
+    return UZK_OK;
+} catch (...) { return uzk::on_exception("uzk_g16_vk_info"); }
+
+int uzk_g16_verify_fold(uint64_t vk, const uint8_t* proofs, const uint64_t* public_mont, uint32_t m, const uint64_t* weights_mont, uzk_g1_affine* a_out,
+                        uzk_g2_affine* b_out, uzk_g1_jac* alpha_out, uzk_g1_jac* x_out, uzk_g1_jac* c_out, uint8_t* status_out) try {
+    API_LOCK;
+    if (m > UZK_G16_VERIFY_MAX_BATCH) { set_error("uzk_g16_verify_fold: %u proofs (at most %d per call)", m, UZK_G16_VERIFY_MAX_BATCH); return UZK_ERR_PARAMETER; }
+    if (m > 1 && !weights_mont) { set_error("uzk_g16_verify_fold: %u proofs need a weight each (unweighted sums let errors cancel)", m); return UZK_ERR_PARAMETER; }
+    if (!alpha_out || !x_out || !c_out || (m > 0 && (!proofs || !a_out || !b_out || !status_out))) { set_error("uzk_g16_verify_fold: null pointer"); return UZK_ERR_PARAMETER; }
+    uint32_t n_inputs = 0;
+    if (!g16v_key_known(vk, &n_inputs, nullptr)) { set_error("uzk_g16_verify_fold: unknown verifying key %llu", (unsigned long long)vk); return UZK_ERR_PARAMETER; }
+    if (m > 0 && n_inputs > 1 && !public_mont) { set_error("uzk_g16_verify_fold: null public inputs"); return UZK_ERR_PARAMETER; }
+    Jac al = jac_inf(), x = jac_inf(), cc = jac_inf();
+    if (m > 0) {
+        UZK_TRY(require_ready());
+        UZK_TRY(g16v_fold_run(ctx(), vk, proofs, as_fp(public_mont), m, weights_mont ? as_fp(weights_mont) : nullptr, reinterpret_cast<Affine*>(a_out),
+                              reinterpret_cast<G2Affine*>(b_out), &al, &x, &cc, status_out));
+    }
+    std::memcpy(alpha_out, &al, sizeof al);
+    std::memcpy(x_out, &x, sizeof x);
+    std::memcpy(c_out, &cc, sizeof cc);
+    return UZK_OK;
+} catch (...) { return uzk::on_exception("uzk_g16_verify_fold"); }
 
 int uzk_test_keccak256(const uint8_t* msgs, const uint64_t* offsets, uint32_t count, uint8_t* digests_out) try {
     API_LOCK;

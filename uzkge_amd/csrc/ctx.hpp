@@ -146,6 +146,8 @@ struct Ctx {
     void* g2 = nullptr;
     // groth16.hip: the workspaces of the Groth16 prover (G16Work*, grow-only)
     void* g16 = nullptr;
+    // g16verify.hip: one block carved into the arrays of a Groth16 fold (proofs, public inputs, weights, decoded points, results)
+    DevBuf g16v_ws;
     int tune_verify_transcript = 0;   // which transcript kernel a fold runs: 1 one proof per lane; 0 / 2 a proof's state spread over a half wave (the default)
     // an entry of the process-wide SRS registry
     struct Srs {
@@ -279,6 +281,14 @@ void g16_release_all();
 void g16_free(Ctx& c);
 int g16_h_run(Ctx& c, uint64_t h, const Fp* d_z, uint32_t batch, Fp* d_h);
 int g16_prove_run(Ctx& c, uint64_t h, const Fp* z, bool z_on_device, const Fp* r_host, const Fp* s_host, uint32_t batch, uzk_g16_proof* out);
+// g16verify.hip: Groth16 verifying keys (process-wide handles) and the fold of a batch of proofs
+int g16v_key_check(const uzk_g16_vk_desc* d);
+int g16v_key_create(Ctx& c, const uzk_g16_vk_desc* d, uint64_t* out);
+bool g16v_key_known(uint64_t h, uint32_t* n_inputs, int* device);
+int g16v_key_release(uint64_t h);
+void g16v_release_all();
+int g16v_fold_run(Ctx& c, uint64_t h, const uint8_t* proofs, const Fp* pub, uint32_t m, const Fp* weights, Affine* a_out, G2Affine* b_out,
+                  Jac* alpha_out, Jac* x_out, Jac* c_out, uint8_t* status_out);
 void msm_plan_info(Ctx& c, size_t n, int* window_bits, int* windows);
 int msm_run(Ctx& c, const Affine* points, const ScalarView& scalars, size_t n, uint32_t batch, Jac* out_host, int pre_c,
             uint32_t pre_stride, uint32_t pre_off);

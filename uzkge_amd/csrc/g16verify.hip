@@ -1,0 +1,356 @@
+// Batch Groth16 verification up to the pairing: M proofs under one verifying key are folded, under the caller's weights rho_i, into
+// the G1 arguments of ONE product of M + 3 Miller loops
+//     prod_i e(rho_i A_i, B_i) . e(-(sum rho) alpha, beta) . e(-sum rho_i X_i, gamma) . e(-sum rho_i C_i, delta) = 1,
+//     sum rho_i X_i = (sum rho) IC_0 + sum_j (sum_i rho_i x_ij) IC_j
+// (Groth16Verifier.sol verifyProof, one proof at a time, is the reference; tests/g16_verify_ref.py is the restatement on Python
+// integers).  Everything per proof runs on the device; the library computes no pairing.
+//
+//   g16v_decode     one lane per proof: eight big-endian words (EVM order a.x a.y b.x.c1 b.x.c0 b.y.c1 b.y.c0 c.x c.y) compared with p,
+//                   into Montgomery form; the curve equation of A and C in Fq, of B in Fq2 on the lazy limbs (fq2_29.hpp)
+//   g16v_subgroup   one lane per proof: [r] B by double-and-add over g2_29.hpp's G2P (the bits of r are the same for every lane, so
+//                   a wave runs one control flow); then the masked weight of the proof (0 unless its status is 0)
+//   g16v_reduce     one workgroup per public input: t_0 = sum rho_i, t_j = sum_i rho_i x_ij over the batch in Fr (no atomics)
+//   g16v_amul       one lane per item: rho_i A_i for the M proofs and t_0 alpha as item M, double-and-add over the full 254 bits of the
+//                   scalar, then the affine map with the inversion in the same lane
+//   two MSMs        X over the key's l resident points, C over the M fresh points, through msm_run (what the PlonK fold uses)
+//
+// The two chains are one lane per item.  A G2P addition keeps four Fq2 coordinates of both operands and a dozen products alive: spread
+// over a quad (ecquad29.hpp's arrangement) it would need that header's cross-lane selects rewritten for pairs of limbs vectors, and
+// the chain would still be 254 doublings long -- the latency of a fold is the chain length, not the lane count (52 proofs are one
+// wave either way).  The shorter chain is an endomorphism criterion for B (a 127-bit multiplication); see DESIGN.md.
+#include <cstring>
+#include <map>
+#include <mutex>
+#include <vector>
+
+#include "ctx.hpp"
+#include "g2_29.hpp"
+#include "host_math.hpp"
+
+namespace uzk {
+
+constexpr uint32_t kGvBlock = 64;
+constexpr uint32_t kGvWords = 8;
+static_assert(kGvWords * 32 == UZK_G16_PROOF_BYTES, "a blob is eight 32-byte words");
+enum { GV_OK = 0, GV_NOT_CANONICAL = 1, GV_OFF_CURVE = 2, GV_NOT_IN_SUBGROUP = 3 };
+
+template <class C>
+UZK_HD bool gv_below_modulus(const Fp& a) {
+    uint64_t br = 0;
+    for (int i = 0; i < 8; ++i) { const uint64_t t = (uint64_t)a.v[i] - C::M[i] - br; br = (t >> 32) & 1; }
+    return br != 0;
+}
+
+UZK_HD bool gv_g1_on_curve(const Affine& p) {
+    const Fp one = Fq::one();
+    const Fp three = Fq::add(Fq::add(one, one), one);
+    return Fq::eq(Fq::sqr(p.y), Fq::add(Fq::mul(Fq::sqr(p.x), p.x), three));
+}
+
+#if defined(__HIP_DEVICE_COMPILE__)
+// the twist's constant 3 / (9 + u) = (27 / 82, -3 / 82), canonical words
+__device__ __forceinline__ Fq2w gv_twist_b() {
+    Fq2w b;
+    const uint32_t c0[8] = {0x24a138e5u, 0x3267e6dcu, 0x59dbefa3u, 0xb5b4c5e5u, 0x1be06ac3u, 0x81be1899u, 0xceb8aaaeu, 0x2b149d40u};
+    const uint32_t c1[8] = {0x85c315d2u, 0xe4a2bd06u, 0xe52d1852u, 0xa74fa084u, 0xeed8fdf4u, 0xcd2cafadu, 0x3af0fed4u, 0x009713b0u};
+    Fp a0, a1;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) { a0.v[i] = c0[i]; a1.v[i] = c1[i]; }
+    b.c0 = Fq::to_mont(a0); b.c1 = Fq::to_mont(a1);
+    return b;
+}
+__device__ __forceinline__ bool gv_g2_on_twist(const G2Affine& p) {
+    using namespace q2;
+    const auto X = ldr(p.x), Y = ldr(p.y);
+    const auto rhs = add(mul(sqr(X), X), ldr(gv_twist_b()));
+    return is_zero(sub(sqr(Y), rhs));
+}
+#endif
+
+// ---- decode and check -----------------------------------------------------------------------------------------------------------
+// A proof with a nonzero status leaves infinities in the three point arrays.  The twist has r (2 p - r) points, an odd number, so no
+// point of it has order two: y = 0 with x != 0 fails the curve equation, and G2P's affine form (y = 0 <=> infinity) loses nothing.
+__global__ __launch_bounds__(kGvBlock) void g16v_decode_kernel(const uint8_t* __restrict__ proofs, Affine* __restrict__ pa, G2Affine* __restrict__ pb,
+                                                                Affine* __restrict__ pc, uint8_t* __restrict__ status, uint32_t m) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    const uint32_t i = blockIdx.x * kGvBlock + threadIdx.x;
+    if (i >= m) return;
+    const uint32_t* src = reinterpret_cast<const uint32_t*>(proofs + (size_t)i * UZK_G16_PROOF_BYTES);
+    Fp w[kGvWords];
+    bool canonical = true;
+#pragma unroll
+    for (uint32_t t = 0; t < kGvWords; ++t) {                     // unrolled: w stays in registers
+        Fp v;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v.v[j] = __builtin_bswap32(src[8 * t + 7 - j]);
+        canonical = canonical && gv_below_modulus<FqCfg>(v);
+        w[t] = Fq::to_mont(v);
+    }
+    Affine a, c;
+    G2Affine b;
+    a.x = w[0]; a.y = w[1];
+    b.x.c1 = w[2]; b.x.c0 = w[3]; b.y.c1 = w[4]; b.y.c0 = w[5];
+    c.x = w[6]; c.y = w[7];
+    uint32_t st = GV_OK;
+    if (!canonical) st = GV_NOT_CANONICAL;
+    else {
+        const bool b_inf = fq2w_is_zero(b.x) && fq2w_is_zero(b.y);
+        if (!affine_is_inf(a) && !gv_g1_on_curve(a)) st = GV_OFF_CURVE;
+        else if (!affine_is_inf(c) && !gv_g1_on_curve(c)) st = GV_OFF_CURVE;
+        else if (!b_inf && !gv_g2_on_twist(b)) st = GV_OFF_CURVE;
+    }
+    if (st != GV_OK) {
+        a.x = Fq::zero(); a.y = a.x; c = a;
+        b.x = fq2w_zero(); b.y = b.x;
+    }
+    pa[i] = a; pb[i] = b; pc[i] = c;
+    status[i] = (uint8_t)st;
+#endif
+}
+
+// ---- [r] B = O, and the masked weights --------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kGvBlock) void g16v_subgroup_kernel(Affine* __restrict__ pa, G2Affine* __restrict__ pb, Affine* __restrict__ pc,
+                                                                  const Fp* __restrict__ rho, uint8_t* __restrict__ status, Fp* __restrict__ wm, uint32_t m) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    const uint32_t i = blockIdx.x * kGvBlock + threadIdx.x;
+    if (i >= m) return;                                            // no barrier and no cross-lane move below
+    uint32_t st = status[i];
+    if (st == GV_OK) {
+        const G2P base = g2p_from_affine(pb[i]);
+        if (!base.inf) {
+            G2P acc = g2p_inf();
+#pragma unroll 1
+            for (int k = 253; k >= 0; --k) {
+                g2p_dbl(acc);
+                if ((FrCfg::M[k >> 5] >> (k & 31)) & 1) g2p_add(acc, base);
+            }
+            if (!acc.inf) st = GV_NOT_IN_SUBGROUP;
+        }
+        if (st != GV_OK) {
+            Affine z;
+            z.x = Fq::zero(); z.y = z.x;
+            G2Affine z2;
+            z2.x = fq2w_zero(); z2.y = z2.x;
+            pa[i] = z; pc[i] = z; pb[i] = z2;
+            status[i] = (uint8_t)st;
+        }
+    }
+    wm[i] = st == GV_OK ? rho[i] : Fr::zero();
+#endif
+}
+
+// t[0] = sum_i wm_i, t[j] = sum_i wm_i x_i(j-1): one workgroup per j
+__global__ __launch_bounds__(256) void g16v_reduce_kernel(const Fp* __restrict__ wm, const Fp* __restrict__ pub, uint32_t m, uint32_t n_pub,
+                                                           Fp* __restrict__ t) {
+    __shared__ Fp part[256];
+    const uint32_t j = blockIdx.x, th = threadIdx.x;
+    Fp acc = Fr::zero();
+    for (uint32_t i = th; i < m; i += 256) acc = Fr::add(acc, j == 0 ? wm[i] : Fr::mul(wm[i], pub[(size_t)i * n_pub + j - 1]));
+    part[th] = acc;
+    __syncthreads();
+    for (uint32_t step = 128; step > 0; step >>= 1) {
+        if (th < step) part[th] = Fr::add(part[th], part[th + step]);
+        __syncthreads();
+    }
+    if (th == 0) t[j] = part[0];
+}
+
+// ---- rho_i A_i and t_0 alpha as canonical affine points ------------------------------------------------------------------------------
+__device__ inline Fp gv_fq_inv(const Fp& a) {                     // a^(p - 2)
+    Fp e = Fq::modulus();
+    e.v[0] -= 2;                                                   // the low word of p ends in ...fd47
+    Fp acc = Fq::one();
+#pragma unroll 1
+    for (int i = 253; i >= 0; --i) {
+        acc = Fq::sqr(acc);
+        if ((e.v[i >> 5] >> (i & 31)) & 1) acc = Fq::mul(acc, a);
+    }
+    return acc;
+}
+
+__global__ __launch_bounds__(kGvBlock) void g16v_amul_kernel(const Affine* __restrict__ pa, const Fp* __restrict__ wm, const Fp* __restrict__ t, Affine alpha,
+                                                              Affine* __restrict__ out, uint32_t m) {
+    const uint32_t i = blockIdx.x * kGvBlock + threadIdx.x;
+    if (i > m) return;
+    const Affine p = i < m ? pa[i] : alpha;
+    const Fp s = Fr::from_mont(i < m ? wm[i] : t[0]);              // canonical: below r < 2^254
+    XYZZ acc = xyzz_inf();
+#pragma unroll 1
+    for (int k = 253; k >= 0; --k) {
+        acc = xyzz_dbl(acc);
+        if ((s.v[k >> 5] >> (k & 31)) & 1) xyzz_madd(acc, p, false);
+    }
+    Affine r;
+    r.x = Fq::zero(); r.y = r.x;
+    if (!xyzz_is_inf(acc)) {
+        const Fp inv = gv_fq_inv(Fq::mul(acc.zz, acc.zzz));
+        r.x = Fq::mul(acc.x, Fq::mul(inv, acc.zzz));               // X / ZZ
+        r.y = Fq::mul(acc.y, Fq::mul(inv, acc.zz));                // Y / ZZZ
+    }
+    out[i] = r;
+}
+
+// ---- keys ---------------------------------------------------------------------------------------------------------------------
+struct GvEntry {
+    int device = 0;
+    uint32_t n_inputs = 0;
+    Affine alpha;
+    Affine* d_ic = nullptr;        // gamma_abc_g1: n_inputs points
+};
+static std::mutex g_gv_mu;
+static std::map<uint64_t, GvEntry> g_gv;
+static uint64_t g_gv_next = 1;
+constexpr uint64_t kGvTag = 6ull << 59;
+
+static bool gv_lookup(uint64_t h, GvEntry* out) {
+    std::lock_guard<std::mutex> lk(g_gv_mu);
+    auto it = g_gv.find(h);
+    if (it == g_gv.end()) return false;
+    *out = it->second;
+    return true;
+}
+// frees the key's device memory; the calling thread's current device is left as it was
+static void gv_free(const GvEntry& e) {
+    int prev = -1;
+    (void)hipGetDevice(&prev);
+    (void)hipSetDevice(e.device);
+    if (e.d_ic) (void)hipFree(e.d_ic);
+    if (prev >= 0) (void)hipSetDevice(prev);
+}
+
+int g16v_key_check(const uzk_g16_vk_desc* d) {
+    if (d->n_inputs < 1 || d->n_inputs > UZK_G16_VERIFY_MAX_INPUTS) {
+        set_error("uzk_g16_vk_create: %u inputs (the constant one included: 1 .. %d)", d->n_inputs, UZK_G16_VERIFY_MAX_INPUTS);
+        return UZK_ERR_PARAMETER;
+    }
+    if (!d->gamma_abc_g1) { set_error("uzk_g16_vk_create: gamma_abc_g1 is null"); return UZK_ERR_PARAMETER; }
+    return UZK_OK;
+}
+
+int g16v_key_create(Ctx& c, const uzk_g16_vk_desc* d, uint64_t* out) {
+    GvEntry e;
+    e.device = c.device; e.n_inputs = d->n_inputs;
+    std::memcpy(&e.alpha, &d->alpha_g1, sizeof e.alpha);
+    const size_t bytes = (size_t)d->n_inputs * sizeof(Affine);
+    hipError_t err = hipMalloc(reinterpret_cast<void**>(&e.d_ic), bytes);
+    if (err == hipSuccess) err = hipMemcpyAsync(e.d_ic, d->gamma_abc_g1, bytes, hipMemcpyHostToDevice, c.stream);
+    if (err == hipSuccess) err = hipStreamSynchronize(c.stream);  // the caller's array may go away
+    if (err != hipSuccess) {
+        (void)hipGetLastError();
+        gv_free(e);
+        set_error("uzk_g16_vk_create: %s", hipGetErrorString(err));
+        return UZK_ERR_DEVICE;
+    }
+    std::lock_guard<std::mutex> lk(g_gv_mu);
+    const uint64_t h = kGvTag | g_gv_next++;
+    g_gv[h] = e;
+    *out = h;
+    return UZK_OK;
+}
+
+bool g16v_key_known(uint64_t h, uint32_t* n_inputs, int* device) {
+    GvEntry e;
+    if (!gv_lookup(h, &e)) return false;
+    if (n_inputs) *n_inputs = e.n_inputs;
+    if (device) *device = e.device;
+    return true;
+}
+
+// The caller makes sure no fold over this key is still running.
+int g16v_key_release(uint64_t h) {
+    GvEntry e;
+    {
+        std::lock_guard<std::mutex> lk(g_gv_mu);
+        auto it = g_gv.find(h);
+        if (it == g_gv.end()) { set_error("uzk_g16_vk_release: unknown verifying key %llu", (unsigned long long)h); return UZK_ERR_PARAMETER; }
+        e = it->second;
+        g_gv.erase(it);
+    }
+    gv_free(e);
+    return UZK_OK;
+}
+
+void g16v_release_all() {
+    std::lock_guard<std::mutex> lk(g_gv_mu);
+    for (auto& kv : g_gv) gv_free(kv.second);
+    g_gv.clear();
+}
+
+// ---- the fold -----------------------------------------------------------------------------------------------------------------
+static size_t gv_align(size_t v) { return (v + 255) & ~(size_t)255; }
+
+// m >= 1.  a_out, b_out: m points each; alpha_out, x_out, c_out: one Jacobian point each.
+int g16v_fold_run(Ctx& c, uint64_t h, const uint8_t* proofs, const Fp* pub, uint32_t m, const Fp* weights, Affine* a_out, G2Affine* b_out,
+                  Jac* alpha_out, Jac* x_out, Jac* c_out, uint8_t* status_out) {
+    GvEntry e;
+    if (!gv_lookup(h, &e)) { set_error("uzk_g16_verify_fold: unknown verifying key %llu", (unsigned long long)h); return UZK_ERR_PARAMETER; }
+    if (e.device != c.device) { set_error("uzk_g16_verify_fold: the key lives on device %d, the calling context on device %d", e.device, c.device); return UZK_ERR_PARAMETER; }
+    const uint32_t n_pub = e.n_inputs - 1;
+    size_t at = 0;
+    auto carve = [&](size_t bytes) { const size_t o = at; at += gv_align(bytes); return o; };
+    const size_t o_proofs = carve((size_t)m * UZK_G16_PROOF_BYTES), o_pub = carve((size_t)m * n_pub * sizeof(Fp)), o_rho = carve((size_t)m * sizeof(Fp)),
+                 o_wm = carve((size_t)m * sizeof(Fp)), o_status = carve(m), o_a = carve((size_t)m * sizeof(Affine)),
+                 o_b = carve((size_t)m * sizeof(G2Affine)), o_c = carve((size_t)m * sizeof(Affine)), o_t = carve((size_t)e.n_inputs * sizeof(Fp)),
+                 o_ra = carve(((size_t)m + 1) * sizeof(Affine));
+    UZK_TRY(c.g16v_ws.reserve(at));
+    char* ws = c.g16v_ws.as<char>();
+    uint8_t* d_proofs = reinterpret_cast<uint8_t*>(ws + o_proofs);
+    Fp* d_pub = reinterpret_cast<Fp*>(ws + o_pub);
+    Fp* d_rho = reinterpret_cast<Fp*>(ws + o_rho);
+    Fp* d_wm = reinterpret_cast<Fp*>(ws + o_wm);
+    uint8_t* d_status = reinterpret_cast<uint8_t*>(ws + o_status);
+    Affine* d_a = reinterpret_cast<Affine*>(ws + o_a);
+    G2Affine* d_b = reinterpret_cast<G2Affine*>(ws + o_b);
+    Affine* d_c = reinterpret_cast<Affine*>(ws + o_c);
+    Fp* d_t = reinterpret_cast<Fp*>(ws + o_t);
+    Affine* d_ra = reinterpret_cast<Affine*>(ws + o_ra);
+    const Fp one = Fr::one();
+    UZK_HIP(hipMemcpyAsync(d_proofs, proofs, (size_t)m * UZK_G16_PROOF_BYTES, hipMemcpyHostToDevice, c.stream));
+    if (n_pub) UZK_HIP(hipMemcpyAsync(d_pub, pub, (size_t)m * n_pub * sizeof(Fp), hipMemcpyHostToDevice, c.stream));
+    UZK_HIP(hipMemcpyAsync(d_rho, weights ? weights : &one, (size_t)m * sizeof(Fp), hipMemcpyHostToDevice, c.stream));
+    const unsigned grid = (m + kGvBlock - 1) / kGvBlock;
+    {
+        KernelScope ks(c, "g16v_decode");
+        hipLaunchKernelGGL(g16v_decode_kernel, dim3(grid), dim3(kGvBlock), 0, c.stream, d_proofs, d_a, d_b, d_c, d_status, m);
+    }
+    UZK_HIP(hipGetLastError());
+    {
+        KernelScope ks(c, "g16v_subgroup");
+        hipLaunchKernelGGL(g16v_subgroup_kernel, dim3(grid), dim3(kGvBlock), 0, c.stream, d_a, d_b, d_c, d_rho, d_status, d_wm, m);
+    }
+    UZK_HIP(hipGetLastError());
+    {
+        KernelScope ks(c, "g16v_reduce");
+        hipLaunchKernelGGL(g16v_reduce_kernel, dim3(e.n_inputs), dim3(256), 0, c.stream, d_wm, d_pub, m, n_pub, d_t);
+    }
+    UZK_HIP(hipGetLastError());
+    {
+        KernelScope ks(c, "g16v_amul");
+        hipLaunchKernelGGL(g16v_amul_kernel, dim3((m + 1 + kGvBlock - 1) / kGvBlock), dim3(kGvBlock), 0, c.stream, d_a, d_wm, d_t, e.alpha, d_ra, m);
+    }
+    UZK_HIP(hipGetLastError());
+    Affine alpha_w;                                                // t_0 alpha, read after the last synchronisation
+    UZK_HIP(hipMemcpyAsync(status_out, d_status, m, hipMemcpyDeviceToHost, c.stream));
+    UZK_HIP(hipMemcpyAsync(a_out, d_ra, (size_t)m * sizeof(Affine), hipMemcpyDeviceToHost, c.stream));
+    UZK_HIP(hipMemcpyAsync(&alpha_w, d_ra + m, sizeof(Affine), hipMemcpyDeviceToHost, c.stream));
+    UZK_HIP(hipMemcpyAsync(b_out, d_b, (size_t)m * sizeof(G2Affine), hipMemcpyDeviceToHost, c.stream));
+    if (c.prof_on) UZK_HIP(hipStreamSynchronize(c.stream));        // so that the two host sections below time the MSMs alone
+    int rc;
+    {
+        HostScope hs(c, "host_g16v_msm_x");
+        rc = msm_run(c, e.d_ic, ScalarView::dense(d_t, e.n_inputs), e.n_inputs, 1, x_out, 0, 0, 0);
+    }
+    if (rc == UZK_OK) {
+        HostScope hs(c, "host_g16v_msm_c");
+        rc = msm_run(c, d_c, ScalarView::dense(d_wm, m), m, 1, c_out, 0, 0, 0);
+    }
+    // also on failure: the copies into the caller's arrays are queued on this stream and must not outlive the call
+    const hipError_t se = hipStreamSynchronize(c.stream);
+    UZK_TRY(rc);
+    UZK_HIP(se);
+    if (affine_is_inf(alpha_w)) *alpha_out = jac_inf();
+    else { alpha_out->x = alpha_w.x; alpha_out->y = alpha_w.y; alpha_out->z = Fq::one(); }
+    return UZK_OK;
+}
+
+}  // namespace uzk

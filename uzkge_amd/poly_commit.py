@@ -488,6 +488,137 @@ class PlonkVerifierKey:
         self.key.release()
 
 
+# ---- Groth16 verifying keys ----------------------------------------------------------------------------------------------------
+_P = FQ_MODULUS
+_TWIST_B = (27 * pow(82, _P - 2, _P) % _P, (-3 * pow(82, _P - 2, _P)) % _P)       # 3 / (9 + u)
+
+
+def _fq_sqrt(a: int):
+    r = pow(a, (_P + 1) // 4, _P)                                                   # p = 3 mod 4
+    return r if r * r % _P == a % _P else None
+
+
+def _fq2_mul(a, b):
+    return ((a[0] * b[0] - a[1] * b[1]) % _P, (a[0] * b[1] + a[1] * b[0]) % _P)
+
+
+def _fq2_sqrt(a):
+    """by the norm: with n = sqrt(a0^2 + a1^2), x0^2 = (a0 +- n) / 2 and x1 = a1 / (2 x0)"""
+    if a[1] == 0:
+        r = _fq_sqrt(a[0])
+        if r is not None:
+            return (r, 0)
+        r = _fq_sqrt((-a[0]) % _P)
+        return None if r is None else (0, r)
+    n = _fq_sqrt((a[0] * a[0] + a[1] * a[1]) % _P)
+    if n is None:
+        return None
+    for s in (n, _P - n):
+        x0 = _fq_sqrt((a[0] + s) * ((_P + 1) // 2) % _P)
+        if x0:
+            x = (x0, a[1] * pow(2 * x0, _P - 2, _P) % _P)
+            if _fq2_mul(x, x) == (a[0] % _P, a[1] % _P):
+                return x
+    return None
+
+
+def _g1_decompress(b: bytes):
+    """ark-serialize, compressed: x little-endian, bit 7 of the last byte = the larger y, bit 6 = infinity"""
+    flags = b[31]
+    if flags & 0x40:
+        return None
+    x = int.from_bytes(b[:31] + bytes([flags & 0x3f]), "little")
+    y = _fq_sqrt((x * x * x + 3) % _P)
+    if x >= _P or y is None:
+        raise UzkgeError(N.UZK_ERR_PARAMETER, "Groth16VerifierKey: a compressed G1 point is not on the curve")
+    return (x, _P - y) if (y > _P - y) != bool(flags & 0x80) else (x, y)
+
+
+def _g2_decompress(b: bytes):
+    flags = b[63]
+    if flags & 0x40:
+        return None
+    x = (int.from_bytes(b[:32], "little"), int.from_bytes(b[32:63] + bytes([flags & 0x3f]), "little"))
+    x3 = _fq2_mul(_fq2_mul(x, x), x)
+    y = _fq2_sqrt(((x3[0] + _TWIST_B[0]) % _P, (x3[1] + _TWIST_B[1]) % _P)) if max(x) < _P else None
+    if y is None:
+        raise UzkgeError(N.UZK_ERR_PARAMETER, "Groth16VerifierKey: a compressed G2 point is not on the twist")
+    ny = ((-y[0]) % _P, (-y[1]) % _P)
+    return (x, ny) if ((y[1], y[0]) > (ny[1], ny[0])) != bool(flags & 0x80) else (x, y)       # ark-ff orders Fq2 by c1, then c0
+
+
+def g2_wire(point) -> np.ndarray:
+    """x.c0, x.c1, y.c0, y.c1 as Montgomery words [16]; None = infinity = zeros"""
+    if point is None:
+        return np.zeros(16, dtype=np.uint64)
+    (x0, x1), (y0, y1) = point
+    return np.concatenate([fq_from_int(int(v)) for v in (x0, x1, y0, y1)])
+
+
+def g16_proof_blob(a, b, c) -> bytes:
+    """The 256-byte blob of a proof: a.x, a.y, b.x.c1, b.x.c0, b.y.c1, b.y.c0, c.x, c.y as 32-byte big-endian words (the EVM order of
+    the reference's contract); None = infinity = zeros."""
+    a, c = a or (0, 0), c or (0, 0)
+    (bx0, bx1), (by0, by1) = b or ((0, 0), (0, 0))
+    return b"".join(int(v).to_bytes(32, "big") for v in (a[0], a[1], bx1, bx0, by1, by0, c[0], c[1]))
+
+
+class Groth16VerifierKey:
+    """A Groth16 verifying key resident on the device, for batches of proofs: `fold` runs everything in front of the pairings for m
+    proofs at once and returns the G1 (and G2) arguments of the ONE product of m + 3 Miller loops
+        prod_i e(rho_i A_i, B_i) . e(-(sum rho) alpha, beta) . e(-sum rho_i X_i, gamma) . e(-sum rho_i C_i, delta) = 1
+    that stands for all of them.  The pairings are the caller's: this library computes none.
+
+    Points are integers: G1 (x, y), G2 ((x0, x1), (y0, y1)), None = infinity."""
+
+    def __init__(self, alpha_g1, beta_g2, gamma_g2, delta_g2, gamma_abc_g1):
+        self.alpha_g1, self.beta_g2, self.gamma_g2, self.delta_g2, self.gamma_abc_g1 = alpha_g1, beta_g2, gamma_g2, delta_g2, list(gamma_abc_g1)
+        ic = np.stack([g1_wire(p) for p in self.gamma_abc_g1]) if self.gamma_abc_g1 else np.zeros((0, 8), dtype=np.uint64)
+        self.key = B.Groth16VerifierKey(g1_wire(alpha_g1), g2_wire(beta_g2), g2_wire(gamma_g2), g2_wire(delta_g2), ic)
+        self.n_inputs = self.key.n_inputs
+
+    @staticmethod
+    def parse_key_bytes(head: bytes):
+        """ark-serialize (compressed) VerifyingKey<Bn254> -- what a ProvingKey file starts with: alpha_g1 | beta_g2 | gamma_g2 |
+        delta_g2 | u64 LE length | gamma_abc_g1.  Returns (alpha_g1, beta_g2, gamma_g2, delta_g2, gamma_abc_g1); bytes behind the key
+        are ignored."""
+        if len(head) < 232:
+            raise UzkgeError(N.UZK_ERR_PARAMETER, "Groth16VerifierKey: %d bytes cannot hold a verifying key" % len(head))
+        alpha = _g1_decompress(head[0:32])
+        beta, gamma, delta = (_g2_decompress(head[32 + 64 * k:96 + 64 * k]) for k in range(3))
+        l = struct.unpack_from("<Q", head, 224)[0]
+        if l < 1 or l > N.G16_VERIFY_MAX_INPUTS or len(head) < 232 + 32 * l:
+            raise UzkgeError(N.UZK_ERR_PARAMETER, "Groth16VerifierKey: gamma_abc_g1 of %d points" % l)
+        return alpha, beta, gamma, delta, [_g1_decompress(head[232 + 32 * j:264 + 32 * j]) for j in range(l)]
+
+    @classmethod
+    def from_key_bytes(cls, head: bytes) -> "Groth16VerifierKey":
+        return cls(*cls.parse_key_bytes(head))
+
+    def fold(self, proofs: Sequence[bytes], publics: Sequence[Sequence[int]], weights: Optional[Sequence[int]] = None):
+        """proofs: m blobs of 256 bytes (g16_proof_blob); publics: m lists of l - 1 integers (the leading one is implied); weights: m
+        integers the CALLER draws after it has the proofs (None only for one proof: weight 1).  Returns (a [m, 8], b [m, 16], alpha
+        [12], x [12], c [12], status [m]): rho_i A_i as affine wire points, B_i, three Jacobian wire points and one byte per proof (0
+        folded, 1 a word >= p, 2 a point off its curve, 3 B outside the subgroup -- such a proof is left out of every sum)."""
+        m = len(proofs)
+        if m != len(publics) or (weights is not None and len(weights) != m) or any(len(p) != N.G16_PROOF_BYTES for p in proofs):
+            raise UzkgeError(N.UZK_ERR_PARAMETER, "Groth16VerifierKey.fold: one 256-byte blob, one list of public inputs and one weight per proof")
+        pub = np.zeros((m, self.n_inputs - 1, 4), dtype=np.uint64)
+        for i, row in enumerate(publics):
+            if len(row) != self.n_inputs - 1:
+                raise UzkgeError(N.UZK_ERR_PARAMETER, "Groth16VerifierKey.fold: %d public inputs per proof" % (self.n_inputs - 1))
+            for j, v in enumerate(row):
+                pub[i, j] = fr_from_int(int(v))
+        w = None if weights is None else np.stack([fr_from_int(int(v)) for v in weights]) if m else np.zeros((0, 4), dtype=np.uint64)
+        return self.key.fold(b"".join(proofs), pub, w)
+
+    def info(self):
+        return self.key.info()
+
+    def release(self) -> None:
+        self.key.release()
+
+
 def hide_polynomial(polynomial: FpPolynomial, blinds: np.ndarray, zeroing_degree: int) -> FpPolynomial:
     """helpers.rs:139-158 with the random blinds given: adds (b_0 + b_1 X + ...) * (X^zeroing_degree - 1)."""
     b = np.ascontiguousarray(blinds, dtype=np.uint64).reshape(-1, 4)
