@@ -738,7 +738,8 @@ int uzk_verify_fold(uint64_t vk, const uint8_t* proofs, const uint64_t* pi_mont,
  *     sum rho_i X_i = (sum rho) IC_0 + sum_j (sum_i rho_i x_ij) IC_j.
  * Everything in front of the pairings runs on the device: decoding and checking the proof bytes, the subgroup check of B, the M
  * scalar multiplications rho_i A_i (normalised to affine), the l dot products in Fr and two MSMs (X over the key's l points, C over
- * the M fresh ones).  The pairings stay with the caller: the library computes no pairing. */
+ * the M fresh ones).  uzk_g16_verify_fold stops there and hands the G1 arguments to the caller; uzk_g16_verify_batch (below) goes on
+ * to the pairing product on the device and returns the verdict. */
 #define UZK_G16_VERIFY_MAX_BATCH 4096
 #define UZK_G16_VERIFY_MAX_INPUTS 1024
 #define UZK_G16_PROOF_BYTES 256
@@ -773,6 +774,31 @@ int uzk_g16_vk_info(uint64_t vk, uint32_t* n_inputs_out, int* device_out);
 int uzk_g16_verify_fold(uint64_t vk, const uint8_t* proofs, const uint64_t* public_mont, uint32_t m, const uint64_t* weights_mont,
                         uzk_g1_affine* a_out, uzk_g2_affine* b_out, uzk_g1_jac* alpha_out, uzk_g1_jac* x_out, uzk_g1_jac* c_out,
                         uint8_t* status_out);
+
+/* ---- the pairing product: prod_i e(P_i, Q_i) on the device --------------------------------------------------------------------------
+ * The optimal ate pairing of BN254: one Miller loop per pair (independent chains, one pair per group of eight lanes), the values
+ * multiplied down a tree, one final exponentiation by (p^12 - 1) / r EXACTLY -- gt_out is the element arkworks' Bn254::multi_pairing
+ * and the test oracle return, bit for bit, not a power of it.
+ * uzk_gt       sum_k (c[k][0] + c[k][1] u) w^k with u^2 = -1, w^6 = 9 + u; Montgomery words, fully reduced
+ * p, q         n points each, canonical Montgomery words; all zeros is the point at infinity, and a pair with either point at infinity
+ *              contributes 1.  Every coordinate is checked against p, every P against y^2 = x^3 + 3, every Q against the twist
+ *              y^2 = x^3 + 3 / (9 + u): a failure is UZK_ERR_PARAMETER and uzk_last_error names the first bad pair.  Membership of Q in
+ *              the subgroup of order r is NOT checked here: it is the caller's business (uzk_g16_verify_batch has it from the fold's
+ *              status 3; key material is checked when the key is made).
+ * gt_out       optional;  is_one_out  1 iff the product is 1.
+ * n == 0: the empty product, 1.  n > UZK_PAIRING_MAX_PAIRS or a null pointer: UZK_ERR_PARAMETER, before the device is touched. */
+#define UZK_PAIRING_MAX_PAIRS 4099            /* UZK_G16_VERIFY_MAX_BATCH + 3 */
+typedef struct { uint64_t c[6][2][4]; } uzk_gt;
+int uzk_pairing_product(const uzk_g1_affine* p, const uzk_g2_affine* q, uint32_t n, uzk_gt* gt_out, int* is_one_out);
+/* uzk_g16_verify_fold to the end: the fold's kernels, the three sums brought to affine and negated on the device, then the product
+ *     prod_i e(rho_i A_i, B_i) . e(-(sum rho) alpha, g2[0]) . e(-sum rho_i X_i, g2[1]) . e(-sum rho_i C_i, g2[2])
+ * with rho_i A_i and B_i taken from the fold's workspace -- they never visit the host.  Arguments and status rules are those of
+ * uzk_g16_verify_fold; g2 = beta, gamma, delta of the verifying key (a call argument, so that uzk_g16_vk_desc stays what it is; a point
+ * of g2 that is not a canonical point of the twist is UZK_ERR_PARAMETER).
+ * accepted_out  1 iff every status is 0 and the product is 1.  A proof with a nonzero status makes the verdict 0; its status byte says
+ *               why.  m == 0 is accepted (the empty product), status_out may then be NULL. */
+int uzk_g16_verify_batch(uint64_t vk, const uint8_t* proofs, const uint64_t* public_mont, uint32_t m, const uint64_t* weights_mont,
+                         const uzk_g2_affine g2[3], uint8_t* status_out, int* accepted_out);
 
 /* ---- synthetic workloads (bench / tests; generated on device, nothing uploaded) -------- */
 /* d_points[i] = (i + 1) * Q with Q = seed_scalar * G: n distinct valid G1 points whose discrete

@@ -82,6 +82,19 @@ int uzk_test_keccak256(const uint8_t* msgs, const uint64_t* offsets, uint32_t co
  * count x 4 limbs, Montgomery form.  uzk_srs_fold_weights is the host's run of the same code. */
 int uzk_test_srs_weights_device(const uint8_t seed[32], uint64_t count, uint64_t* out_mont);
 
+/* ---- the pairing (csrc/fq12_29.hpp, pairing.hip) ----
+ * Fq12 on wire-form elements (uzk_gt's layout: 48 words each), one element per lane group.  op: 0 a b, 1 a^2, 2 a (b_0 + b_1 w + b_3 w^3)
+ * (the product with a sparse line: b's other coefficients are ignored), 3 conj(a) (the p^6 map), 4 / 5 / 6 a^p, a^(p^2), a^(p^3),
+ * 7 a^-1 by the norm chain (the inverse of 0 is 0), 8 the Granger-Scott square (defined on the cyclotomic subgroup only), 9 the easy part
+ * a^((p^6 - 1)(p^2 + 1)), 10 the hard part a^((p^4 - p^2 + 1) / r) (for a in the cyclotomic subgroup).  Unary ops ignore b (it must still be
+ * readable). */
+int uzk_test_fq12_kat(int op, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n);
+/* The n Miller-loop values of the pairs, before the product and the final exponentiation (no point is checked). */
+int uzk_test_miller(const uzk_g1_affine* p, const uzk_g2_affine* q, uint32_t n, uzk_gt* out);
+/* how the Miller kernel is laid out: pairs per wave = pairs per workgroup (a workgroup is one wave); the product tree's radix */
+#define UZK_PAIRING_PAIRS_PER_WAVE 8
+#define UZK_PAIRING_TREE_RADIX 8
+
 /* ---- synthetic circuits ----
  * TEST / TIMING ONLY -- changes results.  Marks the circuit as synthetic (random polynomials no witness satisfies, the frozen
  * parity vectors and the timing chains): round 3 then takes t as its first 5 n - 2 + sum(hiding) coefficients, as

@@ -237,29 +237,29 @@ pub fn reveal_proof_bytes(a: &G1Affine, b: &G2Affine, c: &G1Affine) -> Vec<u8> {
     out
 }
 
-/// Checks `batch` = [(public inputs without the leading one, (A, B, C))] under `vk` with ONE product of pairings: the weights are
-/// drawn here, after every proof of the batch is fixed; `uzk_g16_verify_fold` decodes and checks the points (B's subgroup included),
-/// computes rho_i A_i and the three sums on the device; the M + 3 Miller loops and the final exponentiation are arkworks'.
-///   Some(Ok(()))        every proof is accepted
-///   Some(Err(indices))  malformed proofs (a nonzero status), or -- an empty list -- a well-formed batch whose product is not one:
-///                       the caller then checks proof by proof to name the wrong ones
-///   None                the device could not serve the call: nothing was decided
-pub fn fold_reveals<R: CryptoRng + RngCore>(prng: &mut R, vk: &RevealVerifyingKey, batch: &[(&[Fr], (G1Affine, G2Affine, G1Affine))]) -> Option<Result<(), Vec<usize>>> {
-    if batch.is_empty() {
-        return Some(Ok(()));
-    }
+/// What both reveal verifiers need: the key on the device, the three G2 points in wire form, the proofs' blobs, the public inputs and
+/// the weights (drawn here, after every proof of the batch is fixed).  None: the batch does not fit the entry point, or no device.
+struct RevealBatch {
+    key: sys::Groth16Vk,
+    g2: [sys::uzk_g2_affine; 3],
+    proofs: Vec<u8>,
+    public: Vec<Limbs>,
+    weights: Vec<Limbs>,
+}
+fn prepare_reveals<R: CryptoRng + RngCore>(prng: &mut R, vk: &RevealVerifyingKey, batch: &[(&[Fr], (G1Affine, G2Affine, G1Affine))]) -> Option<RevealBatch> {
     let l = vk.gamma_abc_g1.len();
     if batch.len() > sys::UZK_G16_VERIFY_MAX_BATCH as usize || l == 0 || l > sys::UZK_G16_VERIFY_MAX_INPUTS as usize {
         return None;
     }
     let ic: Vec<sys::uzk_g1_affine> = vk.gamma_abc_g1.iter().map(affine_to_wire).collect();
+    let g2 = [g2_affine_to_wire(vk.beta_g2), g2_affine_to_wire(vk.gamma_g2), g2_affine_to_wire(vk.delta_g2)];
     let desc = sys::uzk_g16_vk_desc {
         n_inputs: l as u32,
         reserved: 0,
         alpha_g1: affine_to_wire(vk.alpha_g1),
-        beta_g2: g2_affine_to_wire(vk.beta_g2),
-        gamma_g2: g2_affine_to_wire(vk.gamma_g2),
-        delta_g2: g2_affine_to_wire(vk.delta_g2),
+        beta_g2: g2[0],
+        gamma_g2: g2[1],
+        delta_g2: g2[2],
         gamma_abc_g1: ic.as_ptr(),
     };
     let key = sys::Groth16Vk::create(&desc).ok()?;
@@ -273,7 +273,22 @@ pub fn fold_reveals<R: CryptoRng + RngCore>(prng: &mut R, vk: &RevealVerifyingKe
         public.extend(inputs.iter().map(fr_limbs));
     }
     let weights: Vec<Limbs> = if batch.len() == 1 { vec![fr_limbs(&Fr::one())] } else { (0..batch.len()).map(|_| fr_limbs(&Fr::rand(prng))).collect() };
-    let fold = key.fold(&proofs, &public, Some(&weights)).ok()?;
+    Some(RevealBatch { key, g2, proofs, public, weights })
+}
+
+/// Checks `batch` = [(public inputs without the leading one, (A, B, C))] under `vk` with ONE product of pairings: the weights are
+/// drawn here, after every proof of the batch is fixed; `uzk_g16_verify_fold` decodes and checks the points (B's subgroup included),
+/// computes rho_i A_i and the three sums on the device; the M + 3 Miller loops and the final exponentiation are arkworks'.
+///   Some(Ok(()))        every proof is accepted
+///   Some(Err(indices))  malformed proofs (a nonzero status), or -- an empty list -- a well-formed batch whose product is not one:
+///                       the caller then checks proof by proof to name the wrong ones
+///   None                the device could not serve the call: nothing was decided
+pub fn fold_reveals<R: CryptoRng + RngCore>(prng: &mut R, vk: &RevealVerifyingKey, batch: &[(&[Fr], (G1Affine, G2Affine, G1Affine))]) -> Option<Result<(), Vec<usize>>> {
+    if batch.is_empty() {
+        return Some(Ok(()));
+    }
+    let r = prepare_reveals(prng, vk, batch)?;
+    let fold = r.key.fold(&r.proofs, &r.public, Some(&r.weights)).ok()?;
     let malformed: Vec<usize> = fold.status.iter().enumerate().filter(|(_, s)| **s != 0).map(|(i, _)| i).collect();
     if !malformed.is_empty() {
         return Some(Err(malformed));
@@ -285,6 +300,25 @@ pub fn fold_reveals<R: CryptoRng + RngCore>(prng: &mut R, vk: &RevealVerifyingKe
         g2.push(*q);
     }
     if Bn254::multi_pairing(g1, g2).0 == <Bn254 as Pairing>::TargetField::one() {
+        Some(Ok(()))
+    } else {
+        Some(Err(Vec::new()))
+    }
+}
+
+/// `fold_reveals` to the end on the device: `uzk_g16_verify_batch` folds the batch and runs the product of its M + 3 pairings there
+/// (rho_i A_i and B_i never visit the host), so no arkworks pairing is needed.  Same answers as `fold_reveals`.
+pub fn verify_reveals<R: CryptoRng + RngCore>(prng: &mut R, vk: &RevealVerifyingKey, batch: &[(&[Fr], (G1Affine, G2Affine, G1Affine))]) -> Option<Result<(), Vec<usize>>> {
+    if batch.is_empty() {
+        return Some(Ok(()));
+    }
+    let r = prepare_reveals(prng, vk, batch)?;
+    let (accepted, status) = r.key.verify_batch(&r.proofs, &r.public, Some(&r.weights), &r.g2).ok()?;
+    let malformed: Vec<usize> = status.iter().enumerate().filter(|(_, s)| **s != 0).map(|(i, _)| i).collect();
+    if !malformed.is_empty() {
+        return Some(Err(malformed));
+    }
+    if accepted {
         Some(Ok(()))
     } else {
         Some(Err(Vec::new()))

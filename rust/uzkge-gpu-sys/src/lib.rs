@@ -440,6 +440,38 @@ impl Groth16Vk {
         out.status.truncate(m);
         Ok(out)
     }
+    /// The arguments of `fold` and the key's beta, gamma, delta: the fold, then the product of its m + 3 pairings on the device
+    /// (`uzk_g16_verify_batch`).  Returns (accepted, status): accepted iff every status is 0 and the product is one.
+    pub fn verify_batch(&self, proofs: &[u8], public: &[Limbs], weights: Option<&[Limbs]>, g2: &[uzk_g2_affine; 3]) -> Result<(bool, Vec<u8>), Error> {
+        let blob = UZK_G16_PROOF_BYTES as usize;
+        if proofs.len() % blob != 0 {
+            return Err(Error::Parameter);
+        }
+        let m = proofs.len() / blob;
+        if public.len() != m * (self.n_inputs - 1) || weights.map_or(m > 1, |w| w.len() != m) {
+            return Err(Error::Parameter);
+        }
+        let mut status = vec![0u8; m.max(1)];
+        let mut accepted: c_int = 0;
+        let w_ptr = weights.map_or(std::ptr::null(), |w| w.as_ptr() as *const u64);
+        check(unsafe {
+            uzk_g16_verify_batch(self.handle, proofs.as_ptr(), public.as_ptr() as *const u64, m as u32, w_ptr, g2.as_ptr(), status.as_mut_ptr(), &mut accepted)
+        })?;
+        status.truncate(m);
+        Ok((accepted != 0, status))
+    }
+}
+
+/// prod_i e(p_i, q_i) on the device (`uzk_pairing_product`): the element after the final exponentiation, and whether it is one.
+/// Points at infinity (zeros) contribute 1; a point off its curve is a `Parameter` error.  Q's subgroup is the caller's business.
+pub fn pairing_product(p: &[uzk_g1_affine], q: &[uzk_g2_affine]) -> Result<(uzk_gt, bool), Error> {
+    if p.len() != q.len() || p.len() > UZK_PAIRING_MAX_PAIRS as usize {
+        return Err(Error::Parameter);
+    }
+    let mut gt = uzk_gt::default();
+    let mut one: c_int = 0;
+    check(unsafe { uzk_pairing_product(p.as_ptr(), q.as_ptr(), p.len() as u32, &mut gt, &mut one) })?;
+    Ok((gt, one != 0))
 }
 impl Drop for Groth16Vk {
     fn drop(&mut self) {

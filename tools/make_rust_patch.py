@@ -37,7 +37,7 @@ EDITS = {
          '#[cfg(feature = "gpu")]\npub use gpu_prover::{prove_batch as gpu_prove_batch, release_circuits};\n'
          '#[cfg(all(feature = "gpu", feature = "shuffle"))]\npub use gpu_prover::refresh_public_key as gpu_refresh_public_key;\n'
          '\n/// A batch of proofs under one verifier key folded on the MI355X into one pairing check.\n#[cfg(feature = "gpu")]\nmod gpu_verifier;\n'
-         '#[cfg(feature = "gpu")]\npub use gpu_verifier::{\n    fold_reveals as gpu_fold_reveals, release_verifier_keys, reveal_proof_bytes, verify_batch as gpu_verify_batch, RevealVerifyingKey,\n};\n'),
+         '#[cfg(feature = "gpu")]\npub use gpu_verifier::{\n    fold_reveals as gpu_fold_reveals, release_verifier_keys, reveal_proof_bytes, verify_batch as gpu_verify_batch, verify_reveals as gpu_verify_reveals,\n    RevealVerifyingKey,\n};\n'),
     ],
     "shuffle/Cargo.toml": [
         ('no_vk = []\n', 'no_vk = []\n# MI355X backend (uzkge/gpu): device-resident prover and the public-key refresh as one device call\ngpu = ["uzkge/gpu"]\n'),

@@ -132,6 +132,8 @@ PROTOTYPES = {
     "uzk_g16_vk_release": (_I, [_U64]),
     "uzk_g16_vk_info": (_I, [_U64, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(_I)]),
     "uzk_g16_verify_fold": (_I, [_U64, _P, _P, ctypes.c_uint32, _P, _P, _P, _P, _P, _P, _P]),
+    "uzk_pairing_product": (_I, [_P, _P, ctypes.c_uint32, _P, ctypes.POINTER(ctypes.c_int)]),
+    "uzk_g16_verify_batch": (_I, [_U64, _P, _P, ctypes.c_uint32, _P, _P, _P, ctypes.POINTER(ctypes.c_int)]),
     "uzk_synth_points_arith": (_I, [_P, _SZ, _P]),
     "uzk_synth_points_random": (_I, [_P, _SZ, _U64]),
     "uzk_synth_scalars": (_I, [_P, _SZ, _U64]),
@@ -161,6 +163,8 @@ TEST_PROTOTYPES = {
     "uzk_test_p29_kat": (_I, [_I, _P, _P, _SZ]),
     "uzk_test_g2_raw_kat": (_I, [_I, _P, _P, _SZ]),
     "uzk_test_keccak256": (_I, [_P, _P, ctypes.c_uint32, _P]),
+    "uzk_test_fq12_kat": (_I, [_I, _P, _P, _P, _SZ]),
+    "uzk_test_miller": (_I, [_P, _P, ctypes.c_uint32, _P]),
     "uzk_test_srs_weights_device": (_I, [_P, _U64, _P]),
     "uzk_test_lanes": (_I, [_I, _P, _P, ctypes.c_uint32, _P, _P, _P, ctypes.c_uint32, _U64, _P, ctypes.POINTER(ctypes.c_int)]),
 }
@@ -271,6 +275,7 @@ class G16KeyDesc(ctypes.Structure):
 G16_VERIFY_MAX_BATCH = 4096
 G16_VERIFY_MAX_INPUTS = 1024
 G16_PROOF_BYTES = 256
+PAIRING_MAX_PAIRS = 4099
 
 
 class G16VkDesc(ctypes.Structure):

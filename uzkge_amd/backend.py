@@ -1068,10 +1068,57 @@ class Groth16VerifierKey:
                                       vp(status)))
         return a[:m], b[:m], alpha, x, c, status[:m]
 
+    def verify_batch(self, proofs, publics, weights=None):
+        """uzk_g16_verify_batch: the arguments of `fold`; the fold, then the product of its m + 3 pairings on the device with this key's
+        beta, gamma, delta.  Returns (accepted, status [m]): accepted iff every status is 0 and the product is one."""
+        raw = np.frombuffer(bytes(proofs), dtype=np.uint8) if isinstance(proofs, (bytes, bytearray)) else np.ascontiguousarray(proofs, dtype=np.uint8)
+        assert raw.size % N.G16_PROOF_BYTES == 0, "proofs: a whole number of %d-byte blobs" % N.G16_PROOF_BYTES
+        m = raw.size // N.G16_PROOF_BYTES
+        pub = np.ascontiguousarray(publics, dtype=np.uint64).reshape(m, self.n_inputs - 1, 4)
+        w = None if weights is None else np.ascontiguousarray(weights, dtype=np.uint64).reshape(m, 4)
+        g2 = np.ascontiguousarray(np.stack([self.beta_g2, self.gamma_g2, self.delta_g2]), dtype=np.uint64)
+        status = np.zeros(max(m, 1), dtype=np.uint8)
+        accepted = ctypes.c_int(0)
+        vp = lambda arr: arr.ctypes.data_as(ctypes.c_void_p)
+        check(lib.uzk_g16_verify_batch(self.handle, vp(raw), vp(pub), m, None if w is None else _ptr(w), _ptr(g2), vp(status), ctypes.byref(accepted)))
+        return bool(accepted.value), status[:m]
+
     def release(self) -> None:
         if self.handle:
             check(lib.uzk_g16_vk_release(self.handle))
             self.handle = 0
+
+
+def pairing_product(p, q, want_gt: bool = True):
+    """uzk_pairing_product: p [n, 8] affine G1 wire points, q [n, 16] affine G2 wire points (zeros = infinity).  Returns (gt, is_one):
+    gt [6, 2, 4] = the coefficients of w^0 .. w^5 (c0, c1 Montgomery words), the product of the n pairings after the final
+    exponentiation (None when not wanted)."""
+    a = np.ascontiguousarray(p, dtype=np.uint64).reshape(-1, 8)
+    b = np.ascontiguousarray(q, dtype=np.uint64).reshape(-1, 16)
+    assert a.shape[0] == b.shape[0], "one G2 point per G1 point"
+    n = a.shape[0]
+    gt = np.zeros((6, 2, 4), dtype=np.uint64) if want_gt else None
+    one = ctypes.c_int(0)
+    check(lib.uzk_pairing_product(_ptr(a) if n else None, _ptr(b) if n else None, n, _ptr(gt) if want_gt else None, ctypes.byref(one)))
+    return gt, bool(one.value)
+
+
+def fq12_kat(op: int, a, b=None) -> np.ndarray:
+    """uzk_test_fq12_kat (test hook): a, b [n, 6, 2, 4] wire elements of Fq12."""
+    x = np.ascontiguousarray(a, dtype=np.uint64).reshape(-1, 6, 2, 4)
+    y = x if b is None else np.ascontiguousarray(b, dtype=np.uint64).reshape(-1, 6, 2, 4)
+    out = np.zeros_like(x)
+    check(lib.uzk_test_fq12_kat(op, _ptr(x), _ptr(y), _ptr(out), x.shape[0]))
+    return out
+
+
+def miller_loops(p, q) -> np.ndarray:
+    """uzk_test_miller (test hook): the n Miller values [n, 6, 2, 4] of the pairs, before the product and the final exponentiation."""
+    a = np.ascontiguousarray(p, dtype=np.uint64).reshape(-1, 8)
+    b = np.ascontiguousarray(q, dtype=np.uint64).reshape(-1, 16)
+    out = np.zeros((a.shape[0], 6, 2, 4), dtype=np.uint64)
+    check(lib.uzk_test_miller(_ptr(a), _ptr(b), a.shape[0], _ptr(out)))
+    return out
 
 
 def keccak256_device(messages) -> list:

@@ -11,6 +11,7 @@
 #include <new>
 
 #include "ctx.hpp"
+#include "fq12_29.hpp"
 #include "g2_29.hpp"
 #include "host_ec64.hpp"
 #include "host_math.hpp"
@@ -229,6 +230,7 @@ static void ctx_release(Ctx& c) {
     g16_free(c);
     c.verify_ws.release();
     c.g16v_ws.release();
+    c.pairing_ws.release();
     msm_free(c);
     poly_free(c);
     c.ntt_scratch[0].release(); c.ntt_scratch[1].release(); c.ntt_io.release(); c.msm_scalars.release();
@@ -1380,6 +1382,62 @@ int uzk_g16_verify_fold(uint64_t vk, const uint8_t* proofs, const uint64_t* publ
     std::memcpy(c_out, &cc, sizeof cc);
     return UZK_OK;
 } catch (...) { return uzk::on_exception("uzk_g16_verify_fold"); }
+
+/* ---- the pairing product -------------------------------------------------------------------- */
+static const char* pairing_status_text(uint8_t st) { return st == 1 ? "a coordinate word is not below p" : "a point is not on its curve"; }
+
+int uzk_pairing_product(const uzk_g1_affine* p, const uzk_g2_affine* q, uint32_t n, uzk_gt* gt_out, int* is_one_out) try {
+    API_LOCK;
+    if (n > UZK_PAIRING_MAX_PAIRS) { set_error("uzk_pairing_product: %u pairs (at most %d per call)", n, UZK_PAIRING_MAX_PAIRS); return UZK_ERR_PARAMETER; }
+    if (!is_one_out || (n > 0 && (!p || !q))) { set_error("uzk_pairing_product: null pointer"); return UZK_ERR_PARAMETER; }
+    Fq12w gt;
+    uint32_t bad = n;
+    uint8_t bad_status = 0;
+    if (n > 0) UZK_TRY(require_ready());
+    UZK_TRY(pairing_product_run(ctx(), reinterpret_cast<const Affine*>(p), reinterpret_cast<const G2Affine*>(q), false, n, &gt, &bad, &bad_status));
+    if (bad < n) { set_error("uzk_pairing_product: pair %u: %s", bad, pairing_status_text(bad_status)); return UZK_ERR_PARAMETER; }
+    static_assert(sizeof(uzk_gt) == sizeof(Fq12w), "uzk_gt is the wire form of Fq12");
+    if (gt_out) std::memcpy(gt_out, &gt, sizeof gt);
+    *is_one_out = gt_is_one(gt) ? 1 : 0;
+    return UZK_OK;
+} catch (...) { return uzk::on_exception("uzk_pairing_product"); }
+
+int uzk_g16_verify_batch(uint64_t vk, const uint8_t* proofs, const uint64_t* public_mont, uint32_t m, const uint64_t* weights_mont, const uzk_g2_affine g2[3],
+                         uint8_t* status_out, int* accepted_out) try {
+    API_LOCK;
+    if (m > UZK_G16_VERIFY_MAX_BATCH) { set_error("uzk_g16_verify_batch: %u proofs (at most %d per call)", m, UZK_G16_VERIFY_MAX_BATCH); return UZK_ERR_PARAMETER; }
+    if (m > 1 && !weights_mont) { set_error("uzk_g16_verify_batch: %u proofs need a weight each (unweighted sums let errors cancel)", m); return UZK_ERR_PARAMETER; }
+    if (!accepted_out || !g2 || (m > 0 && (!proofs || !status_out))) { set_error("uzk_g16_verify_batch: null pointer"); return UZK_ERR_PARAMETER; }
+    uint32_t n_inputs = 0;
+    if (!g16v_key_known(vk, &n_inputs, nullptr)) { set_error("uzk_g16_verify_batch: unknown verifying key %llu", (unsigned long long)vk); return UZK_ERR_PARAMETER; }
+    if (m > 0 && n_inputs > 1 && !public_mont) { set_error("uzk_g16_verify_batch: null public inputs"); return UZK_ERR_PARAMETER; }
+    if (m == 0) { *accepted_out = 1; return UZK_OK; }              // the empty product
+    UZK_TRY(require_ready());
+    Fq12w gt;
+    uint32_t bad_g2 = 3;
+    UZK_TRY(g16v_verify_run(ctx(), vk, proofs, as_fp(public_mont), m, weights_mont ? as_fp(weights_mont) : nullptr, reinterpret_cast<const G2Affine*>(g2), status_out,
+                            &gt, &bad_g2));
+    if (bad_g2 < 3) { set_error("uzk_g16_verify_batch: g2[%u] is not a canonical point of the twist", bad_g2); return UZK_ERR_PARAMETER; }
+    bool ok = gt_is_one(gt);
+    for (uint32_t i = 0; i < m; ++i) ok = ok && status_out[i] == 0;
+    *accepted_out = ok ? 1 : 0;
+    return UZK_OK;
+} catch (...) { return uzk::on_exception("uzk_g16_verify_batch"); }
+
+int uzk_test_fq12_kat(int op, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n) try {
+    API_LOCK;
+    if (op < 0 || op > 10) { set_error("uzk_test_fq12_kat: unknown op %d", op); return UZK_ERR_PARAMETER; }
+    if (n > (1u << 20) || (n > 0 && (!a || !b || !out))) { set_error("uzk_test_fq12_kat: null pointer or more than 2^20 elements"); return UZK_ERR_PARAMETER; }
+    UZK_TRY(require_ready());
+    return pairing_kat_device(ctx(), op, reinterpret_cast<const Fq12w*>(a), reinterpret_cast<const Fq12w*>(b), reinterpret_cast<Fq12w*>(out), (uint32_t)n);
+} catch (...) { return uzk::on_exception("uzk_test_fq12_kat"); }
+
+int uzk_test_miller(const uzk_g1_affine* p, const uzk_g2_affine* q, uint32_t n, uzk_gt* out) try {
+    API_LOCK;
+    if (n > UZK_PAIRING_MAX_PAIRS || (n > 0 && (!p || !q || !out))) { set_error("uzk_test_miller: null pointer or too many pairs"); return UZK_ERR_PARAMETER; }
+    UZK_TRY(require_ready());
+    return pairing_miller_device(ctx(), reinterpret_cast<const Affine*>(p), reinterpret_cast<const G2Affine*>(q), n, reinterpret_cast<Fq12w*>(out));
+} catch (...) { return uzk::on_exception("uzk_test_miller"); }
 
 int uzk_test_keccak256(const uint8_t* msgs, const uint64_t* offsets, uint32_t count, uint8_t* digests_out) try {
     API_LOCK;

@@ -148,6 +148,9 @@ struct Ctx {
     void* g16 = nullptr;
     // g16verify.hip: one block carved into the arrays of a Groth16 fold (proofs, public inputs, weights, decoded points, results)
     DevBuf g16v_ws;
+    // pairing.hip: one block carved into the arrays of a pairing product (constants, points, statuses, the tree's two levels)
+    DevBuf pairing_ws;
+    std::vector<uint8_t> pairing_status;   // the statuses of a product's pairs on the host (grow-only)
     int tune_verify_transcript = 0;   // which transcript kernel a fold runs: 1 one proof per lane; 0 / 2 a proof's state spread over a half wave (the default)
     // an entry of the process-wide SRS registry
     struct Srs {
@@ -289,6 +292,16 @@ int g16v_key_release(uint64_t h);
 void g16v_release_all();
 int g16v_fold_run(Ctx& c, uint64_t h, const uint8_t* proofs, const Fp* pub, uint32_t m, const Fp* weights, Affine* a_out, G2Affine* b_out,
                   Jac* alpha_out, Jac* x_out, Jac* c_out, uint8_t* status_out);
+// pairing.hip: the pairing product over host or device points (the first pair that failed its check in *bad_out, n if none), the
+// constants the host computes at start-up, the known-answer kernels
+struct Fq12w;
+int pairing_product_run(Ctx& c, const Affine* p, const G2Affine* q, bool on_device, uint32_t n, Fq12w* gt_out, uint32_t* bad_out, uint8_t* bad_status);
+bool gt_is_one(const Fq12w& a);
+int pairing_kat_device(Ctx& c, int op, const Fq12w* a, const Fq12w* b, Fq12w* out, uint32_t n);
+int pairing_miller_device(Ctx& c, const Affine* p, const G2Affine* q, uint32_t n, Fq12w* out);
+// g16verify.hip: the fold, then the product of its M + 3 pairs without leaving the device (g2: beta, gamma, delta on the host)
+int g16v_verify_run(Ctx& c, uint64_t h, const uint8_t* proofs, const Fp* pub, uint32_t m, const Fp* weights, const G2Affine* g2, uint8_t* status_out,
+                    Fq12w* gt_out, uint32_t* bad_g2_out);
 void msm_plan_info(Ctx& c, size_t n, int* window_bits, int* windows);
 int msm_run(Ctx& c, const Affine* points, const ScalarView& scalars, size_t n, uint32_t batch, Jac* out_host, int pre_c,
             uint32_t pre_stride, uint32_t pre_off);

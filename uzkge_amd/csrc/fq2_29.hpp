@@ -102,6 +102,16 @@ __device__ __forceinline__ E2<1, Z::prod_v(V, 1)> mul_fq(const E2<1, V>& x, cons
     Lz<Fq29, 1, 1> k; k.v = F::constant(c);
     E2<1, Z::prod_v(V, 1)> r; r.a = Z::mul(x.a, k); r.b = Z::mul(x.b, k); return r;
 }
+// the product with an element of Fq (2^261-form): two products
+template <int V, int Vb>
+__device__ __forceinline__ E2<1, Z::prod_v(V, Vb)> mul_base(const E2<1, V>& x, const Lz<Fq29, 1, Vb>& k) {
+    E2<1, Z::prod_v(V, Vb)> r; r.a = Z::mul(x.a, k); r.b = Z::mul(x.b, k); return r;
+}
+// a0 - a1 u (the p-power map of Fq2)
+template <int K, int V>
+__device__ __forceinline__ E2<K + 3, V + 2> conj(const E2<K, V>& x) {
+    E2<K + 3, V + 2> r; r.a = Z::template relax<K + 3, V + 2>(x.a); r.b = Z::sub(Z::zero(), x.b); return r;
+}
 // 0 in Fq2?  Exact for every value below 32 M: one reduction (< 2 M), then the three candidates 0, M, 2 M.  The second component is
 // only looked at when the first is zero.
 template <int K, int V>

@@ -24,6 +24,8 @@
 #include <vector>
 
 #include "ctx.hpp"
+#include "curvecheck.hpp"
+#include "fq12_29.hpp"
 #include "g2_29.hpp"
 #include "host_math.hpp"
 
@@ -33,39 +35,6 @@ constexpr uint32_t kGvBlock = 64;
 constexpr uint32_t kGvWords = 8;
 static_assert(kGvWords * 32 == UZK_G16_PROOF_BYTES, "a blob is eight 32-byte words");
 enum { GV_OK = 0, GV_NOT_CANONICAL = 1, GV_OFF_CURVE = 2, GV_NOT_IN_SUBGROUP = 3 };
-
-template <class C>
-UZK_HD bool gv_below_modulus(const Fp& a) {
-    uint64_t br = 0;
-    for (int i = 0; i < 8; ++i) { const uint64_t t = (uint64_t)a.v[i] - C::M[i] - br; br = (t >> 32) & 1; }
-    return br != 0;
-}
-
-UZK_HD bool gv_g1_on_curve(const Affine& p) {
-    const Fp one = Fq::one();
-    const Fp three = Fq::add(Fq::add(one, one), one);
-    return Fq::eq(Fq::sqr(p.y), Fq::add(Fq::mul(Fq::sqr(p.x), p.x), three));
-}
-
-#if defined(__HIP_DEVICE_COMPILE__)
-// the twist's constant 3 / (9 + u) = (27 / 82, -3 / 82), canonical words
-__device__ __forceinline__ Fq2w gv_twist_b() {
-    Fq2w b;
-    const uint32_t c0[8] = {0x24a138e5u, 0x3267e6dcu, 0x59dbefa3u, 0xb5b4c5e5u, 0x1be06ac3u, 0x81be1899u, 0xceb8aaaeu, 0x2b149d40u};
-    const uint32_t c1[8] = {0x85c315d2u, 0xe4a2bd06u, 0xe52d1852u, 0xa74fa084u, 0xeed8fdf4u, 0xcd2cafadu, 0x3af0fed4u, 0x009713b0u};
-    Fp a0, a1;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) { a0.v[i] = c0[i]; a1.v[i] = c1[i]; }
-    b.c0 = Fq::to_mont(a0); b.c1 = Fq::to_mont(a1);
-    return b;
-}
-__device__ __forceinline__ bool gv_g2_on_twist(const G2Affine& p) {
-    using namespace q2;
-    const auto X = ldr(p.x), Y = ldr(p.y);
-    const auto rhs = add(mul(sqr(X), X), ldr(gv_twist_b()));
-    return is_zero(sub(sqr(Y), rhs));
-}
-#endif
 
 // ---- decode and check -----------------------------------------------------------------------------------------------------------
 // A proof with a nonzero status leaves infinities in the three point arrays.  The twist has r (2 p - r) points, an odd number, so no
@@ -279,19 +248,79 @@ void g16v_release_all() {
 // ---- the fold -----------------------------------------------------------------------------------------------------------------
 static size_t gv_align(size_t v) { return (v + 255) & ~(size_t)255; }
 
+// The G1 arguments of the last three pairs: -(t_0 alpha) from the scalar multiplications' array, -X and -C from the MSMs' Jacobian sums
+// (X / Z^2, Y / Z^3), brought to affine with the inversion in the lane.  Three lanes; no barrier.
+// out may be alpha_w: lane 0 reads its point before it writes it, the other lanes write behind it
+__global__ __launch_bounds__(kGvBlock) void g16v_tail_kernel(const Affine* alpha_w, const Jac* __restrict__ xc, Affine* out) {
+    const uint32_t t = threadIdx.x;
+    if (t >= 3) return;
+    Affine r;
+    r.x = Fq::zero(); r.y = r.x;
+    if (t == 0) {
+        if (!affine_is_inf(*alpha_w)) { r.x = alpha_w->x; r.y = Fq::neg(alpha_w->y); }
+    } else {
+        const Jac j = xc[t - 1];
+        if (!Fq::is_zero(j.z)) {
+            const Fp zi = gv_fq_inv(j.z), zi2 = Fq::sqr(zi);
+            r.x = Fq::mul(j.x, zi2);
+            r.y = Fq::neg(Fq::mul(j.y, Fq::mul(zi2, zi)));
+        }
+    }
+    out[t] = r;
+}
+
+struct GvKeep {            // where a fold left rho_i A_i (then t_0 alpha) and B_i, each with room for the product's three further pairs
+    const char* who = "uzk_g16_verify_batch";
+    Affine* d_ra = nullptr;
+    G2Affine* d_b = nullptr;
+    Jac* d_xc = nullptr;
+};
+static int g16v_fold_impl(Ctx& c, uint64_t h, const uint8_t* proofs, const Fp* pub, uint32_t m, const Fp* weights, Affine* a_out, G2Affine* b_out,
+                          Jac* alpha_out, Jac* x_out, Jac* c_out, uint8_t* status_out, GvKeep* keep);
+
 // m >= 1.  a_out, b_out: m points each; alpha_out, x_out, c_out: one Jacobian point each.
 int g16v_fold_run(Ctx& c, uint64_t h, const uint8_t* proofs, const Fp* pub, uint32_t m, const Fp* weights, Affine* a_out, G2Affine* b_out,
                   Jac* alpha_out, Jac* x_out, Jac* c_out, uint8_t* status_out) {
+    return g16v_fold_impl(c, h, proofs, pub, m, weights, a_out, b_out, alpha_out, x_out, c_out, status_out, nullptr);
+}
+
+// The fold's kernels, then prod_i e(rho_i A_i, B_i) e(-t_0 alpha, beta) e(-X, gamma) e(-C, delta): rho_i A_i and B_i go from the
+// fold's workspace to the Miller loops without leaving the device; the two MSM sums come back from msm_run as Jacobian points and
+// are brought to affine and negated on the device.  *bad_g2_out < 3: that point of g2 failed the product's check.
+int g16v_verify_run(Ctx& c, uint64_t h, const uint8_t* proofs, const Fp* pub, uint32_t m, const Fp* weights, const G2Affine* g2, uint8_t* status_out,
+                    Fq12w* gt_out, uint32_t* bad_g2_out) {
+    GvKeep k;
+    Jac xc[2], al;
+    UZK_TRY(g16v_fold_impl(c, h, proofs, pub, m, weights, nullptr, nullptr, &al, &xc[0], &xc[1], status_out, &k));
+    UZK_HIP(hipMemcpyAsync(k.d_xc, xc, sizeof xc, hipMemcpyHostToDevice, c.stream));
+    UZK_HIP(hipMemcpyAsync(k.d_b + m, g2, 3 * sizeof(G2Affine), hipMemcpyHostToDevice, c.stream));
+    {
+        KernelScope ks(c, "g16v_tail");                            // t_0 alpha is replaced by its negative where it lies; -X and -C follow it
+        hipLaunchKernelGGL(g16v_tail_kernel, dim3(1), dim3(kGvBlock), 0, c.stream, k.d_ra + m, k.d_xc, k.d_ra + m);
+    }
+    UZK_HIP(hipGetLastError());
+    uint32_t bad = m + 3;
+    uint8_t bad_status = 0;
+    UZK_TRY(pairing_product_run(c, k.d_ra, k.d_b, true, m + 3, gt_out, &bad, &bad_status));   // synchronises: xc and g2 were read
+    // the fold's own points passed the same checks in g16v_decode; only the caller's three can fail here
+    *bad_g2_out = bad >= m && bad < m + 3 ? bad - m : 3;
+    if (bad < m) { set_error("uzk_g16_verify_batch: pair %u of the fold failed the product's check", bad); return UZK_ERR_DEVICE; }
+    return UZK_OK;
+}
+
+static int g16v_fold_impl(Ctx& c, uint64_t h, const uint8_t* proofs, const Fp* pub, uint32_t m, const Fp* weights, Affine* a_out, G2Affine* b_out,
+                          Jac* alpha_out, Jac* x_out, Jac* c_out, uint8_t* status_out, GvKeep* keep) {
     GvEntry e;
-    if (!gv_lookup(h, &e)) { set_error("uzk_g16_verify_fold: unknown verifying key %llu", (unsigned long long)h); return UZK_ERR_PARAMETER; }
-    if (e.device != c.device) { set_error("uzk_g16_verify_fold: the key lives on device %d, the calling context on device %d", e.device, c.device); return UZK_ERR_PARAMETER; }
+    const char* who = keep ? keep->who : "uzk_g16_verify_fold";
+    if (!gv_lookup(h, &e)) { set_error("%s: unknown verifying key %llu", who, (unsigned long long)h); return UZK_ERR_PARAMETER; }
+    if (e.device != c.device) { set_error("%s: the key lives on device %d, the calling context on device %d", who, e.device, c.device); return UZK_ERR_PARAMETER; }
     const uint32_t n_pub = e.n_inputs - 1;
     size_t at = 0;
     auto carve = [&](size_t bytes) { const size_t o = at; at += gv_align(bytes); return o; };
     const size_t o_proofs = carve((size_t)m * UZK_G16_PROOF_BYTES), o_pub = carve((size_t)m * n_pub * sizeof(Fp)), o_rho = carve((size_t)m * sizeof(Fp)),
                  o_wm = carve((size_t)m * sizeof(Fp)), o_status = carve(m), o_a = carve((size_t)m * sizeof(Affine)),
-                 o_b = carve((size_t)m * sizeof(G2Affine)), o_c = carve((size_t)m * sizeof(Affine)), o_t = carve((size_t)e.n_inputs * sizeof(Fp)),
-                 o_ra = carve(((size_t)m + 1) * sizeof(Affine));
+                 o_b = carve(((size_t)m + 3) * sizeof(G2Affine)), o_c = carve((size_t)m * sizeof(Affine)), o_t = carve((size_t)e.n_inputs * sizeof(Fp)),
+                 o_ra = carve(((size_t)m + 3) * sizeof(Affine)), o_xc = carve(2 * sizeof(Jac));   // m + 1 of o_ra for a fold; the product's pairs lie behind
     UZK_TRY(c.g16v_ws.reserve(at));
     char* ws = c.g16v_ws.as<char>();
     uint8_t* d_proofs = reinterpret_cast<uint8_t*>(ws + o_proofs);
@@ -304,6 +333,9 @@ int g16v_fold_run(Ctx& c, uint64_t h, const uint8_t* proofs, const Fp* pub, uint
     Affine* d_c = reinterpret_cast<Affine*>(ws + o_c);
     Fp* d_t = reinterpret_cast<Fp*>(ws + o_t);
     Affine* d_ra = reinterpret_cast<Affine*>(ws + o_ra);
+    if (keep) {
+        keep->d_ra = d_ra; keep->d_b = d_b; keep->d_xc = reinterpret_cast<Jac*>(ws + o_xc);
+    }
     const Fp one = Fr::one();
     UZK_HIP(hipMemcpyAsync(d_proofs, proofs, (size_t)m * UZK_G16_PROOF_BYTES, hipMemcpyHostToDevice, c.stream));
     if (n_pub) UZK_HIP(hipMemcpyAsync(d_pub, pub, (size_t)m * n_pub * sizeof(Fp), hipMemcpyHostToDevice, c.stream));
@@ -331,9 +363,9 @@ int g16v_fold_run(Ctx& c, uint64_t h, const uint8_t* proofs, const Fp* pub, uint
     UZK_HIP(hipGetLastError());
     Affine alpha_w;                                                // t_0 alpha, read after the last synchronisation
     UZK_HIP(hipMemcpyAsync(status_out, d_status, m, hipMemcpyDeviceToHost, c.stream));
-    UZK_HIP(hipMemcpyAsync(a_out, d_ra, (size_t)m * sizeof(Affine), hipMemcpyDeviceToHost, c.stream));
+    if (a_out) UZK_HIP(hipMemcpyAsync(a_out, d_ra, (size_t)m * sizeof(Affine), hipMemcpyDeviceToHost, c.stream));
     UZK_HIP(hipMemcpyAsync(&alpha_w, d_ra + m, sizeof(Affine), hipMemcpyDeviceToHost, c.stream));
-    UZK_HIP(hipMemcpyAsync(b_out, d_b, (size_t)m * sizeof(G2Affine), hipMemcpyDeviceToHost, c.stream));
+    if (b_out) UZK_HIP(hipMemcpyAsync(b_out, d_b, (size_t)m * sizeof(G2Affine), hipMemcpyDeviceToHost, c.stream));
     if (c.prof_on) UZK_HIP(hipStreamSynchronize(c.stream));        // so that the two host sections below time the MSMs alone
     int rc;
     {

@@ -447,7 +447,7 @@ class PlonkVerifierKey:
     """PlonkVerifierParams (uzkge/src/plonk/indexer.rs) resident on the device, for batches of proofs: `fold` runs everything of the
     verifier (verifier.rs:17-164) in front of its two pairings for m proofs at once and returns the two G1 points of the ONE check
         e(L, [tau] G2) = e(R, G2)
-    that stands for all of them.  The pairing is the caller's: this library computes none.
+    that stands for all of them; `verify_batch` goes on to that check on the device (uzk_pairing_product) and returns the verdict.
 
     vk: the key as integers -- cm_q (9 points), cm_s (5), cm_qb, cm_prk (4), k (5), anemoi_g, anemoi_g_inv, edwards_a, root, cs_size,
     pi_root_powers, pi_lagrange and, with the shuffle feature, cm_q_ecc, cm_shuffle_public_key (12), cm_shuffle_generator (12);
@@ -483,6 +483,19 @@ class PlonkVerifierKey:
                 pi[i, j] = fr_from_int(int(v))
         w = None if weights is None else np.stack([fr_from_int(int(v)) for v in weights]) if m else np.zeros((0, 4), dtype=np.uint64)
         return self.key.fold(b"".join(proofs), pi, w)
+
+    def verify_batch(self, proofs: Sequence[bytes], pis: Sequence[Sequence[int]], weights: Optional[Sequence[int]], g2_0, g2_1):
+        """`fold`, then the check it stands for on the device: e(L, [tau] H) e(-R, H) = 1 with H = g2_0 and [tau] H = g2_1, the two G2
+        elements of the SRS as integers ((x0, x1), (y0, y1)).  Returns (accepted, status): accepted iff every status is 0 and the
+        product is one."""
+        left, right, status = self.fold(proofs, pis, weights)
+        l_aff, r_aff = B.g1_to_affine(left), B.g1_to_affine(right)
+        y = _wire_int(r_aff[4:])
+        if y:
+            y = FQ_MODULUS - y                                       # Montgomery form is linear: -R
+            r_aff = np.concatenate([r_aff[:4], np.array([(y >> (64 * k)) & _MASK64 for k in range(4)], dtype=np.uint64)])
+        _, one = B.pairing_product(np.stack([l_aff, r_aff]), np.stack([g2_wire(g2_1), g2_wire(g2_0)]), want_gt=False)
+        return bool(one and not np.any(status)), status
 
     def release(self) -> None:
         self.key.release()
@@ -567,7 +580,7 @@ class Groth16VerifierKey:
     """A Groth16 verifying key resident on the device, for batches of proofs: `fold` runs everything in front of the pairings for m
     proofs at once and returns the G1 (and G2) arguments of the ONE product of m + 3 Miller loops
         prod_i e(rho_i A_i, B_i) . e(-(sum rho) alpha, beta) . e(-sum rho_i X_i, gamma) . e(-sum rho_i C_i, delta) = 1
-    that stands for all of them.  The pairings are the caller's: this library computes none.
+    that stands for all of them; `verify_batch` goes on to that product on the device and returns the verdict.
 
     Points are integers: G1 (x, y), G2 ((x0, x1), (y0, y1)), None = infinity."""
 
@@ -595,22 +608,32 @@ class Groth16VerifierKey:
     def from_key_bytes(cls, head: bytes) -> "Groth16VerifierKey":
         return cls(*cls.parse_key_bytes(head))
 
+    def _inputs(self, what, proofs, publics, weights):
+        m = len(proofs)
+        if m != len(publics) or (weights is not None and len(weights) != m) or any(len(p) != N.G16_PROOF_BYTES for p in proofs):
+            raise UzkgeError(N.UZK_ERR_PARAMETER, "Groth16VerifierKey.%s: one 256-byte blob, one list of public inputs and one weight per proof" % what)
+        pub = np.zeros((m, self.n_inputs - 1, 4), dtype=np.uint64)
+        for i, row in enumerate(publics):
+            if len(row) != self.n_inputs - 1:
+                raise UzkgeError(N.UZK_ERR_PARAMETER, "Groth16VerifierKey.%s: %d public inputs per proof" % (what, self.n_inputs - 1))
+            for j, v in enumerate(row):
+                pub[i, j] = fr_from_int(int(v))
+        w = None if weights is None else np.stack([fr_from_int(int(v)) for v in weights]) if m else np.zeros((0, 4), dtype=np.uint64)
+        return pub, w
+
     def fold(self, proofs: Sequence[bytes], publics: Sequence[Sequence[int]], weights: Optional[Sequence[int]] = None):
         """proofs: m blobs of 256 bytes (g16_proof_blob); publics: m lists of l - 1 integers (the leading one is implied); weights: m
         integers the CALLER draws after it has the proofs (None only for one proof: weight 1).  Returns (a [m, 8], b [m, 16], alpha
         [12], x [12], c [12], status [m]): rho_i A_i as affine wire points, B_i, three Jacobian wire points and one byte per proof (0
         folded, 1 a word >= p, 2 a point off its curve, 3 B outside the subgroup -- such a proof is left out of every sum)."""
-        m = len(proofs)
-        if m != len(publics) or (weights is not None and len(weights) != m) or any(len(p) != N.G16_PROOF_BYTES for p in proofs):
-            raise UzkgeError(N.UZK_ERR_PARAMETER, "Groth16VerifierKey.fold: one 256-byte blob, one list of public inputs and one weight per proof")
-        pub = np.zeros((m, self.n_inputs - 1, 4), dtype=np.uint64)
-        for i, row in enumerate(publics):
-            if len(row) != self.n_inputs - 1:
-                raise UzkgeError(N.UZK_ERR_PARAMETER, "Groth16VerifierKey.fold: %d public inputs per proof" % (self.n_inputs - 1))
-            for j, v in enumerate(row):
-                pub[i, j] = fr_from_int(int(v))
-        w = None if weights is None else np.stack([fr_from_int(int(v)) for v in weights]) if m else np.zeros((0, 4), dtype=np.uint64)
+        pub, w = self._inputs("fold", proofs, publics, weights)
         return self.key.fold(b"".join(proofs), pub, w)
+
+    def verify_batch(self, proofs: Sequence[bytes], publics: Sequence[Sequence[int]], weights: Optional[Sequence[int]] = None):
+        """The arguments of `fold`; the fold and the product of its m + 3 pairings on the device (uzk_g16_verify_batch).  Returns
+        (accepted, status [m]): accepted iff every status is 0 and the product is one; no proofs are accepted."""
+        pub, w = self._inputs("verify_batch", proofs, publics, weights)
+        return self.key.verify_batch(b"".join(proofs), pub, w)
 
     def info(self):
         return self.key.info()
