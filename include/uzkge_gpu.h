@@ -800,6 +800,48 @@ int uzk_pairing_product(const uzk_g1_affine* p, const uzk_g2_affine* q, uint32_t
 int uzk_g16_verify_batch(uint64_t vk, const uint8_t* proofs, const uint64_t* public_mont, uint32_t m, const uint64_t* weights_mont,
                          const uzk_g2_affine g2[3], uint8_t* status_out, int* accepted_out);
 
+/* ---- Baby Jubjub: the curve the cards live on, and the Chaum-Pedersen reveal proofs over it ------------------------------------------
+ * zshuffle's cards and keys are points of the twisted Edwards curve x^2 + y^2 = 1 + d x^2 y^2 over BN254's scalar field
+ * (ark_ed_on_bn254: a = 1, d = 168696 / 168700, identity (0, 1), cofactor 8, prime subgroup of order
+ * L = 2736030358979909402780800718157159386076813972158567259200215660948447373041, generator as in EdOnBN254.sol).  The six public
+ * signals of a Groth16 reveal proof are three of its points -- masked.e1, reveal = sk e1, pk = sk G -- and the plain reveal path
+ * (shuffle/src/reveal.rs over uzkge/src/chaum_pedersen/dl.rs; ChaumPedersenDLVerifier.sol) proves the same statement with a
+ * Chaum-Pedersen DL proof, 52 per player per deck.  Batches run one lane per item (per equation for the verifier).
+ *   point      two elements of Fr, x then y, in EXACTLY the element encoding uzk_g16_verify_fold takes for its public signals
+ *              (4 Montgomery words each).  Affine; the identity is (0, 1) as in arkworks (the contract's (0, 0) is not a point here)
+ *   scalar     a 256-bit integer, 4 little-endian 64-bit words, NOT in Montgomery form and not reduced: an integer multiple is
+ *              defined on the whole curve
+ *   statement  six elements e1.x, e1.y, reveal.x, reveal.y, pk.x, pk.y: ONE buffer of m x 6 elements serves both
+ *              uzk_g16_verify_fold / uzk_g16_verify_batch (as public_mont, l = 7) and uzk_cp_reveal_verify_batch
+ *   proof      ChaumPedersenDLProof::to_uncompress: UZK_CP_PROOF_BYTES, the 32-byte big-endian words a.x a.y b.x b.y r
+ * Calls that compute with their points (mul, sum, unmask, prove) refuse a coordinate that is not below q with UZK_ERR_PARAMETER
+ * before the device is touched; the two checking calls report it as status 1.  A batch of 0 is UZK_ERR_PARAMETER. */
+#define UZK_ED_MAX_BATCH 1048576
+#define UZK_ED_MAX_ROWS 1024
+#define UZK_CP_MAX_BATCH 65536
+#define UZK_CP_PROOF_BYTES 160
+/* status_out: n bytes, the first that applies: 1 a coordinate word >= q; 2 off the curve; 3 [L] P != identity; 0 otherwise. */
+int uzk_ed_check_points(const uint64_t* points_mont, size_t n, uint8_t* status_out);
+/* out_i = s_i P_i, canonical affine words.  point_stride 1: n points; 0: points_mont holds one base shared by every item. */
+int uzk_ed_mul_batch(const uint64_t* points_mont, size_t point_stride, const uint64_t* scalars, size_t n, uint64_t* out_mont);
+/* out_j = sum_k rows[k n + j] over k rows of n points (aggregateKeys: n = 1, one key per row). */
+int uzk_ed_sum_batch(const uint64_t* rows_mont, uint32_t k, uint32_t n, uint64_t* out_mont);
+/* out_j = e2_j - sum_k reveals[k n + j]: the cards of n masked cards from the reveals of k players (shuffle/src/reveal.rs unmask). */
+int uzk_ed_unmask_batch(const uint64_t* e2_mont, const uint64_t* reveals_mont, uint32_t k, uint32_t n, uint64_t* out_mont);
+/* One player's reveals of m masked cards: reveal_i = sk e1_i, pk = sk G and the proof (a_i = omega_i e1_i, b_i = omega_i G,
+ * c_i = Keccak-256(pad32("Revealing") | pad32("DL") | e1_i, G, reveal_i, pk, a_i, b_i as big-endian words) mod L,
+ * r_i = omega_i + c_i sk mod L).  sk: one scalar below L; omegas: m scalars drawn by the CALLER (the library has no random number
+ * generator); e1: m points of the prime subgroup (uzk_ed_check_points says whether they are).
+ * reveal_out: m points; pk_out: one point; proofs_out: m blobs. */
+int uzk_cp_reveal_prove_batch(const uint64_t* sk, const uint64_t* e1_mont, const uint64_t* omegas, uint32_t m, uint64_t* reveal_out, uint64_t* pk_out,
+                              uint8_t* proofs_out);
+/* verdict_out     m bytes, the first that applies: 1 a statement or proof coordinate >= q; 2 a point off the curve; 3 a point outside
+ *                 the prime subgroup; 4 r e1 != a + c reveal; 5 r G != b + c pk; 0 accepted.  r is taken as any 256-bit integer (the
+ *                 reference reduces it mod L; on subgroup points the results agree).  The call returns UZK_OK unless it is itself
+ *                 malformed: the caller reads the verdicts
+ * challenges_out  optional, m x 4 words: c_i as plain integers below L (undefined for a verdict of 1) */
+int uzk_cp_reveal_verify_batch(const uint64_t* statements_mont, const uint8_t* proofs, uint32_t m, uint8_t* verdict_out, uint64_t* challenges_out);
+
 /* ---- synthetic workloads (bench / tests; generated on device, nothing uploaded) -------- */
 /* d_points[i] = (i + 1) * Q with Q = seed_scalar * G: n distinct valid G1 points whose discrete
  * logs relative to Q are known, so MSM(points, s) == (sum_i s_i (i+1)) * Q for any size. */

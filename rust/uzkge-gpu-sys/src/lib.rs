@@ -479,6 +479,84 @@ impl Drop for Groth16Vk {
     }
 }
 
+// ---- Baby Jubjub (ark_ed_on_bn254) and the Chaum-Pedersen reveal proofs over it ---------------------------------------------------
+/// A point on the wire: x then y, the Montgomery words of `ark_bn254::Fr` (the element encoding of the Groth16 public signals).
+pub type EdPoint = [Limbs; 2];
+/// A reveal statement: e1, reveal, pk -- also the six public signals of the Groth16 reveal proof of the same statement.
+pub type RevealStatement = [EdPoint; 3];
+
+/// The status of every point (`uzk_ed_check_points`): 0 in the prime subgroup, 1 a coordinate word >= q, 2 off the curve, 3 on the
+/// curve outside the subgroup.
+pub fn ed_check_points(points: &[EdPoint]) -> Result<Vec<u8>, Error> {
+    if points.is_empty() {
+        return Err(Error::Parameter);
+    }
+    let mut status = vec![0u8; points.len()];
+    check(unsafe { uzk_ed_check_points(points.as_ptr() as *const u64, points.len(), status.as_mut_ptr()) })?;
+    Ok(status)
+}
+
+/// s_i P_i for 256-bit integers s_i as four little-endian words, not reduced (`uzk_ed_mul_batch`); one point serves every scalar.
+pub fn ed_mul_batch(points: &[EdPoint], scalars: &[Limbs]) -> Result<Vec<EdPoint>, Error> {
+    if scalars.is_empty() || (points.len() != scalars.len() && points.len() != 1) {
+        return Err(Error::Parameter);
+    }
+    let stride = if points.len() == scalars.len() { 1 } else { 0 };
+    let mut out = vec![[[0u64; 4]; 2]; scalars.len()];
+    check(unsafe { uzk_ed_mul_batch(points.as_ptr() as *const u64, stride, scalars.as_ptr() as *const u64, scalars.len(), out.as_mut_ptr() as *mut u64) })?;
+    Ok(out)
+}
+
+/// The sum over k rows of n points, card by card (`uzk_ed_sum_batch`); rows[k * n + j].
+pub fn ed_sum_batch(rows: &[EdPoint], k: usize, n: usize) -> Result<Vec<EdPoint>, Error> {
+    if k == 0 || n == 0 || rows.len() != k * n {
+        return Err(Error::Parameter);
+    }
+    let mut out = vec![[[0u64; 4]; 2]; n];
+    check(unsafe { uzk_ed_sum_batch(rows.as_ptr() as *const u64, k as u32, n as u32, out.as_mut_ptr() as *mut u64) })?;
+    Ok(out)
+}
+
+/// e2_j minus the k reveals of card j (`uzk_ed_unmask_batch`); reveals[k * n + j].
+pub fn ed_unmask_batch(e2: &[EdPoint], reveals: &[EdPoint], k: usize) -> Result<Vec<EdPoint>, Error> {
+    let n = e2.len();
+    if k == 0 || n == 0 || reveals.len() != k * n {
+        return Err(Error::Parameter);
+    }
+    let mut out = vec![[[0u64; 4]; 2]; n];
+    check(unsafe { uzk_ed_unmask_batch(e2.as_ptr() as *const u64, reveals.as_ptr() as *const u64, k as u32, n as u32, out.as_mut_ptr() as *mut u64) })?;
+    Ok(out)
+}
+
+/// One player's reveals of m masked cards (`uzk_cp_reveal_prove_batch`): (reveal cards, pk, m proof blobs of UZK_CP_PROOF_BYTES).
+/// `sk` and `omegas` are plain integers below the subgroup order; the caller draws one fresh omega per card.
+pub fn cp_reveal_prove_batch(sk: &Limbs, e1: &[EdPoint], omegas: &[Limbs]) -> Result<(Vec<EdPoint>, EdPoint, Vec<u8>), Error> {
+    let m = e1.len();
+    if m == 0 || m > UZK_CP_MAX_BATCH as usize || omegas.len() != m {
+        return Err(Error::Parameter);
+    }
+    let mut reveal = vec![[[0u64; 4]; 2]; m];
+    let mut pk: EdPoint = [[0u64; 4]; 2];
+    let mut proofs = vec![0u8; m * UZK_CP_PROOF_BYTES as usize];
+    check(unsafe {
+        uzk_cp_reveal_prove_batch(sk.as_ptr(), e1.as_ptr() as *const u64, omegas.as_ptr() as *const u64, m as u32, reveal.as_mut_ptr() as *mut u64,
+                                  pk.as_mut_ptr() as *mut u64, proofs.as_mut_ptr())
+    })?;
+    Ok((reveal, pk, proofs))
+}
+
+/// The verdict byte of every (statement, proof) (`uzk_cp_reveal_verify_batch`): 0 accepted, 1 .. 3 a malformed point (as
+/// `ed_check_points`), 4 the first equation fails, 5 the second.
+pub fn cp_reveal_verify_batch(statements: &[RevealStatement], proofs: &[u8]) -> Result<Vec<u8>, Error> {
+    let m = statements.len();
+    if m == 0 || m > UZK_CP_MAX_BATCH as usize || proofs.len() != m * UZK_CP_PROOF_BYTES as usize {
+        return Err(Error::Parameter);
+    }
+    let mut verdict = vec![0u8; m];
+    check(unsafe { uzk_cp_reveal_verify_batch(statements.as_ptr() as *const u64, proofs.as_ptr(), m as u32, verdict.as_mut_ptr(), std::ptr::null_mut()) })?;
+    Ok(verdict)
+}
+
 /// How provers of ONE proof made from now on are shared between threads (`uzk_coalesce_config`): the library runs round calls of
 /// several threads that stand at the same round of proofs over the same circuit as one lockstep launch sequence.  On by default
 /// (at most 8 proofs per sequence, the provers at work spread over 4 sequences, 2000 us gathering wait -- include/uzkge_gpu.h; 0 = a default);

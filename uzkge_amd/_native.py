@@ -134,6 +134,12 @@ PROTOTYPES = {
     "uzk_g16_verify_fold": (_I, [_U64, _P, _P, ctypes.c_uint32, _P, _P, _P, _P, _P, _P, _P]),
     "uzk_pairing_product": (_I, [_P, _P, ctypes.c_uint32, _P, ctypes.POINTER(ctypes.c_int)]),
     "uzk_g16_verify_batch": (_I, [_U64, _P, _P, ctypes.c_uint32, _P, _P, _P, ctypes.POINTER(ctypes.c_int)]),
+    "uzk_ed_check_points": (_I, [_P, _SZ, _P]),
+    "uzk_ed_mul_batch": (_I, [_P, _SZ, _P, _SZ, _P]),
+    "uzk_ed_sum_batch": (_I, [_P, ctypes.c_uint32, ctypes.c_uint32, _P]),
+    "uzk_ed_unmask_batch": (_I, [_P, _P, ctypes.c_uint32, ctypes.c_uint32, _P]),
+    "uzk_cp_reveal_prove_batch": (_I, [_P, _P, _P, ctypes.c_uint32, _P, _P, _P]),
+    "uzk_cp_reveal_verify_batch": (_I, [_P, _P, ctypes.c_uint32, _P, _P]),
     "uzk_synth_points_arith": (_I, [_P, _SZ, _P]),
     "uzk_synth_points_random": (_I, [_P, _SZ, _U64]),
     "uzk_synth_scalars": (_I, [_P, _SZ, _U64]),
@@ -276,6 +282,9 @@ G16_VERIFY_MAX_BATCH = 4096
 G16_VERIFY_MAX_INPUTS = 1024
 G16_PROOF_BYTES = 256
 PAIRING_MAX_PAIRS = 4099
+CP_PROOF_BYTES = 160
+CP_MAX_BATCH = 65536
+ED_MAX_BATCH = 1 << 20
 
 
 class G16VkDesc(ctypes.Structure):

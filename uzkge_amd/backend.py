@@ -1103,6 +1103,82 @@ def pairing_product(p, q, want_gt: bool = True):
     return gt, bool(one.value)
 
 
+def _u8(blobs, size: int) -> np.ndarray:
+    raw = np.frombuffer(bytes(blobs), dtype=np.uint8) if isinstance(blobs, (bytes, bytearray)) else np.ascontiguousarray(blobs, dtype=np.uint8)
+    assert raw.size % size == 0, "a whole number of %d-byte blobs" % size
+    return raw.reshape(-1)
+
+
+def ed_check_points(points) -> np.ndarray:
+    """uzk_ed_check_points: points [n, 8] (x then y, Montgomery words).  Returns status [n]: 0 in the prime subgroup, 1 a coordinate
+    word >= q, 2 off the curve, 3 on the curve outside the subgroup."""
+    p = np.ascontiguousarray(points, dtype=np.uint64).reshape(-1, 8)
+    status = np.zeros(max(p.shape[0], 1), dtype=np.uint8)
+    check(lib.uzk_ed_check_points(_ptr(p), p.shape[0], status.ctypes.data_as(ctypes.c_void_p)))
+    return status[:p.shape[0]]
+
+
+def ed_mul_batch(points, scalars) -> np.ndarray:
+    """uzk_ed_mul_batch: scalars [n, 4] plain 256-bit integers (little-endian words); points [n, 8], or one point [8] shared by every
+    item.  Returns [n, 8] canonical affine points."""
+    s = np.ascontiguousarray(scalars, dtype=np.uint64).reshape(-1, 4)
+    p = np.ascontiguousarray(points, dtype=np.uint64)
+    shared = p.size == 8 and p.ndim == 1
+    p = p.reshape(-1, 8)
+    assert shared or p.shape[0] == s.shape[0], "one point per scalar, or one point [8] for all"
+    out = np.zeros((max(s.shape[0], 1), 8), dtype=np.uint64)
+    check(lib.uzk_ed_mul_batch(_ptr(p), 0 if shared else 1, _ptr(s), s.shape[0], _ptr(out)))
+    return out[:s.shape[0]]
+
+
+def ed_sum_batch(rows) -> np.ndarray:
+    """uzk_ed_sum_batch: rows [k, n, 8].  Returns [n, 8]: the sum over the k rows, card by card."""
+    r = np.ascontiguousarray(rows, dtype=np.uint64)
+    assert r.ndim == 3 and r.shape[2] == 8, "rows [k, n, 8]"
+    out = np.zeros((max(r.shape[1], 1), 8), dtype=np.uint64)
+    check(lib.uzk_ed_sum_batch(_ptr(r), r.shape[0], r.shape[1], _ptr(out)))
+    return out[:r.shape[1]]
+
+
+def ed_unmask_batch(e2, reveals) -> np.ndarray:
+    """uzk_ed_unmask_batch: e2 [n, 8], reveals [k, n, 8].  Returns [n, 8]: e2_j minus the k reveals of card j."""
+    r = np.ascontiguousarray(reveals, dtype=np.uint64)
+    assert r.ndim == 3 and r.shape[2] == 8, "reveals [k, n, 8]"
+    e = np.ascontiguousarray(e2, dtype=np.uint64).reshape(-1, 8)
+    assert e.shape[0] == r.shape[1], "one e2 per card"
+    out = np.zeros((max(r.shape[1], 1), 8), dtype=np.uint64)
+    check(lib.uzk_ed_unmask_batch(_ptr(e), _ptr(r), r.shape[0], r.shape[1], _ptr(out)))
+    return out[:r.shape[1]]
+
+
+def cp_reveal_prove_batch(sk, e1, omegas):
+    """uzk_cp_reveal_prove_batch: sk [4] and omegas [m, 4] plain integers below L, e1 [m, 8] subgroup points.  Returns
+    (reveal [m, 8], pk [8], proofs: uint8 [m, 160])."""
+    k = np.ascontiguousarray(sk, dtype=np.uint64).reshape(4)
+    p = np.ascontiguousarray(e1, dtype=np.uint64).reshape(-1, 8)
+    w = np.ascontiguousarray(omegas, dtype=np.uint64).reshape(-1, 4)
+    assert p.shape[0] == w.shape[0], "one omega per card"
+    m = p.shape[0]
+    reveal, pk = np.zeros((max(m, 1), 8), dtype=np.uint64), np.zeros(8, dtype=np.uint64)
+    proofs = np.zeros((max(m, 1), N.CP_PROOF_BYTES), dtype=np.uint8)
+    check(lib.uzk_cp_reveal_prove_batch(_ptr(k), _ptr(p), _ptr(w), m, _ptr(reveal), _ptr(pk), proofs.ctypes.data_as(ctypes.c_void_p)))
+    return reveal[:m], pk, proofs[:m]
+
+
+def cp_reveal_verify_batch(statements, proofs, want_challenges: bool = False):
+    """uzk_cp_reveal_verify_batch: statements [m, 6, 4] (e1, reveal, pk: x and y each -- the public signals of the Groth16 reveal proof
+    of the same statement), proofs m blobs of 160 bytes.  Returns verdict [m] (0 accepted, 1 .. 5 the first failing check), and with
+    want_challenges also c [m, 4] as plain integers."""
+    raw = _u8(proofs, N.CP_PROOF_BYTES)
+    m = raw.size // N.CP_PROOF_BYTES
+    st = np.ascontiguousarray(statements, dtype=np.uint64).reshape(m, 6, 4)
+    verdict = np.zeros(max(m, 1), dtype=np.uint8)
+    ch = np.zeros((max(m, 1), 4), dtype=np.uint64) if want_challenges else None
+    vp = lambda arr: arr.ctypes.data_as(ctypes.c_void_p)
+    check(lib.uzk_cp_reveal_verify_batch(_ptr(st), vp(raw), m, vp(verdict), _ptr(ch) if want_challenges else None))
+    return (verdict[:m], ch[:m]) if want_challenges else verdict[:m]
+
+
 def fq12_kat(op: int, a, b=None) -> np.ndarray:
     """uzk_test_fq12_kat (test hook): a, b [n, 6, 2, 4] wire elements of Fq12."""
     x = np.ascontiguousarray(a, dtype=np.uint64).reshape(-1, 6, 2, 4)

@@ -230,6 +230,7 @@ static void ctx_release(Ctx& c) {
     g16_free(c);
     c.verify_ws.release();
     c.g16v_ws.release();
+    c.ed_ws.release();
     c.pairing_ws.release();
     msm_free(c);
     poly_free(c);
@@ -1423,6 +1424,77 @@ int uzk_g16_verify_batch(uint64_t vk, const uint8_t* proofs, const uint64_t* pub
     *accepted_out = ok ? 1 : 0;
     return UZK_OK;
 } catch (...) { return uzk::on_exception("uzk_g16_verify_batch"); }
+
+/* ---- Baby Jubjub and the Chaum-Pedersen reveal proofs ------------------------------------------- */
+static const EdAffine* as_ed(const uint64_t* p) { return reinterpret_cast<const EdAffine*>(p); }
+static EdAffine* as_ed(uint64_t* p) { return reinterpret_cast<EdAffine*>(p); }
+// the callers' points enter the lazy limbs as canonical words: anything else is refused before the device is touched
+static int ed_require_canonical(const char* who, const char* what, const uint64_t* words, size_t points) {
+    const size_t bad = ed_first_noncanonical(as_fp(words), 2 * points);
+    if (bad < 2 * points) { set_error("%s: %s[%zu]: the %c coordinate is not below q", who, what, bad / 2, bad % 2 ? 'y' : 'x'); return UZK_ERR_PARAMETER; }
+    return UZK_OK;
+}
+
+int uzk_ed_check_points(const uint64_t* points_mont, size_t n, uint8_t* status_out) try {
+    API_LOCK;
+    if (n == 0 || n > UZK_ED_MAX_BATCH) { set_error("uzk_ed_check_points: %zu points (1 .. %d per call)", n, UZK_ED_MAX_BATCH); return UZK_ERR_PARAMETER; }
+    if (!points_mont || !status_out) { set_error("uzk_ed_check_points: null pointer"); return UZK_ERR_PARAMETER; }
+    UZK_TRY(require_ready());
+    return ed_check_run(ctx(), as_ed(points_mont), n, status_out);
+} catch (...) { return uzk::on_exception("uzk_ed_check_points"); }
+
+int uzk_ed_mul_batch(const uint64_t* points_mont, size_t point_stride, const uint64_t* scalars, size_t n, uint64_t* out_mont) try {
+    API_LOCK;
+    if (n == 0 || n > UZK_ED_MAX_BATCH) { set_error("uzk_ed_mul_batch: %zu items (1 .. %d per call)", n, UZK_ED_MAX_BATCH); return UZK_ERR_PARAMETER; }
+    if (point_stride > 1) { set_error("uzk_ed_mul_batch: point stride %zu (0: one shared base, 1: a base per item)", point_stride); return UZK_ERR_PARAMETER; }
+    if (!points_mont || !scalars || !out_mont) { set_error("uzk_ed_mul_batch: null pointer"); return UZK_ERR_PARAMETER; }
+    UZK_TRY(ed_require_canonical("uzk_ed_mul_batch", "points", points_mont, point_stride ? n : 1));
+    UZK_TRY(require_ready());
+    return ed_mul_run(ctx(), as_ed(points_mont), point_stride == 0, as_fp(scalars), n, as_ed(out_mont));
+} catch (...) { return uzk::on_exception("uzk_ed_mul_batch"); }
+
+int uzk_ed_sum_batch(const uint64_t* rows_mont, uint32_t k, uint32_t n, uint64_t* out_mont) try {
+    API_LOCK;
+    if (k == 0 || k > UZK_ED_MAX_ROWS || n == 0 || n > UZK_ED_MAX_BATCH) {
+        set_error("uzk_ed_sum_batch: %u rows of %u points (1 .. %d rows of 1 .. %d)", k, n, UZK_ED_MAX_ROWS, UZK_ED_MAX_BATCH);
+        return UZK_ERR_PARAMETER;
+    }
+    if (!rows_mont || !out_mont) { set_error("uzk_ed_sum_batch: null pointer"); return UZK_ERR_PARAMETER; }
+    UZK_TRY(ed_require_canonical("uzk_ed_sum_batch", "rows", rows_mont, (size_t)k * n));
+    UZK_TRY(require_ready());
+    return ed_sum_run(ctx(), nullptr, as_ed(rows_mont), k, n, as_ed(out_mont));
+} catch (...) { return uzk::on_exception("uzk_ed_sum_batch"); }
+
+int uzk_ed_unmask_batch(const uint64_t* e2_mont, const uint64_t* reveals_mont, uint32_t k, uint32_t n, uint64_t* out_mont) try {
+    API_LOCK;
+    if (k == 0 || k > UZK_ED_MAX_ROWS || n == 0 || n > UZK_ED_MAX_BATCH) {
+        set_error("uzk_ed_unmask_batch: %u rows of %u points (1 .. %d rows of 1 .. %d)", k, n, UZK_ED_MAX_ROWS, UZK_ED_MAX_BATCH);
+        return UZK_ERR_PARAMETER;
+    }
+    if (!e2_mont || !reveals_mont || !out_mont) { set_error("uzk_ed_unmask_batch: null pointer"); return UZK_ERR_PARAMETER; }
+    UZK_TRY(ed_require_canonical("uzk_ed_unmask_batch", "e2", e2_mont, n));
+    UZK_TRY(ed_require_canonical("uzk_ed_unmask_batch", "reveals", reveals_mont, (size_t)k * n));
+    UZK_TRY(require_ready());
+    return ed_sum_run(ctx(), as_ed(e2_mont), as_ed(reveals_mont), k, n, as_ed(out_mont));
+} catch (...) { return uzk::on_exception("uzk_ed_unmask_batch"); }
+
+int uzk_cp_reveal_prove_batch(const uint64_t* sk, const uint64_t* e1_mont, const uint64_t* omegas, uint32_t m, uint64_t* reveal_out, uint64_t* pk_out,
+                              uint8_t* proofs_out) try {
+    API_LOCK;
+    if (m == 0 || m > UZK_CP_MAX_BATCH) { set_error("uzk_cp_reveal_prove_batch: %u cards (1 .. %d per call)", m, UZK_CP_MAX_BATCH); return UZK_ERR_PARAMETER; }
+    if (!sk || !e1_mont || !omegas || !reveal_out || !pk_out || !proofs_out) { set_error("uzk_cp_reveal_prove_batch: null pointer"); return UZK_ERR_PARAMETER; }
+    UZK_TRY(ed_require_canonical("uzk_cp_reveal_prove_batch", "e1", e1_mont, m));
+    UZK_TRY(require_ready());
+    return cp_prove_run(ctx(), as_fp(sk), as_ed(e1_mont), as_fp(omegas), m, as_ed(reveal_out), as_ed(pk_out), proofs_out);
+} catch (...) { return uzk::on_exception("uzk_cp_reveal_prove_batch"); }
+
+int uzk_cp_reveal_verify_batch(const uint64_t* statements_mont, const uint8_t* proofs, uint32_t m, uint8_t* verdict_out, uint64_t* challenges_out) try {
+    API_LOCK;
+    if (m == 0 || m > UZK_CP_MAX_BATCH) { set_error("uzk_cp_reveal_verify_batch: %u proofs (1 .. %d per call)", m, UZK_CP_MAX_BATCH); return UZK_ERR_PARAMETER; }
+    if (!statements_mont || !proofs || !verdict_out) { set_error("uzk_cp_reveal_verify_batch: null pointer"); return UZK_ERR_PARAMETER; }
+    UZK_TRY(require_ready());
+    return cp_verify_run(ctx(), as_ed(statements_mont), proofs, m, verdict_out, reinterpret_cast<Fp*>(challenges_out));
+} catch (...) { return uzk::on_exception("uzk_cp_reveal_verify_batch"); }
 
 int uzk_test_fq12_kat(int op, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n) try {
     API_LOCK;

@@ -151,6 +151,8 @@ struct Ctx {
     // pairing.hip: one block carved into the arrays of a pairing product (constants, points, statuses, the tree's two levels)
     DevBuf pairing_ws;
     std::vector<uint8_t> pairing_status;   // the statuses of a product's pairs on the host (grow-only)
+    // edwards.hip: one block carved into the arrays of a Baby Jubjub call (points, scalars, proofs, statuses, results)
+    DevBuf ed_ws;
     int tune_verify_transcript = 0;   // which transcript kernel a fold runs: 1 one proof per lane; 0 / 2 a proof's state spread over a half wave (the default)
     // an entry of the process-wide SRS registry
     struct Srs {
@@ -302,6 +304,14 @@ int pairing_miller_device(Ctx& c, const Affine* p, const G2Affine* q, uint32_t n
 // g16verify.hip: the fold, then the product of its M + 3 pairs without leaving the device (g2: beta, gamma, delta on the host)
 int g16v_verify_run(Ctx& c, uint64_t h, const uint8_t* proofs, const Fp* pub, uint32_t m, const Fp* weights, const G2Affine* g2, uint8_t* status_out,
                     Fq12w* gt_out, uint32_t* bad_g2_out);
+// edwards.hip: Baby Jubjub -- point classification, scalar multiplications, sums, and the Chaum-Pedersen reveal proofs over it
+struct EdAffine;
+size_t ed_first_noncanonical(const Fp* words, size_t count);
+int ed_check_run(Ctx& c, const EdAffine* pts, size_t n, uint8_t* status_out);
+int ed_mul_run(Ctx& c, const EdAffine* pts, bool shared_base, const Fp* scalars, size_t n, EdAffine* out);
+int ed_sum_run(Ctx& c, const EdAffine* e2, const EdAffine* rows, uint32_t k, uint32_t n, EdAffine* out);
+int cp_verify_run(Ctx& c, const EdAffine* statements, const uint8_t* proofs, uint32_t m, uint8_t* verdict_out, Fp* challenges_out);
+int cp_prove_run(Ctx& c, const Fp* sk, const EdAffine* e1, const Fp* omegas, uint32_t m, EdAffine* reveal_out, EdAffine* pk_out, uint8_t* proofs_out);
 void msm_plan_info(Ctx& c, size_t n, int* window_bits, int* windows);
 int msm_run(Ctx& c, const Affine* points, const ScalarView& scalars, size_t n, uint32_t batch, Jac* out_host, int pre_c,
             uint32_t pre_stride, uint32_t pre_off);

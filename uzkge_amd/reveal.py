@@ -1,0 +1,97 @@
+"""The plain reveal path of a zshuffle game over arrays of cards, with the reference's names (shuffle/src/reveal.rs, keygen.rs;
+RevealVerifier.sol): every function is one call of the Baby Jubjub layer of the C ABI (include/uzkge_gpu.h, uzk_ed_* / uzk_cp_reveal_*).
+
+Points are affine integer pairs (x, y) below q, the identity is (0, 1); a masked card is (e1, e2); secrets and omegas are integers below
+the subgroup order L; a proof is the 160 bytes of ChaumPedersenDLProof::to_uncompress.  The library draws no randomness: the caller
+supplies one omega per card, as it supplies the fold weights of the batch verifiers."""
+from __future__ import annotations
+
+from typing import List, Sequence, Tuple
+
+import numpy as np
+
+from . import _native as N
+from . import backend as b
+
+Q = 21888242871839275222246405745257275088548364400416034343698204186575808495617
+L = 2736030358979909402780800718157159386076813972158567259200215660948447373041
+GENERATOR = (0x2B8CFD91B905CAE31D41E7DEDF4A927EE3BC429AAD7E344D59D2810D82876C32, 0x2AAA6C24A758209E90ACED1F10277B762A7C1115DBC0E16AC276FC2C671A861F)
+_R = (1 << 256) % Q
+_R_INV = pow(_R, -1, Q)
+_MASK = (1 << 64) - 1
+
+Point = Tuple[int, int]
+
+
+def _words(v: int) -> List[int]:
+    return [(v >> (64 * k)) & _MASK for k in range(4)]
+
+
+def points_to_wire(points: Sequence[Point]) -> np.ndarray:
+    """[n, 8]: x then y, Montgomery words"""
+    out = np.zeros((len(points), 8), dtype=np.uint64)
+    for i, (x, y) in enumerate(points):
+        if not (0 <= x < Q and 0 <= y < Q):
+            raise ValueError("point %d: a coordinate is not below q" % i)
+        out[i] = _words(x * _R % Q) + _words(y * _R % Q)
+    return out
+
+
+def points_from_wire(wire: np.ndarray) -> List[Point]:
+    w = np.asarray(wire, dtype=np.uint64).reshape(-1, 2, 4)
+    val = lambda r: sum(int(r[k]) << (64 * k) for k in range(4)) * _R_INV % Q
+    return [(val(p[0]), val(p[1])) for p in w]
+
+
+def scalars_to_wire(scalars: Sequence[int]) -> np.ndarray:
+    """[n, 4]: plain 256-bit integers, little-endian words"""
+    out = np.zeros((len(scalars), 4), dtype=np.uint64)
+    for i, s in enumerate(scalars):
+        if not 0 <= s < (1 << 256):
+            raise ValueError("scalar %d does not fit 256 bits" % i)
+        out[i] = _words(s)
+    return out
+
+
+def statements_to_wire(pks: Sequence[Point], e1s: Sequence[Point], reveal_cards: Sequence[Point]) -> np.ndarray:
+    """[m, 6, 4]: e1, reveal, pk -- also the public signals of the Groth16 reveal proof of the same statement"""
+    rows = [p for e1, rv, pk in zip(e1s, reveal_cards, pks) for p in (e1, rv, pk)]
+    return points_to_wire(rows).reshape(len(e1s), 6, 4)
+
+
+def keypair_public(sks: Sequence[int]) -> List[Point]:
+    """pk = sk G for every secret"""
+    return points_from_wire(b.ed_mul_batch(points_to_wire([GENERATOR])[0], scalars_to_wire(sks)))
+
+
+def aggregate_keys(pks: Sequence[Point]) -> Point:
+    """the joint key: the sum of the players' keys (RevealVerifier.aggregateKeys)"""
+    return points_from_wire(b.ed_sum_batch(points_to_wire(pks).reshape(len(pks), 1, 8)))[0]
+
+
+def reveal(sk: int, masked_cards: Sequence[Tuple[Point, Point]], omegas: Sequence[int]):
+    """One player's reveals of the masked cards (e1, e2): (reveal cards, proofs, pk).  omegas: one fresh uniform integer below L per
+    card, drawn by the caller and never reused."""
+    if len(omegas) != len(masked_cards):
+        raise ValueError("one omega per card")
+    rv, pk, proofs = b.cp_reveal_prove_batch(scalars_to_wire([sk])[0], points_to_wire([c[0] for c in masked_cards]), scalars_to_wire(omegas))
+    return points_from_wire(rv), [bytes(p) for p in proofs], points_from_wire(pk)[0]
+
+
+def verify_reveal(pks: Sequence[Point], masked_cards: Sequence[Tuple[Point, Point]], reveal_cards: Sequence[Point], proofs: Sequence[bytes]) -> List[int]:
+    """The verdict of every (pk, masked card, reveal card, proof): 0 accepted, else the first failing check (uzk_cp_reveal_verify_batch)."""
+    if not len(pks) == len(masked_cards) == len(reveal_cards) == len(proofs):
+        raise ValueError("one key, one masked card and one proof per reveal card")
+    if any(len(p) != N.CP_PROOF_BYTES for p in proofs):
+        raise ValueError("a proof is %d bytes" % N.CP_PROOF_BYTES)
+    st = statements_to_wire(pks, [c[0] for c in masked_cards], reveal_cards)
+    return [int(v) for v in b.cp_reveal_verify_batch(st, b"".join(proofs))]
+
+
+def unmask(masked_cards: Sequence[Tuple[Point, Point]], reveal_cards: Sequence[Sequence[Point]]) -> List[Point]:
+    """card_j = e2_j minus every player's reveal of card j; reveal_cards[k][j] is player k's reveal of card j"""
+    n = len(masked_cards)
+    if any(len(row) != n for row in reveal_cards):
+        raise ValueError("every player reveals every card")
+    rows = np.stack([points_to_wire(row) for row in reveal_cards])
+    return points_from_wire(b.ed_unmask_batch(points_to_wire([c[1] for c in masked_cards]), rows))
