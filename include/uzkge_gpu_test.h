@@ -91,9 +91,29 @@ int uzk_test_srs_weights_device(const uint8_t seed[32], uint64_t count, uint64_t
 int uzk_test_fq12_kat(int op, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n);
 /* The n Miller-loop values of the pairs, before the product and the final exponentiation (no point is checked). */
 int uzk_test_miller(const uzk_g1_affine* p, const uzk_g2_affine* q, uint32_t n, uzk_gt* out);
+/* Fq12 on RAW limbs, one element per lane group as above.  An element is 108 words: the coefficient of w^0 first, each c0 then c1 of 9
+ * limbs, taken EXACTLY as given (nothing re-limbed or reduced) as members of q12::El = E2<1, 2> (2^261-form, low limbs below
+ * 2^29 + 2^6, value < 2 M).  Record i of in is two elements a, b (216 words); out[i] is one element, raw (no to_wire, no canon).
+ * op 0..10 as uzk_test_fq12_kat; 11 xi_mul of every coefficient of a; 12 q2::to_wire of every coefficient of a: eight canonical
+ * words per component, the ninth 0. */
+int uzk_test_fq12_raw_kat(int op, const uint32_t* in, uint32_t* out, size_t n);
+/* One step of the Miller loop on RAW limbs, one record per lane group.  Record i of in (108 words): T = x, y, z and Q = qx, qy (each c0
+ * then c1 of 9 limbs, members of E2<1, 2>), then xP and -yP (9 limbs each, members of Lz<Fq29, 1, 4>); 3 b' is the library's own
+ * constant.  The hook fills the group's block of the LDS as the Miller kernel does (Q, 3 b', xP, -yP, then the barrier).  op 0
+ * dbl_step, 1 add_step.  out[i] (126 words): x, y, z, l0, l1, l3 of the group's lane 0, raw, then 18 words holding the OR over the
+ * other five coefficient lanes (and the six values) of their result XOR lane 0's: every lane computes the same step, so they are 0. */
+int uzk_test_miller_step_raw(int op, const uint32_t* in, uint32_t* out, size_t n);
 /* how the Miller kernel is laid out: pairs per wave = pairs per workgroup (a workgroup is one wave); the product tree's radix */
 #define UZK_PAIRING_PAIRS_PER_WAVE 8
 #define UZK_PAIRING_TREE_RADIX 8
+
+/* ---- Baby Jubjub (csrc/ed29.hpp, edwards.hip) ----
+ * The group law of ed29.hpp on RAW limbs, one record per lane.  A point is 36 words: x, y, z, t of 9 limbs each, taken EXACTLY as given
+ * (nothing re-limbed or reduced) as members of ed::C = Lz<Fr29, 1, 2> (2^261-form, low limbs below 2^29 + 2^6, value < 2 M).  Record i of
+ * in is two points a, b (72 words); out[i] is one point, raw, and a flag word (37 words).  op: 0 add(a, b); 1 neg(a); 2 is_identity(a),
+ * 3 eq_affine(a, b.x, b.y), 4 on_curve(a.x, a.y): the answer in the flag, the point zero; 5 to_affine(a): the eight canonical wire words
+ * of x and of y, the ninth 0, z and t zero; 6 inv(a.x), raw, in x. */
+int uzk_test_ed_raw_kat(int op, const uint32_t* in, uint32_t* out, size_t n);
 
 /* ---- synthetic circuits ----
  * TEST / TIMING ONLY -- changes results.  Marks the circuit as synthetic (random polynomials no witness satisfies, the frozen

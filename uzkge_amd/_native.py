@@ -171,6 +171,9 @@ TEST_PROTOTYPES = {
     "uzk_test_keccak256": (_I, [_P, _P, ctypes.c_uint32, _P]),
     "uzk_test_fq12_kat": (_I, [_I, _P, _P, _P, _SZ]),
     "uzk_test_miller": (_I, [_P, _P, ctypes.c_uint32, _P]),
+    "uzk_test_fq12_raw_kat": (_I, [_I, _P, _P, _SZ]),
+    "uzk_test_miller_step_raw": (_I, [_I, _P, _P, _SZ]),
+    "uzk_test_ed_raw_kat": (_I, [_I, _P, _P, _SZ]),
     "uzk_test_srs_weights_device": (_I, [_P, _U64, _P]),
     "uzk_test_lanes": (_I, [_I, _P, _P, ctypes.c_uint32, _P, _P, _P, ctypes.c_uint32, _U64, _P, ctypes.POINTER(ctypes.c_int)]),
 }

@@ -686,6 +686,28 @@ def g2_raw_op(op: int, records: np.ndarray) -> np.ndarray:
     return out
 
 
+def _raw_hook(fn, op: int, records: np.ndarray, w_in: int, w_out: int) -> np.ndarray:
+    x = np.ascontiguousarray(records, dtype=np.uint32).reshape(-1, w_in)
+    out = np.zeros((x.shape[0], w_out), dtype=np.uint32)
+    check(fn(op, x.ctypes.data_as(ctypes.c_void_p), out.ctypes.data_as(ctypes.c_void_p), x.shape[0]))
+    return out
+
+
+def fq12_raw_op(op: int, records: np.ndarray) -> np.ndarray:
+    """uzk_test_fq12_raw_kat: [n, 216] uint32 records (two raw Fq12 elements of 108 words) -> [n, 108] raw elements"""
+    return _raw_hook(lib.uzk_test_fq12_raw_kat, op, records, 216, 108)
+
+
+def miller_step_raw(op: int, records: np.ndarray) -> np.ndarray:
+    """uzk_test_miller_step_raw: [n, 108] uint32 records (T, Q, xP, -yP raw) -> [n, 126] (x, y, z, l0, l1, l3 raw, lane differences)"""
+    return _raw_hook(lib.uzk_test_miller_step_raw, op, records, 108, 126)
+
+
+def ed_raw_op(op: int, records: np.ndarray) -> np.ndarray:
+    """uzk_test_ed_raw_kat: [n, 72] uint32 records (two raw extended points of 36 words) -> [n, 37] (a raw point and a flag)"""
+    return _raw_hook(lib.uzk_test_ed_raw_kat, op, records, 72, 37)
+
+
 def profile_enable(on: bool) -> None:
     check(lib.uzk_profile_enable(int(on)))
 

@@ -1772,6 +1772,27 @@ int uzk_test_g2_raw_kat(int op, const uint32_t* in, uint32_t* out, size_t n) try
     UZK_TRY(require_ready());
     return g2_raw_op_device(ctx(), op, in, out, n);
 } catch (...) { return uzk::on_exception("uzk_test_g2_raw_kat"); }
+int uzk_test_fq12_raw_kat(int op, const uint32_t* in, uint32_t* out, size_t n) try {
+    API_LOCK;
+    if (n > (1u << 20) || (n > 0 && (!in || !out))) { set_error("uzk_test_fq12_raw_kat: null pointer or more than 2^20 elements"); return UZK_ERR_PARAMETER; }
+    if (op < 0 || op > 12) { set_error("uzk_test_fq12_raw_kat: bad op"); return UZK_ERR_PARAMETER; }
+    UZK_TRY(require_ready());
+    return pairing_raw_kat_device(ctx(), op, in, out, (uint32_t)n);
+} catch (...) { return uzk::on_exception("uzk_test_fq12_raw_kat"); }
+int uzk_test_miller_step_raw(int op, const uint32_t* in, uint32_t* out, size_t n) try {
+    API_LOCK;
+    if (n > (1u << 20) || (n > 0 && (!in || !out))) { set_error("uzk_test_miller_step_raw: null pointer or more than 2^20 records"); return UZK_ERR_PARAMETER; }
+    if (op < 0 || op > 1) { set_error("uzk_test_miller_step_raw: bad op"); return UZK_ERR_PARAMETER; }
+    UZK_TRY(require_ready());
+    return pairing_raw_step_device(ctx(), op, in, out, (uint32_t)n);
+} catch (...) { return uzk::on_exception("uzk_test_miller_step_raw"); }
+int uzk_test_ed_raw_kat(int op, const uint32_t* in, uint32_t* out, size_t n) try {
+    API_LOCK;
+    if (n > 0 && (!in || !out)) { set_error("uzk_test_ed_raw_kat: null pointer"); return UZK_ERR_PARAMETER; }
+    if (op < 0 || op > 6) { set_error("uzk_test_ed_raw_kat: bad op"); return UZK_ERR_PARAMETER; }
+    UZK_TRY(require_ready());
+    return ed_raw_op_device(ctx(), op, in, out, n);
+} catch (...) { return uzk::on_exception("uzk_test_ed_raw_kat"); }
 int uzk_test_lanes(int op, const void* const* d_polys, const uint64_t* lane_strides, uint32_t count, const uint32_t* lens, const uint32_t* pts,
                    const uint64_t* args, uint32_t lanes, uint64_t len, uint64_t* out, int* kernel) try {
     API_LOCK;

@@ -301,6 +301,8 @@ int pairing_product_run(Ctx& c, const Affine* p, const G2Affine* q, bool on_devi
 bool gt_is_one(const Fq12w& a);
 int pairing_kat_device(Ctx& c, int op, const Fq12w* a, const Fq12w* b, Fq12w* out, uint32_t n);
 int pairing_miller_device(Ctx& c, const Affine* p, const G2Affine* q, uint32_t n, Fq12w* out);
+int pairing_raw_kat_device(Ctx& c, int op, const uint32_t* in, uint32_t* out, uint32_t n);
+int pairing_raw_step_device(Ctx& c, int op, const uint32_t* in, uint32_t* out, uint32_t n);
 // g16verify.hip: the fold, then the product of its M + 3 pairs without leaving the device (g2: beta, gamma, delta on the host)
 int g16v_verify_run(Ctx& c, uint64_t h, const uint8_t* proofs, const Fp* pub, uint32_t m, const Fp* weights, const G2Affine* g2, uint8_t* status_out,
                     Fq12w* gt_out, uint32_t* bad_g2_out);
@@ -312,6 +314,7 @@ int ed_mul_run(Ctx& c, const EdAffine* pts, bool shared_base, const Fp* scalars,
 int ed_sum_run(Ctx& c, const EdAffine* e2, const EdAffine* rows, uint32_t k, uint32_t n, EdAffine* out);
 int cp_verify_run(Ctx& c, const EdAffine* statements, const uint8_t* proofs, uint32_t m, uint8_t* verdict_out, Fp* challenges_out);
 int cp_prove_run(Ctx& c, const Fp* sk, const EdAffine* e1, const Fp* omegas, uint32_t m, EdAffine* reveal_out, EdAffine* pk_out, uint8_t* proofs_out);
+int ed_raw_op_device(Ctx& c, int op, const uint32_t* in, uint32_t* out, size_t n);
 void msm_plan_info(Ctx& c, size_t n, int* window_bits, int* windows);
 int msm_run(Ctx& c, const Affine* points, const ScalarView& scalars, size_t n, uint32_t batch, Jac* out_host, int pre_c,
             uint32_t pre_stride, uint32_t pre_off);

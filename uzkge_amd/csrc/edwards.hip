@@ -189,6 +189,72 @@ __global__ __launch_bounds__(kEdBlock) void cp_prove_mul_kernel(const EdAffine* 
 #endif
 }
 
+// The group law on RAW limbs (uzk_test_ed_raw_kat): coordinates are taken exactly as given -- nothing is re-limbed or reduced on the way
+// in, nothing canonicalised on the way out -- so a test can put every coordinate at the edge of ed::C's bound.
+struct EdRawPt {
+    uint32_t c[4][9];                  // x, y, z, t, nine limbs each (op 5 out: eight wire words of x and y, the ninth 0)
+};
+struct EdRawIn {
+    EdRawPt a, b;
+};
+struct EdRawOut {
+    EdRawPt p;
+    uint32_t flag;
+};
+
+#if defined(__HIP_DEVICE_COMPILE__)
+__device__ __forceinline__ ed::C edraw_c(const uint32_t (&c)[9]) {
+    ed::C r;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) r.v.l[i] = c[i];
+    return r;
+}
+__device__ __forceinline__ void edraw_put(uint32_t (&c)[9], const ed::C& x) {
+#pragma unroll
+    for (int i = 0; i < 9; ++i) c[i] = x.v.l[i];
+}
+__device__ __forceinline__ void edraw_put_wire(uint32_t (&c)[9], const Fp& w) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) c[i] = w.v[i];
+    c[8] = 0;
+}
+__device__ __forceinline__ ed::P edraw_point(const EdRawPt& r) {
+    ed::P p;
+    p.x = edraw_c(r.c[0]); p.y = edraw_c(r.c[1]); p.z = edraw_c(r.c[2]); p.t = edraw_c(r.c[3]);
+    return p;
+}
+__device__ __forceinline__ void edraw_put_point(EdRawPt& r, const ed::P& p) {
+    edraw_put(r.c[0], p.x); edraw_put(r.c[1], p.y); edraw_put(r.c[2], p.z); edraw_put(r.c[3], p.t);
+}
+#endif
+
+// op 0 add(a, b), 1 neg(a), 2 is_identity(a), 3 eq_affine(a, b.x, b.y), 4 on_curve(a.x, a.y) (the answers in out.flag), 5 to_affine(a) as
+// wire words, 6 inv(a.x)
+__global__ __launch_bounds__(kEdBlock) void ed_raw_kat_kernel(int op, const EdRawIn* __restrict__ in, EdRawOut* __restrict__ out, size_t n) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    const size_t i = (size_t)blockIdx.x * kEdBlock + threadIdx.x;
+    if (i >= n) return;
+    const EdRawIn rec = in[i];
+    EdRawOut r;
+    for (int k = 0; k < 4; ++k)
+        for (int l = 0; l < 9; ++l) r.p.c[k][l] = 0;
+    r.flag = 0;
+    const ed::P a = edraw_point(rec.a);
+    if (op == 0) edraw_put_point(r.p, ed::add(a, edraw_point(rec.b)));
+    else if (op == 1) edraw_put_point(r.p, ed::neg(a));
+    else if (op == 2) r.flag = ed::is_identity(a);
+    else if (op == 3) r.flag = ed::eq_affine(a, edraw_c(rec.b.c[0]), edraw_c(rec.b.c[1]));
+    else if (op == 4) r.flag = ed::on_curve(a.x, a.y);
+    else if (op == 5) {
+        const EdAffine w = ed::to_affine(a);
+        edraw_put_wire(r.p.c[0], w.x); edraw_put_wire(r.p.c[1], w.y);
+    } else {
+        edraw_put(r.p.c[0], ed::inv(a.x));
+    }
+    out[i] = r;
+#endif
+}
+
 // ---- host side ------------------------------------------------------------------------------------------------------------------
 static size_t ed_align(size_t v) { return (v + 255) & ~(size_t)255; }
 static unsigned ed_grid(size_t lanes) { return (unsigned)((lanes + kEdBlock - 1) / kEdBlock); }
@@ -334,6 +400,27 @@ int cp_prove_run(Ctx& c, const Fp* sk, const EdAffine* e1, const Fp* omegas, uin
     UZK_HIP(hipMemcpyAsync(pk_out, d_pk, sizeof(EdAffine), hipMemcpyDeviceToHost, c.stream));
     UZK_HIP(hipMemcpyAsync(proofs_out, d_proofs, (size_t)m * UZK_CP_PROOF_BYTES, hipMemcpyDeviceToHost, c.stream));
     UZK_HIP(hipStreamSynchronize(c.stream));
+    return UZK_OK;
+}
+
+// n records of EdRawIn (72 words) -> n records of EdRawOut (37 words), both on the host
+int ed_raw_op_device(Ctx& c, int op, const uint32_t* in, uint32_t* out, size_t n) {
+    if (n == 0) return UZK_OK;
+    static_assert(sizeof(EdRawIn) == 72 * sizeof(uint32_t) && sizeof(EdRawOut) == 37 * sizeof(uint32_t), "records are packed words");
+    EdRawIn* din = nullptr;
+    EdRawOut* dout = nullptr;
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&din), n * sizeof(EdRawIn));
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&dout), n * sizeof(EdRawOut));
+    if (e == hipSuccess) e = hipMemcpyAsync(din, in, n * sizeof(EdRawIn), hipMemcpyHostToDevice, c.stream);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(ed_raw_kat_kernel, dim3(ed_grid(n)), dim3(kEdBlock), 0, c.stream, op, din, dout, n);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(out, dout, n * sizeof(EdRawOut), hipMemcpyDeviceToHost, c.stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c.stream);
+    if (din) (void)hipFree(din);
+    if (dout) (void)hipFree(dout);
+    UZK_HIP(e);
     return UZK_OK;
 }
 

@@ -59,6 +59,7 @@ __device__ __forceinline__ E2<K2, V2> relax(const E2<K, V>& x) {
 template <int K, int V>
 __device__ __forceinline__ E2<1, 2> red(const E2<K, V>& x) {
     static_assert(V <= 32, "reduce() takes values below 32 M");
+    static_assert(K <= 7, "reduce() takes limbs below 2^32 - 2^3: K (2^29 + 2^6) stays below that up to K = 7");
     E2<1, 2> r; r.a.v = F::reduce(x.a.v); r.b.v = F::reduce(x.b.v); return r;
 }
 // the loop-carried form of a value: bound VT, normalized -- a carry step when the bound holds, a reduction when it does not
@@ -117,6 +118,7 @@ __device__ __forceinline__ E2<K + 3, V + 2> conj(const E2<K, V>& x) {
 template <int K, int V>
 __device__ __forceinline__ bool is_zero(const E2<K, V>& x) {
     static_assert(V <= 32, "reduce() takes values below 32 M");
+    static_assert(K <= 7, "reduce() takes limbs below 2^32 - 2^3: K (2^29 + 2^6) stays below that up to K = 7");
     if (!F::is_zero_mod_small(F::reduce(x.a.v))) return false;
     return F::is_zero_mod_small(F::reduce(x.b.v));
 }

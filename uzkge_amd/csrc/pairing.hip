@@ -222,6 +222,140 @@ __global__ __launch_bounds__(kPairBlock) void pairing_kat_kernel(int op, const F
 #endif
 }
 
+// The same operations on RAW limbs (uzk_test_fq12_raw_kat, uzk_test_miller_step_raw): components are taken exactly as given -- nothing is
+// re-limbed or reduced on the way in, nothing canonicalised on the way out -- so a test can put every component at the edge of El's bound
+// and read whether the result is inside it.
+struct F12Raw {
+    uint32_t c[6][2][9];               // the coefficient of w^k: c0 then c1, nine limbs (op 12 out: eight wire words, the ninth 0)
+};
+struct F12RawIn {
+    F12Raw a, b;
+};
+struct MillerRawIn {
+    uint32_t t[3][2][9];               // T = x, y, z
+    uint32_t q[2][2][9];               // Q = qx, qy
+    uint32_t base[2][9];               // xP, -yP
+};
+struct MillerRawOut {
+    uint32_t r[6][2][9];               // x, y, z, l0, l1, l3 of lane 0
+    uint32_t diff[2][9];               // OR over lanes 1 .. 5 and the six values of (their result XOR lane 0's)
+};
+
+#if defined(__HIP_DEVICE_COMPILE__)
+namespace q12 {
+__device__ __forceinline__ El raw_el(const uint32_t (&c)[2][9]) {
+    El r;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) { r.a.v.l[i] = c[0][i]; r.b.v.l[i] = c[1][i]; }
+    return r;
+}
+__device__ __forceinline__ void raw_put(uint32_t (&c)[2][9], const El& x) {
+#pragma unroll
+    for (int i = 0; i < 9; ++i) { c[0][i] = x.a.v.l[i]; c[1][i] = x.b.v.l[i]; }
+}
+__device__ __forceinline__ Base raw_base(const uint32_t (&c)[9]) {
+    Base r;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) r.v.l[i] = c[i];
+    return r;
+}
+}  // namespace q12
+#endif
+
+// uzk_test_fq12_raw_kat: one element per group, lane k holds coefficient k as it lies in the record
+__global__ __launch_bounds__(kPairBlock) void pairing_raw_kat_kernel(int op, const F12RawIn* __restrict__ in, F12Raw* __restrict__ out, uint32_t n,
+                                                                      const Fq12Consts* __restrict__ cst) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    using namespace q12;
+    __shared__ Sh sh[kPairsPerBlock];
+    const uint32_t g = threadIdx.x / kGroup, lane = threadIdx.x % kGroup;
+    const uint32_t item = blockIdx.x * kPairsPerBlock + g;
+    const uint32_t src = item < n ? item : 0;                      // n >= 1: a group past the end runs element 0 and drops it
+    Lane L{&sh[g], lane < 6 ? (int)lane : 0, lane < 6, 0};
+    const El x = raw_el(in[src].a.c[L.k]), y = raw_el(in[src].b.c[L.k]);
+    El r = x;
+    switch (op) {                                                  // the same op in every lane: the barriers inside are uniform
+        case 0: r = f12_mul(L, x, y); break;
+        case 1: r = f12_sqr(L, x); break;
+        case 2: r = f12_sparse(L, x, raw_el(in[src].b.c[0]), raw_el(in[src].b.c[1]), raw_el(in[src].b.c[3])); break;
+        case 3: r = f12_conj(L, x); break;
+        case 4: r = f12_frob<1>(L, x, cst); break;
+        case 5: r = f12_frob<2>(L, x, cst); break;
+        case 6: r = f12_frob<3>(L, x, cst); break;
+        case 7: r = f12_inv(L, x, cst); break;
+        case 8: r = f12_cyc(L, x); break;
+        case 9: r = f12_easy(L, x, cst); break;
+        case 10: r = f12_hard(L, x, cst); break;
+        case 11: r = xi_mul(x); break;
+        default: break;
+    }
+    if (item < n && L.act) {
+        if (op == 12) {
+            const Fq2w w = q2::to_wire(x);
+            uint32_t (&c)[2][9] = out[item].c[L.k];
+#pragma unroll
+            for (int i = 0; i < 8; ++i) { c[0][i] = w.c0.v[i]; c[1][i] = w.c1.v[i]; }
+            c[0][8] = 0; c[1][8] = 0;
+        } else {
+            raw_put(out[item].c[L.k], r);
+        }
+    }
+#endif
+}
+
+// uzk_test_miller_step_raw: one record per group; the group's block of the LDS is filled as miller() fills it, every lane computes the
+// same step, lane 0's result is written with what the other five coefficient lanes' results differ from it by
+__global__ __launch_bounds__(kPairBlock) void pairing_raw_step_kernel(int op, const MillerRawIn* __restrict__ in, MillerRawOut* __restrict__ out, uint32_t n,
+                                                                       const Fq12Consts* __restrict__ cst) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    using namespace q12;
+    __shared__ Sh sh[kPairsPerBlock];
+    const uint32_t g = threadIdx.x / kGroup, lane = threadIdx.x % kGroup;
+    const uint32_t item = blockIdx.x * kPairsPerBlock + g;
+    const uint32_t src = item < n ? item : 0;
+    Lane L{&sh[g], lane < 6 ? (int)lane : 0, lane < 6, 0};
+    const MillerRawIn& rec = in[src];
+    El v[6];
+    v[0] = raw_el(rec.t[0]); v[1] = raw_el(rec.t[1]); v[2] = raw_el(rec.t[2]);
+    if (L.act && L.k == 0) {
+        L.sh->keep[0] = raw_el(rec.q[0]); L.sh->keep[1] = raw_el(rec.q[1]); L.sh->keep[2] = q2::ldr(cst->twist_b3);
+        L.sh->base[0] = raw_base(rec.base[0]); L.sh->base[1] = raw_base(rec.base[1]);
+    }
+    __syncthreads();
+    if (op == 0) {
+        dbl_step(L.sh, v[0], v[1], v[2], v[3], v[4], v[5]);
+    } else {
+        const El qx = L.sh->keep[0], qy = L.sh->keep[1];
+        add_step(L.sh, v[0], v[1], v[2], qx, qy, v[3], v[4], v[5]);
+    }
+    // a workgroup is one wave: lane 0 of the group collects the differences by shuffles that every lane of the wave runs
+    uint32_t diff[2][9];
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int i = 0; i < 9; ++i) {
+            uint32_t d = 0;
+#pragma unroll
+            for (int t = 0; t < 6; ++t) {
+                const uint32_t mine = j == 0 ? v[t].a.v.l[i] : v[t].b.v.l[i];
+                d |= mine ^ (uint32_t)__shfl((int)mine, (int)(g * kGroup), 64);
+            }
+            uint32_t acc = 0;
+#pragma unroll
+            for (int o = 1; o < 6; ++o) acc |= (uint32_t)__shfl((int)d, (int)(g * kGroup + o), 64);
+            diff[j][i] = acc;
+        }
+    if (item < n && lane == 0) {
+#pragma unroll
+        for (int t = 0; t < 6; ++t) raw_put(out[item].r[t], v[t]);
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int i = 0; i < 9; ++i) out[item].diff[j][i] = diff[j][i];
+    }
+#endif
+}
+
 // ---- host -----------------------------------------------------------------------------------------------------------------------
 // xi^((p - 1) / 6) by square and multiply over the quotient's bits, then gamma_1,k = g^k, gamma_2,k = gamma_1,k conj(gamma_1,k),
 // gamma_3,k = gamma_1,k gamma_2,k (gamma^(p^2) = gamma in Fq2); 3 b' = 9 / xi.
@@ -391,6 +525,39 @@ int pairing_miller_device(Ctx& c, const Affine* p, const G2Affine* q, uint32_t n
     UZK_HIP(hipMemcpyAsync(out, w.f[0], (size_t)n * sizeof(Fq12w), hipMemcpyDeviceToHost, c.stream));
     UZK_HIP(hipStreamSynchronize(c.stream));
     return UZK_OK;
+}
+
+// n records In -> n records Out, both on the host, through device buffers of the call's own (the constants with them)
+template <class In, class Out, class Kernel>
+static int pairing_raw_run(Ctx& c, Kernel kernel, int op, const uint32_t* in, uint32_t* out, uint32_t n) {
+    if (n == 0) return UZK_OK;
+    In* din = nullptr;
+    Out* dout = nullptr;
+    Fq12Consts* d_cst = nullptr;
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&din), (size_t)n * sizeof(In));
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&dout), (size_t)n * sizeof(Out));
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d_cst), sizeof(Fq12Consts));
+    if (e == hipSuccess) e = hipMemcpyAsync(d_cst, &pairing_consts(), sizeof(Fq12Consts), hipMemcpyHostToDevice, c.stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(din, in, (size_t)n * sizeof(In), hipMemcpyHostToDevice, c.stream);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(kernel, dim3((n + kPairsPerBlock - 1) / kPairsPerBlock), dim3(kPairBlock), 0, c.stream, op, din, dout, n, d_cst);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(out, dout, (size_t)n * sizeof(Out), hipMemcpyDeviceToHost, c.stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c.stream);
+    if (din) (void)hipFree(din);
+    if (dout) (void)hipFree(dout);
+    if (d_cst) (void)hipFree(d_cst);
+    UZK_HIP(e);
+    return UZK_OK;
+}
+int pairing_raw_kat_device(Ctx& c, int op, const uint32_t* in, uint32_t* out, uint32_t n) {
+    static_assert(sizeof(F12RawIn) == 216 * sizeof(uint32_t) && sizeof(F12Raw) == 108 * sizeof(uint32_t), "records are packed words");
+    return pairing_raw_run<F12RawIn, F12Raw>(c, pairing_raw_kat_kernel, op, in, out, n);
+}
+int pairing_raw_step_device(Ctx& c, int op, const uint32_t* in, uint32_t* out, uint32_t n) {
+    static_assert(sizeof(MillerRawIn) == 108 * sizeof(uint32_t) && sizeof(MillerRawOut) == 126 * sizeof(uint32_t), "records are packed words");
+    return pairing_raw_run<MillerRawIn, MillerRawOut>(c, pairing_raw_step_kernel, op, in, out, n);
 }
 
 }  // namespace uzk
