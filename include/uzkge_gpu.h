@@ -842,6 +842,41 @@ int uzk_cp_reveal_prove_batch(const uint64_t* sk, const uint64_t* e1_mont, const
  * challenges_out  optional, m x 4 words: c_i as plain integers below L (undefined for a verdict of 1) */
 int uzk_cp_reveal_verify_batch(const uint64_t* statements_mont, const uint8_t* proofs, uint32_t m, uint8_t* verdict_out, uint64_t* challenges_out);
 
+/* -- masking a card and the remask of a shuffle (shuffle/src/mask.rs; uzkge/src/shuffle/remark.rs) --
+ * A masked card is e1 = r G, e2 = card + r pk under the joint key pk, with a Chaum-Pedersen DL proof over the parameters g = G, h = pk
+ * and the statement (e1, e2 - card): a_i = omega_i G, b_i = omega_i pk,
+ * c_i = Keccak-256(pad32("Masking") | pad32("DL") | G, pk, e1_i, e2_i - card_i, a_i, b_i as big-endian words) mod L,
+ * r'_i = omega_i + c_i r_i mod L; the blob is the same UZK_CP_PROOF_BYTES layout.  A shuffle re-randomises every card by
+ * UZK_REMARK_ITERATIONS signed additions from two tables  T_P[i][j] = (j + 1) 16^i P  (i < 84, j < 4; P = G for e1, P = pk for e2):
+ *   digit     one byte per (card, iteration): bits 0 and 1 give j = bit0 + 2 bit1, bit 2 set adds T[i][j], clear subtracts it; bits
+ *             3 .. 7 must be 0.  Equivalent scalar: rho = sum_i +-(j_i + 1) 16^i, and the remasked card is (e1 + rho G, e2 + rho pk)
+ *   trace     the affine (c2.x, c2.y, c1.x, c1.y) after every step, c1 from e1 and c2 from e2 (RemarkTrace::intermediate_values: the
+ *             witness of the shuffle circuit's remark gates); entry 83 is the remasked card; the identity is (0, 1)
+ *   tables    x, y, d x y of every entry, [84][4][3] elements: what compute_shuffle_public_key_selectors /
+ *             load_shuffle_remark_parameters put into the circuit; laying them out over the size-n domain stays with the caller
+ * The computing calls (key_create, remark_batch, mask_prove) refuse a coordinate that is not below q, a batch of 0 or above the
+ * maximum, a perm that is no permutation, a digit above 7 and an unknown key with UZK_ERR_PARAMETER before the device is touched;
+ * they check neither the curve nor the subgroup (uzk_ed_check_points does; off the curve the outputs are unspecified).  The library
+ * draws no randomness: digits, rs, omegas and perm come from the caller. */
+#define UZK_REMARK_ITERATIONS 84
+/* Builds T_pk on the current context's device and keeps it until the key is released (once per game). */
+int uzk_remark_key_create(const uint64_t* pk_mont, uint64_t* key_out);
+int uzk_remark_key_release(uint64_t key);
+/* Either output optional: [84][4][3] elements (x, y, d x y) of T_pk / T_G. */
+int uzk_remark_key_tables(uint64_t key, uint64_t* pk_tables_out, uint64_t* gen_tables_out);
+/* digits: n x 84 bytes; perm: n entries, a permutation of 0 .. n-1 (out[i] = remasked[perm[i]], the row convention of Permutation),
+ * or NULL for the identity; trace_out optional: n x 84 x 4 elements in INPUT card order; e1_out / e2_out: n points in OUTPUT order. */
+int uzk_remark_batch(uint64_t key, const uint64_t* e1_mont, const uint64_t* e2_mont, const uint8_t* digits, const uint32_t* perm, uint32_t n,
+                     uint64_t* e1_out, uint64_t* e2_out, uint64_t* trace_out);
+/* pk: one point; cards: m points; rs, omegas: m scalars each, drawn by the CALLER.  e1_out, e2_out: m points; proofs_out: m blobs. */
+int uzk_cp_mask_prove_batch(const uint64_t* pk_mont, const uint64_t* cards_mont, const uint64_t* rs, const uint64_t* omegas, uint32_t m,
+                            uint64_t* e1_out, uint64_t* e2_out, uint8_t* proofs_out);
+/* verdict_out     m bytes, the first that applies over the six points pk, card, e1, e2, a, b: 1 a coordinate or proof word >= q; 2 a
+ *                 point off the curve; 3 a point outside the prime subgroup; 4 r G != a + c e1; 5 r pk != b + c (e2 - card); 0 accepted
+ * challenges_out  optional, m x 4 words: c_i as plain integers below L (undefined for a verdict of 1) */
+int uzk_cp_mask_verify_batch(const uint64_t* pk_mont, const uint64_t* cards_mont, const uint64_t* e1_mont, const uint64_t* e2_mont,
+                             const uint8_t* proofs, uint32_t m, uint8_t* verdict_out, uint64_t* challenges_out);
+
 /* ---- synthetic workloads (bench / tests; generated on device, nothing uploaded) -------- */
 /* d_points[i] = (i + 1) * Q with Q = seed_scalar * G: n distinct valid G1 points whose discrete
  * logs relative to Q are known, so MSM(points, s) == (sum_i s_i (i+1)) * Q for any size. */

@@ -557,6 +557,90 @@ pub fn cp_reveal_verify_batch(statements: &[RevealStatement], proofs: &[u8]) -> 
     Ok(verdict)
 }
 
+// ---- masking a card and the remask of a shuffle --------------------------------------------------------------------------------------
+/// One table of a remask key: [84][4] entries of (x, y, d x y).
+pub type RemarkTable = Vec<[Limbs; 3]>;
+/// The result of `RemarkKey::remark_batch`: e1 and e2 of the new deck in output order, and the trace (n x 84 entries of
+/// c2.x, c2.y, c1.x, c1.y in input card order) where it was asked for.
+pub type RemarkOutput = (Vec<EdPoint>, Vec<EdPoint>, Option<Vec<[Limbs; 4]>>);
+
+/// The remask tables of one joint key, resident on the current context's device (`uzk_remark_key_create`); released on drop.
+pub struct RemarkKey {
+    handle: u64,
+}
+impl RemarkKey {
+    pub fn new(pk: &EdPoint) -> Result<Self, Error> {
+        let mut handle = 0u64;
+        check(unsafe { uzk_remark_key_create(pk.as_ptr() as *const u64, &mut handle) })?;
+        Ok(Self { handle })
+    }
+    /// (T_pk, T_G): x, y, d x y of every entry (`uzk_remark_key_tables`) -- what compute_shuffle_public_key_selectors and
+    /// load_shuffle_remark_parameters lay out over the circuit's domain.
+    pub fn tables(&self) -> Result<(RemarkTable, RemarkTable), Error> {
+        let entries = UZK_REMARK_ITERATIONS as usize * 4;
+        let mut pk = vec![[[0u64; 4]; 3]; entries];
+        let mut gen = vec![[[0u64; 4]; 3]; entries];
+        check(unsafe { uzk_remark_key_tables(self.handle, pk.as_mut_ptr() as *mut u64, gen.as_mut_ptr() as *mut u64) })?;
+        Ok((pk, gen))
+    }
+    /// Every card remasked by its 84 digits, then out[i] = remasked[perm[i]] (`uzk_remark_batch`).  digits: n x 84 bytes (bits 0, 1: j;
+    /// bit 2 set: add, clear: subtract); perm: a permutation of 0 .. n-1, or None for the identity.
+    pub fn remark_batch(&self, e1: &[EdPoint], e2: &[EdPoint], digits: &[u8], perm: Option<&[u32]>, want_trace: bool) -> Result<RemarkOutput, Error> {
+        let n = e1.len();
+        let iters = UZK_REMARK_ITERATIONS as usize;
+        if n == 0 || n > UZK_ED_MAX_BATCH as usize || e2.len() != n || digits.len() != n * iters || perm.map_or(false, |p| p.len() != n) {
+            return Err(Error::Parameter);
+        }
+        let mut o1 = vec![[[0u64; 4]; 2]; n];
+        let mut o2 = vec![[[0u64; 4]; 2]; n];
+        let mut trace = if want_trace { Some(vec![[[0u64; 4]; 4]; n * iters]) } else { None };
+        let trace_ptr = trace.as_mut().map_or(std::ptr::null_mut(), |t| t.as_mut_ptr() as *mut u64);
+        let perm_ptr = perm.map_or(std::ptr::null(), |p| p.as_ptr());
+        check(unsafe {
+            uzk_remark_batch(self.handle, e1.as_ptr() as *const u64, e2.as_ptr() as *const u64, digits.as_ptr(), perm_ptr, n as u32, o1.as_mut_ptr() as *mut u64,
+                             o2.as_mut_ptr() as *mut u64, trace_ptr)
+        })?;
+        Ok((o1, o2, trace))
+    }
+}
+impl Drop for RemarkKey {
+    fn drop(&mut self) {
+        unsafe { uzk_remark_key_release(self.handle) };
+    }
+}
+
+/// m cards masked under the joint key (`uzk_cp_mask_prove_batch`): (e1, e2, m proof blobs of UZK_CP_PROOF_BYTES).  `rs` and `omegas`
+/// are plain integers below the subgroup order, drawn by the caller.
+pub fn cp_mask_prove_batch(pk: &EdPoint, cards: &[EdPoint], rs: &[Limbs], omegas: &[Limbs]) -> Result<(Vec<EdPoint>, Vec<EdPoint>, Vec<u8>), Error> {
+    let m = cards.len();
+    if m == 0 || m > UZK_CP_MAX_BATCH as usize || rs.len() != m || omegas.len() != m {
+        return Err(Error::Parameter);
+    }
+    let mut e1 = vec![[[0u64; 4]; 2]; m];
+    let mut e2 = vec![[[0u64; 4]; 2]; m];
+    let mut proofs = vec![0u8; m * UZK_CP_PROOF_BYTES as usize];
+    check(unsafe {
+        uzk_cp_mask_prove_batch(pk.as_ptr() as *const u64, cards.as_ptr() as *const u64, rs.as_ptr() as *const u64, omegas.as_ptr() as *const u64, m as u32,
+                                e1.as_mut_ptr() as *mut u64, e2.as_mut_ptr() as *mut u64, proofs.as_mut_ptr())
+    })?;
+    Ok((e1, e2, proofs))
+}
+
+/// The verdict byte of every (card, masked card, proof) under the joint key (`uzk_cp_mask_verify_batch`): 0 accepted, 1 .. 3 a
+/// malformed point among pk, card, e1, e2, a, b, 4 the first equation fails, 5 the second.
+pub fn cp_mask_verify_batch(pk: &EdPoint, cards: &[EdPoint], e1: &[EdPoint], e2: &[EdPoint], proofs: &[u8]) -> Result<Vec<u8>, Error> {
+    let m = cards.len();
+    if m == 0 || m > UZK_CP_MAX_BATCH as usize || e1.len() != m || e2.len() != m || proofs.len() != m * UZK_CP_PROOF_BYTES as usize {
+        return Err(Error::Parameter);
+    }
+    let mut verdict = vec![0u8; m];
+    check(unsafe {
+        uzk_cp_mask_verify_batch(pk.as_ptr() as *const u64, cards.as_ptr() as *const u64, e1.as_ptr() as *const u64, e2.as_ptr() as *const u64, proofs.as_ptr(),
+                                 m as u32, verdict.as_mut_ptr(), std::ptr::null_mut())
+    })?;
+    Ok(verdict)
+}
+
 /// How provers of ONE proof made from now on are shared between threads (`uzk_coalesce_config`): the library runs round calls of
 /// several threads that stand at the same round of proofs over the same circuit as one lockstep launch sequence.  On by default
 /// (at most 8 proofs per sequence, the provers at work spread over 4 sequences, 2000 us gathering wait -- include/uzkge_gpu.h; 0 = a default);

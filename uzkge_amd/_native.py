@@ -140,6 +140,12 @@ PROTOTYPES = {
     "uzk_ed_unmask_batch": (_I, [_P, _P, ctypes.c_uint32, ctypes.c_uint32, _P]),
     "uzk_cp_reveal_prove_batch": (_I, [_P, _P, _P, ctypes.c_uint32, _P, _P, _P]),
     "uzk_cp_reveal_verify_batch": (_I, [_P, _P, ctypes.c_uint32, _P, _P]),
+    "uzk_remark_key_create": (_I, [_P, ctypes.POINTER(_U64)]),
+    "uzk_remark_key_release": (_I, [_U64]),
+    "uzk_remark_key_tables": (_I, [_U64, _P, _P]),
+    "uzk_remark_batch": (_I, [_U64, _P, _P, _P, _P, ctypes.c_uint32, _P, _P, _P]),
+    "uzk_cp_mask_prove_batch": (_I, [_P, _P, _P, _P, ctypes.c_uint32, _P, _P, _P]),
+    "uzk_cp_mask_verify_batch": (_I, [_P, _P, _P, _P, _P, ctypes.c_uint32, _P, _P]),
     "uzk_synth_points_arith": (_I, [_P, _SZ, _P]),
     "uzk_synth_points_random": (_I, [_P, _SZ, _U64]),
     "uzk_synth_scalars": (_I, [_P, _SZ, _U64]),
@@ -288,6 +294,7 @@ PAIRING_MAX_PAIRS = 4099
 CP_PROOF_BYTES = 160
 CP_MAX_BATCH = 65536
 ED_MAX_BATCH = 1 << 20
+REMARK_ITERATIONS = 84
 
 
 class G16VkDesc(ctypes.Structure):

@@ -1201,6 +1201,82 @@ def cp_reveal_verify_batch(statements, proofs, want_challenges: bool = False):
     return (verdict[:m], ch[:m]) if want_challenges else verdict[:m]
 
 
+class RemarkKey:
+    """uzk_remark_key_create: the remask tables of one joint key, T_pk[i][j] = (j + 1) 16^i pk, resident on the current context's
+    device for the length of a game.  A context manager: the key is released on exit."""
+
+    def __init__(self, pk):
+        p = np.ascontiguousarray(pk, dtype=np.uint64).reshape(8)
+        h = ctypes.c_uint64(0)
+        check(lib.uzk_remark_key_create(_ptr(p), ctypes.byref(h)))
+        self.handle = h.value
+
+    def tables(self, want_pk: bool = True, want_gen: bool = True):
+        """uzk_remark_key_tables: (T_pk, T_G), each [84, 4, 3, 4] -- x, y, d x y of every entry -- or None where not wanted"""
+        shape = (N.REMARK_ITERATIONS, 4, 3, 4)
+        tp = np.zeros(shape, dtype=np.uint64) if want_pk else None
+        tg = np.zeros(shape, dtype=np.uint64) if want_gen else None
+        check(lib.uzk_remark_key_tables(self.handle, _ptr(tp) if want_pk else None, _ptr(tg) if want_gen else None))
+        return tp, tg
+
+    def remark_batch(self, e1, e2, digits, perm=None, want_trace: bool = False):
+        """uzk_remark_batch: e1, e2 [n, 8]; digits uint8 [n, 84]; perm uint32 [n] or None.  Returns (e1_out [n, 8], e2_out [n, 8] in
+        output order, trace [n, 84, 4, 4] in input order or None)."""
+        a = np.ascontiguousarray(e1, dtype=np.uint64).reshape(-1, 8)
+        c = np.ascontiguousarray(e2, dtype=np.uint64).reshape(-1, 8)
+        n = a.shape[0]
+        d = np.ascontiguousarray(digits, dtype=np.uint8).reshape(-1, N.REMARK_ITERATIONS)
+        assert c.shape[0] == n and d.shape[0] == n, "one e2 and 84 digits per card"
+        pm = None if perm is None else np.ascontiguousarray(perm, dtype=np.uint32).reshape(-1)
+        assert pm is None or pm.size == n, "one perm entry per card"
+        o1, o2 = np.zeros((max(n, 1), 8), dtype=np.uint64), np.zeros((max(n, 1), 8), dtype=np.uint64)
+        tr = np.zeros((max(n, 1), N.REMARK_ITERATIONS, 4, 4), dtype=np.uint64) if want_trace else None
+        vp = lambda arr: arr.ctypes.data_as(ctypes.c_void_p)
+        check(lib.uzk_remark_batch(self.handle, _ptr(a), _ptr(c), vp(d), None if pm is None else vp(pm), n, _ptr(o1), _ptr(o2), _ptr(tr) if want_trace else None))
+        return o1[:n], o2[:n], (tr[:n] if want_trace else None)
+
+    def release(self) -> None:
+        if self.handle:
+            check(lib.uzk_remark_key_release(self.handle))
+            self.handle = 0
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc) -> None:
+        self.release()
+
+
+def cp_mask_prove_batch(pk, cards, rs, omegas):
+    """uzk_cp_mask_prove_batch: pk [8]; cards [m, 8]; rs, omegas [m, 4] plain integers.  Returns (e1 [m, 8], e2 [m, 8], proofs: uint8
+    [m, 160])."""
+    k = np.ascontiguousarray(pk, dtype=np.uint64).reshape(8)
+    p = np.ascontiguousarray(cards, dtype=np.uint64).reshape(-1, 8)
+    r = np.ascontiguousarray(rs, dtype=np.uint64).reshape(-1, 4)
+    w = np.ascontiguousarray(omegas, dtype=np.uint64).reshape(-1, 4)
+    m = p.shape[0]
+    assert r.shape[0] == m and w.shape[0] == m, "one r and one omega per card"
+    e1, e2 = np.zeros((max(m, 1), 8), dtype=np.uint64), np.zeros((max(m, 1), 8), dtype=np.uint64)
+    proofs = np.zeros((max(m, 1), N.CP_PROOF_BYTES), dtype=np.uint8)
+    check(lib.uzk_cp_mask_prove_batch(_ptr(k), _ptr(p), _ptr(r), _ptr(w), m, _ptr(e1), _ptr(e2), proofs.ctypes.data_as(ctypes.c_void_p)))
+    return e1[:m], e2[:m], proofs[:m]
+
+
+def cp_mask_verify_batch(pk, cards, e1, e2, proofs, want_challenges: bool = False):
+    """uzk_cp_mask_verify_batch: pk [8]; cards, e1, e2 [m, 8]; proofs m blobs of 160 bytes.  Returns verdict [m] (0 accepted, 1 .. 5 the
+    first failing check), and with want_challenges also c [m, 4] as plain integers."""
+    raw = _u8(proofs, N.CP_PROOF_BYTES)
+    m = raw.size // N.CP_PROOF_BYTES
+    k = np.ascontiguousarray(pk, dtype=np.uint64).reshape(8)
+    arrs = [np.ascontiguousarray(x, dtype=np.uint64).reshape(-1, 8) for x in (cards, e1, e2)]
+    assert all(x.shape[0] == m for x in arrs), "one card, one e1 and one e2 per proof"
+    verdict = np.zeros(max(m, 1), dtype=np.uint8)
+    ch = np.zeros((max(m, 1), 4), dtype=np.uint64) if want_challenges else None
+    vp = lambda arr: arr.ctypes.data_as(ctypes.c_void_p)
+    check(lib.uzk_cp_mask_verify_batch(_ptr(k), _ptr(arrs[0]), _ptr(arrs[1]), _ptr(arrs[2]), vp(raw), m, vp(verdict), _ptr(ch) if want_challenges else None))
+    return (verdict[:m], ch[:m]) if want_challenges else verdict[:m]
+
+
 def fq12_kat(op: int, a, b=None) -> np.ndarray:
     """uzk_test_fq12_kat (test hook): a, b [n, 6, 2, 4] wire elements of Fq12."""
     x = np.ascontiguousarray(a, dtype=np.uint64).reshape(-1, 6, 2, 4)

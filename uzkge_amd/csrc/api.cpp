@@ -231,6 +231,8 @@ static void ctx_release(Ctx& c) {
     c.verify_ws.release();
     c.g16v_ws.release();
     c.ed_ws.release();
+    c.ed_gen.release();
+    c.ed_gen_ready = false;
     c.pairing_ws.release();
     msm_free(c);
     poly_free(c);
@@ -323,6 +325,7 @@ int uzk_shutdown(void) try {
     g2_release_all();                      // G2 bases
     g16_release_all();                     // Groth16 proving keys
     g16v_release_all();                    // Groth16 verifying keys
+    remark_release_all();                  // remask keys
     std::lock_guard<std::mutex> lk(s.mu);
     if (!s.bound) return UZK_OK;
     ctx_release(default_ctx());
@@ -1495,6 +1498,71 @@ int uzk_cp_reveal_verify_batch(const uint64_t* statements_mont, const uint8_t* p
     UZK_TRY(require_ready());
     return cp_verify_run(ctx(), as_ed(statements_mont), proofs, m, verdict_out, reinterpret_cast<Fp*>(challenges_out));
 } catch (...) { return uzk::on_exception("uzk_cp_reveal_verify_batch"); }
+
+int uzk_remark_key_create(const uint64_t* pk_mont, uint64_t* key_out) try {
+    API_LOCK;
+    if (!pk_mont || !key_out) { set_error("uzk_remark_key_create: null pointer"); return UZK_ERR_PARAMETER; }
+    UZK_TRY(ed_require_canonical("uzk_remark_key_create", "pk", pk_mont, 1));
+    UZK_TRY(require_ready());
+    return remark_key_create(ctx(), as_ed(pk_mont), key_out);
+} catch (...) { return uzk::on_exception("uzk_remark_key_create"); }
+
+int uzk_remark_key_release(uint64_t key) try {
+    API_LOCK;
+    return remark_key_release(key);
+} catch (...) { return uzk::on_exception("uzk_remark_key_release"); }
+
+int uzk_remark_key_tables(uint64_t key, uint64_t* pk_tables_out, uint64_t* gen_tables_out) try {
+    API_LOCK;
+    if (!remark_key_known(key, nullptr)) { set_error("uzk_remark_key_tables: unknown remask key %llu", (unsigned long long)key); return UZK_ERR_PARAMETER; }
+    UZK_TRY(require_ready());
+    return remark_tables_run(ctx(), key, reinterpret_cast<Fp*>(pk_tables_out), reinterpret_cast<Fp*>(gen_tables_out));
+} catch (...) { return uzk::on_exception("uzk_remark_key_tables"); }
+
+int uzk_remark_batch(uint64_t key, const uint64_t* e1_mont, const uint64_t* e2_mont, const uint8_t* digits, const uint32_t* perm, uint32_t n, uint64_t* e1_out,
+                     uint64_t* e2_out, uint64_t* trace_out) try {
+    API_LOCK;
+    if (n == 0 || n > UZK_ED_MAX_BATCH) { set_error("uzk_remark_batch: %u cards (1 .. %d per call)", n, UZK_ED_MAX_BATCH); return UZK_ERR_PARAMETER; }
+    if (!e1_mont || !e2_mont || !digits || !e1_out || !e2_out) { set_error("uzk_remark_batch: null pointer"); return UZK_ERR_PARAMETER; }
+    UZK_TRY(ed_require_canonical("uzk_remark_batch", "e1", e1_mont, n));
+    UZK_TRY(ed_require_canonical("uzk_remark_batch", "e2", e2_mont, n));
+    for (size_t i = 0; i < (size_t)n * UZK_REMARK_ITERATIONS; ++i)
+        if (digits[i] > 7) {
+            set_error("uzk_remark_batch: digit %zu of card %zu is %u (three bits: 0 .. 7)", i % UZK_REMARK_ITERATIONS, i / UZK_REMARK_ITERATIONS, digits[i]);
+            return UZK_ERR_PARAMETER;
+        }
+    std::vector<uint32_t> slot;                                     // slot[perm[i]] = i: where card perm[i] goes
+    if (perm) {
+        slot.assign(n, 0xffffffffu);
+        for (uint32_t i = 0; i < n; ++i) {
+            if (perm[i] >= n || slot[perm[i]] != 0xffffffffu) { set_error("uzk_remark_batch: perm[%u] = %u: not a permutation of 0 .. %u", i, perm[i], n - 1); return UZK_ERR_PARAMETER; }
+            slot[perm[i]] = i;
+        }
+    }
+    if (!remark_key_known(key, nullptr)) { set_error("uzk_remark_batch: unknown remask key %llu", (unsigned long long)key); return UZK_ERR_PARAMETER; }
+    UZK_TRY(require_ready());
+    return remark_run(ctx(), key, as_ed(e1_mont), as_ed(e2_mont), digits, perm ? slot.data() : nullptr, n, as_ed(e1_out), as_ed(e2_out), reinterpret_cast<Fp*>(trace_out));
+} catch (...) { return uzk::on_exception("uzk_remark_batch"); }
+
+int uzk_cp_mask_prove_batch(const uint64_t* pk_mont, const uint64_t* cards_mont, const uint64_t* rs, const uint64_t* omegas, uint32_t m, uint64_t* e1_out,
+                            uint64_t* e2_out, uint8_t* proofs_out) try {
+    API_LOCK;
+    if (m == 0 || m > UZK_CP_MAX_BATCH) { set_error("uzk_cp_mask_prove_batch: %u cards (1 .. %d per call)", m, UZK_CP_MAX_BATCH); return UZK_ERR_PARAMETER; }
+    if (!pk_mont || !cards_mont || !rs || !omegas || !e1_out || !e2_out || !proofs_out) { set_error("uzk_cp_mask_prove_batch: null pointer"); return UZK_ERR_PARAMETER; }
+    UZK_TRY(ed_require_canonical("uzk_cp_mask_prove_batch", "pk", pk_mont, 1));
+    UZK_TRY(ed_require_canonical("uzk_cp_mask_prove_batch", "cards", cards_mont, m));
+    UZK_TRY(require_ready());
+    return cp_mask_prove_run(ctx(), as_ed(pk_mont), as_ed(cards_mont), as_fp(rs), as_fp(omegas), m, as_ed(e1_out), as_ed(e2_out), proofs_out);
+} catch (...) { return uzk::on_exception("uzk_cp_mask_prove_batch"); }
+
+int uzk_cp_mask_verify_batch(const uint64_t* pk_mont, const uint64_t* cards_mont, const uint64_t* e1_mont, const uint64_t* e2_mont, const uint8_t* proofs, uint32_t m,
+                             uint8_t* verdict_out, uint64_t* challenges_out) try {
+    API_LOCK;
+    if (m == 0 || m > UZK_CP_MAX_BATCH) { set_error("uzk_cp_mask_verify_batch: %u proofs (1 .. %d per call)", m, UZK_CP_MAX_BATCH); return UZK_ERR_PARAMETER; }
+    if (!pk_mont || !cards_mont || !e1_mont || !e2_mont || !proofs || !verdict_out) { set_error("uzk_cp_mask_verify_batch: null pointer"); return UZK_ERR_PARAMETER; }
+    UZK_TRY(require_ready());
+    return cp_mask_verify_run(ctx(), as_ed(pk_mont), as_ed(cards_mont), as_ed(e1_mont), as_ed(e2_mont), proofs, m, verdict_out, reinterpret_cast<Fp*>(challenges_out));
+} catch (...) { return uzk::on_exception("uzk_cp_mask_verify_batch"); }
 
 int uzk_test_fq12_kat(int op, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n) try {
     API_LOCK;

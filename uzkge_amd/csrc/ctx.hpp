@@ -153,6 +153,8 @@ struct Ctx {
     std::vector<uint8_t> pairing_status;   // the statuses of a product's pairs on the host (grow-only)
     // edwards.hip: one block carved into the arrays of a Baby Jubjub call (points, scalars, proofs, statuses, results)
     DevBuf ed_ws;
+    DevBuf ed_gen;                    // T_G, the generator's half of the remask tables: a constant, built once per context
+    bool ed_gen_ready = false;
     int tune_verify_transcript = 0;   // which transcript kernel a fold runs: 1 one proof per lane; 0 / 2 a proof's state spread over a half wave (the default)
     // an entry of the process-wide SRS registry
     struct Srs {
@@ -315,6 +317,18 @@ int ed_sum_run(Ctx& c, const EdAffine* e2, const EdAffine* rows, uint32_t k, uin
 int cp_verify_run(Ctx& c, const EdAffine* statements, const uint8_t* proofs, uint32_t m, uint8_t* verdict_out, Fp* challenges_out);
 int cp_prove_run(Ctx& c, const Fp* sk, const EdAffine* e1, const Fp* omegas, uint32_t m, EdAffine* reveal_out, EdAffine* pk_out, uint8_t* proofs_out);
 int ed_raw_op_device(Ctx& c, int op, const uint32_t* in, uint32_t* out, size_t n);
+// edwards.hip: the Chaum-Pedersen proofs of a mask; remask keys (process-wide handles: T_pk on the device), the tables and the remask
+int cp_mask_prove_run(Ctx& c, const EdAffine* pk, const EdAffine* cards, const Fp* rs, const Fp* omegas, uint32_t m, EdAffine* e1_out, EdAffine* e2_out,
+                      uint8_t* proofs_out);
+int cp_mask_verify_run(Ctx& c, const EdAffine* pk, const EdAffine* cards, const EdAffine* e1, const EdAffine* e2, const uint8_t* proofs, uint32_t m,
+                       uint8_t* verdict_out, Fp* challenges_out);
+int remark_key_create(Ctx& c, const EdAffine* pk, uint64_t* out);
+bool remark_key_known(uint64_t h, int* device);
+int remark_key_release(uint64_t h);
+void remark_release_all();
+int remark_tables_run(Ctx& c, uint64_t h, Fp* pk_tables_out, Fp* gen_tables_out);
+int remark_run(Ctx& c, uint64_t h, const EdAffine* e1, const EdAffine* e2, const uint8_t* digits, const uint32_t* slot, uint32_t n, EdAffine* e1_out,
+               EdAffine* e2_out, Fp* trace_out);
 void msm_plan_info(Ctx& c, size_t n, int* window_bits, int* windows);
 int msm_run(Ctx& c, const Affine* points, const ScalarView& scalars, size_t n, uint32_t batch, Jac* out_host, int pre_c,
             uint32_t pre_stride, uint32_t pre_off);

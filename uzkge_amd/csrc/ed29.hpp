@@ -94,17 +94,25 @@ UZK_HD Fp ed_d_wire() {
     return ed_words(d);
 }
 
-// ---- the Chaum-Pedersen transcript of a reveal -------------------------------------------------------------------------------------
-// Keccak-256 of 448 bytes: pad32("Revealing"), pad32("DL"), then x and y of e1, G, reveal, pk, a, b as 32-byte big-endian words
-// (Transcript::new + the appends of chaum_pedersen/dl.rs; utils/transcript.rs left-pads short messages with zeros).  w: the twelve
-// coordinates as PLAIN canonical integers.  Returns the digest read as a big-endian integer, not reduced.
-UZK_HD Fp cp_transcript_digest(const Fp (&w)[12]) {
+// ---- the Chaum-Pedersen transcript of a DL proof -----------------------------------------------------------------------------------
+// Keccak-256 of 448 bytes: pad32(label), pad32("DL"), then x and y of g, h, u, v, a, b as 32-byte big-endian words -- the parameters
+// (g, h), the statement (u, v) and the commitments of uzkge/src/chaum_pedersen/dl.rs (Transcript::new + its appends;
+// utils/transcript.rs left-pads short messages with zeros).  A reveal is g = e1, h = G, u = reveal, v = pk under "Revealing"; a mask is
+// g = G, h = pk, u = e1, v = e2 - card under "Masking".  w: the twelve coordinates as PLAIN canonical integers.  Returns the digest
+// read as a big-endian integer, not reduced.
+struct CpLabel {
+    uint64_t lane2, lane3;             // bytes 16 .. 31 of the first word as two little-endian sponge lanes (labels of up to 16 bytes)
+};
+// "Revealing" = 52 65 76 65 61 6c 69 6e 67: the last nine bytes of the first word
+UZK_HD CpLabel cp_label_revealing() { return CpLabel{0x52ull << 56, 0x676e696c61657665ull}; }
+// "Masking" = 4d 61 73 6b 69 6e 67: the last seven
+UZK_HD CpLabel cp_label_masking() { return CpLabel{0, 0x676e696b73614d00ull}; }
+UZK_HD Fp cp_transcript_digest(const Fp (&w)[12], const CpLabel label = cp_label_revealing()) {
     uint64_t lanes[56];
     for (int i = 0; i < 8; ++i) lanes[i] = 0;
-    // "Revealing" = 52 65 76 65 61 6c 69 6e 67: the last nine bytes of the first word; "DL" = 44 4c: the last two of the second
-    lanes[2] = 0x52ull << 56;
-    lanes[3] = 0x676e696c61657665ull;
-    lanes[7] = 0x4c44ull << 48;
+    lanes[2] = label.lane2;
+    lanes[3] = label.lane3;
+    lanes[7] = 0x4c44ull << 48;                                      // "DL" = 44 4c: the last two bytes of the second word
 #pragma unroll
     for (int j = 0; j < 12; ++j) {
 #pragma unroll

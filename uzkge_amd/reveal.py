@@ -1,5 +1,7 @@
-"""The plain reveal path of a zshuffle game over arrays of cards, with the reference's names (shuffle/src/reveal.rs, keygen.rs;
-RevealVerifier.sol): every function is one call of the Baby Jubjub layer of the C ABI (include/uzkge_gpu.h, uzk_ed_* / uzk_cp_reveal_*).
+"""The Baby Jubjub side of a zshuffle game over arrays of cards, with the reference's names: the plain reveal path
+(shuffle/src/reveal.rs, keygen.rs; RevealVerifier.sol), masking (shuffle/src/mask.rs) and the remask of a shuffle
+(uzkge/src/shuffle/remark.rs).  Every function is one call of the Baby Jubjub layer of the C ABI (include/uzkge_gpu.h, uzk_ed_* /
+uzk_cp_* / uzk_remark_*).
 
 Points are affine integer pairs (x, y) below q, the identity is (0, 1); a masked card is (e1, e2); secrets and omegas are integers below
 the subgroup order L; a proof is the 160 bytes of ChaumPedersenDLProof::to_uncompress.  The library draws no randomness: the caller
@@ -95,3 +97,55 @@ def unmask(masked_cards: Sequence[Tuple[Point, Point]], reveal_cards: Sequence[S
         raise ValueError("every player reveals every card")
     rows = np.stack([points_to_wire(row) for row in reveal_cards])
     return points_from_wire(b.ed_unmask_batch(points_to_wire([c[1] for c in masked_cards]), rows))
+
+
+def remark_key(pk: Point) -> b.RemarkKey:
+    """the remask tables of the joint key, built once per game; a context manager"""
+    return b.RemarkKey(points_to_wire([pk])[0])
+
+
+def mask(pk: Point, cards: Sequence[Point], rs: Sequence[int], omegas: Sequence[int]):
+    """(masked cards (e1, e2), proofs) of the cards under the joint key: e1 = r G, e2 = card + r pk with a "Masking" proof each.  rs and
+    omegas: one integer below L per card, drawn by the caller (init_masked_cards uses r = 1)."""
+    if not len(cards) == len(rs) == len(omegas):
+        raise ValueError("one r and one omega per card")
+    e1, e2, proofs = b.cp_mask_prove_batch(points_to_wire([pk])[0], points_to_wire(cards), scalars_to_wire(rs), scalars_to_wire(omegas))
+    return list(zip(points_from_wire(e1), points_from_wire(e2))), [bytes(p) for p in proofs]
+
+
+def verify_mask(pk: Point, cards: Sequence[Point], masked_cards: Sequence[Tuple[Point, Point]], proofs: Sequence[bytes]) -> List[int]:
+    """The verdict of every (card, masked card, proof) under the joint key: 0 accepted, else the first failing check
+    (uzk_cp_mask_verify_batch)."""
+    if not len(cards) == len(masked_cards) == len(proofs):
+        raise ValueError("one masked card and one proof per card")
+    if any(len(p) != N.CP_PROOF_BYTES for p in proofs):
+        raise ValueError("a proof is %d bytes" % N.CP_PROOF_BYTES)
+    wire = points_to_wire
+    return [int(v) for v in b.cp_mask_verify_batch(wire([pk])[0], wire(cards), wire([c[0] for c in masked_cards]), wire([c[1] for c in masked_cards]),
+                                                   b"".join(proofs))]
+
+
+def remark_scalar(digits: Sequence[int]) -> int:
+    """rho = sum_i +-(j_i + 1) 16^i of one card's 84 digits (bits 0, 1: j; bit 2 set: +): the remasked card is (e1 + rho G, e2 + rho pk)"""
+    if len(digits) != N.REMARK_ITERATIONS:
+        raise ValueError("%d digits per card" % N.REMARK_ITERATIONS)
+    if any(not 0 <= d <= 7 for d in digits):
+        raise ValueError("a digit is three bits")
+    return sum((1 if d & 4 else -1) * ((d & 3) + 1) << (4 * i) for i, d in enumerate(digits))
+
+
+def shuffle(remark_key: b.RemarkKey, masked_cards: Sequence[Tuple[Point, Point]], digits: Sequence[Sequence[int]], perm: Sequence[int] = None,
+            want_trace: bool = False):
+    """One player's shuffle: every card remasked by its 84 digits, then out[i] = remasked[perm[i]].  Returns the new deck, and with
+    want_trace also the traces in INPUT card order: per card 84 entries (c2.x, c2.y, c1.x, c1.y), the intermediate values of
+    eval_remark_with_trace.  digits and perm come from the caller."""
+    if len(digits) != len(masked_cards):
+        raise ValueError("84 digits per card")
+    e1, e2, tr = remark_key.remark_batch(points_to_wire([c[0] for c in masked_cards]), points_to_wire([c[1] for c in masked_cards]),
+                                         np.asarray(digits, dtype=np.uint8), perm, want_trace)
+    deck = list(zip(points_from_wire(e1), points_from_wire(e2)))
+    if not want_trace:
+        return deck
+    flat = points_from_wire(tr)                                       # (c2.x, c2.y), (c1.x, c1.y) alternating
+    per = N.REMARK_ITERATIONS
+    return deck, [[flat[2 * (k * per + i)] + flat[2 * (k * per + i) + 1] for i in range(per)] for k in range(len(masked_cards))]
