@@ -74,6 +74,14 @@ int uzk_test_g2_raw_kat(int op, const uint32_t* in, uint32_t* out, size_t n);
 int uzk_test_lanes(int op, const void* const* d_polys, const uint64_t* lane_strides, uint32_t count, const uint32_t* lens, const uint32_t* pts,
                    const uint64_t* args, uint32_t lanes, uint64_t len, uint64_t* out, int* kernel);
 
+/* ntt_run exactly as uzk_ntt_fr_batch_strided_device calls it (forward only), with the caller's statement that every input vector
+ * is zero from index in_len on (0 = no statement).  Synchronous.  Only the prover makes that statement (derive_cosets: in_len = n on
+ * 6n-point slots; round 3: n + 8): with 3 * 2^k points, fused sub-transforms (n / 3 >= 4096) and 0 < in_len <= n / 3 the first
+ * Stockham pass neither reads nor combines the two upper thirds and takes every element from in_len on as zero WITHOUT reading it --
+ * whatever lies there.  Any other n or in_len runs the full transform.  Arguments and error codes as the public entry point's. */
+int uzk_test_ntt_in_len(const void* d_in, uint64_t in_stride, void* d_out, uint64_t out_stride, uint64_t n, uint32_t batch,
+                        const uint64_t* coset_shift_mont, uint64_t in_len);
+
 /* Keccak-256 (padding byte 0x01) of `count` messages by the sponge of the verifier's transcript kernel (csrc/verify.hip), one lane
  * per message: message i is bytes [offsets[i], offsets[i + 1]) of msgs (count + 1 offsets), digests_out count x 32 bytes. */
 int uzk_test_keccak256(const uint8_t* msgs, const uint64_t* offsets, uint32_t count, uint8_t* digests_out);

@@ -65,30 +65,44 @@ def fold_and_commit(c, mono_pts, coefs_ints, degree):
     return commit_with_blinds(c.lagrange_wire, mono_pts, oc.ntt(oc.fr_from_ints(fold)), blinds, npow), blinds
 
 
-def oracle_chain(c, shuffle=True):
-    """c: ChainInputs.  Returns a dict of expected values (numpy arrays, wire format; commitments as affine [k, 8])."""
+def coset_tables(c):
+    """The circuit's coset tables from its coefficient polynomials (coset FFT over the 6n domain)."""
+    return np.stack([oc.ntt(oc.mul_var(pad(c.table_polys[i], c.m), c.k[1]), threads=4) for i in range(c.table_polys.shape[0])])
+
+
+def oracle_chain(c, shuffle=True, hide_w=None, with_wsel=True, tables=None, upto_t=False):
+    """c: ChainInputs.  Returns a dict of expected values (numpy arrays, wire format; commitments as affine [k, 8]).
+    hide_w: the wires' hiding degrees (default HIDE_W; c.t_len is HIDE_W's); with_wsel=False: a proof without wire selectors (their
+    three polynomials are zero and nothing is committed for them); tables: coset_tables(c) computed earlier; upto_t: stop after round
+    3's t, before the split."""
     from prover_chain import eval_plan, open_plan, r_plan
     from uzkge_amd.poly_commit import fr_to_int
     n, m = c.n, c.m
     out = {}
     mono_pts = {i: opy.wire_to_affine(c.mono_wire[i].tobytes()) for i in list(range(3)) + list(range(n, n + 3))}
     # ---- setup: the circuit's coset tables from its coefficient polynomials (coset FFT over the 6n domain)
-    tables = np.stack([oc.ntt(oc.mul_var(pad(c.table_polys[i], m), c.k[1]), threads=4) for i in range(c.table_polys.shape[0])])
+    if tables is None:
+        tables = coset_tables(c)
     out["tables"] = tables
     tpolys = [ints(c.table_polys[i]) for i in range(c.table_polys.shape[0])]
     # ---- round 1
-    evals9 = [c.w_evals[i] for i in range(5)] + [c.wsel_evals[i] for i in range(3)] + [c.pi_evals]
     from prover_chain import HIDE_W, HIDE_WSEL
-    blinds9 = [ints(c.blinds_w[i])[: HIDE_W[i]] for i in range(5)] + [ints(c.blinds_wsel[i])[:HIDE_WSEL] for i in range(3)] + [[]]
+    hide_w = HIDE_W if hide_w is None else hide_w
+    assert with_wsel or not shuffle
+    wsel_evals = c.wsel_evals if with_wsel else np.zeros_like(c.wsel_evals)
+    evals9 = [c.w_evals[i] for i in range(5)] + [wsel_evals[i] for i in range(3)] + [c.pi_evals]
+    blinds9 = [ints(c.blinds_w[i])[: hide_w[i]] for i in range(5)] + [ints(c.blinds_wsel[i])[:HIDE_WSEL] if with_wsel else [] for i in range(3)] + [[]]
     polys = [add_blinds(ints(oc.ntt(evals9[i], inverse=True)), blinds9[i], n) for i in range(9)]
-    out["cm_w_wsel"] = aff_wire([commit_with_blinds(c.lagrange_wire, mono_pts, evals9[i], blinds9[i], n) for i in range(8)])
+    if not upto_t:
+        out["cm_w_wsel"] = aff_wire([commit_with_blinds(c.lagrange_wire, mono_pts, evals9[i], blinds9[i], n) for i in range(8 if with_wsel else 5)])
     # ---- round 2
     g = fr_to_int(c.group_gen)
     group = oc.fr_from_ints([pow(g, i, opy.R) for i in range(n)])
     z_evals = oc.z_poly(c.w_evals, c.perm, group, c.k, c.beta, c.gamma)
     out["z_evals"] = z_evals
     polys.append(add_blinds(ints(oc.ntt(z_evals, inverse=True)), ints(c.blinds_z), n))
-    out["cm_z"] = aff_wire([commit_with_blinds(c.lagrange_wire, mono_pts, z_evals, ints(c.blinds_z), n)])
+    if not upto_t:
+        out["cm_z"] = aff_wire([commit_with_blinds(c.lagrange_wire, mono_pts, z_evals, ints(c.blinds_z), n)])
     out["coefs"] = np.stack([pad(oc.fr_from_ints(p), n + 3) for p in polys])
     # ---- round 3
     cos = np.stack([oc.ntt(oc.mul_var(pad(oc.fr_from_ints(p), m), c.k[1])) for p in polys])
@@ -101,6 +115,8 @@ def oracle_chain(c, shuffle=True):
     out["t_quotient"] = tq
     t = oc.mul_var(oc.ntt(tq, inverse=True), c.k1_inv)
     out["t"] = t
+    if upto_t:
+        return out
     t_int = ints(t)[: c.t_len]
     # split_t_and_commit (helpers.rs:1335-1394) with the reference's argument n + 2
     chunk_size, prev, rands = n + 2, 0, ints(c.t_rands)

@@ -78,7 +78,8 @@ class ChainInputs:
     """Everything a chain run consumes, as host arrays (no GPU needed): the reference's SRS files, the synthetic circuit
     and witness, the seeded challenges and blinds.  tests/chain_oracle.py computes the expected outputs from the same object."""
 
-    def __init__(self, n: int = 1 << 14, seed: int = 2024):
+    def __init__(self, n: int = 1 << 14, seed: int = 2024, lagrange_wire: np.ndarray = None):
+        """lagrange_wire: n commit bases to use where the reference has no lagrange-srs-{n}.bin (n < 4096: any valid points serve)."""
         self.n, self.m, self.seed = n, 6 * n, seed
         m = self.m
         rng = np.random.default_rng(seed)
@@ -88,7 +89,8 @@ class ChainInputs:
             a[..., 3] &= np.uint64(0x0FFFFFFFFFFFFFFF)
             return a
         # ---- parameters (reference files) and the combined commit bases
-        self.lagrange_wire = pc.parse_srs_g1_wire(open(os.path.join(GOLDEN, f"lagrange-srs-{n}.bin"), "rb").read())
+        self.lagrange_wire = (np.ascontiguousarray(lagrange_wire[:n]) if lagrange_wire is not None else
+                              pc.parse_srs_g1_wire(open(os.path.join(GOLDEN, f"lagrange-srs-{n}.bin"), "rb").read()))
         self.mono_wire = pc.srs_params_wire(open(os.path.join(GOLDEN, "srs-padding.bin"), "rb").read(), n)
         self.bases = np.concatenate([self.lagrange_wire, self.mono_wire[:3], self.mono_wire[n:n + 3]])      # n + 6 points
         # ---- synthetic circuit: witness evaluations, wire selectors, public input, permutation, per-circuit polynomials

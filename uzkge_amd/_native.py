@@ -182,6 +182,7 @@ TEST_PROTOTYPES = {
     "uzk_test_ed_raw_kat": (_I, [_I, _P, _P, _SZ]),
     "uzk_test_srs_weights_device": (_I, [_P, _U64, _P]),
     "uzk_test_lanes": (_I, [_I, _P, _P, ctypes.c_uint32, _P, _P, _P, ctypes.c_uint32, _U64, _P, ctypes.POINTER(ctypes.c_int)]),
+    "uzk_test_ntt_in_len": (_I, [_P, _U64, _P, _U64, _U64, ctypes.c_uint32, _P, _U64]),
 }
 
 

@@ -812,6 +812,15 @@ def ntt_batch_strided_device(d_in: int, in_stride: int, d_out: int, out_stride: 
                                               int(inverse), _ptr(cs) if cs is not None else None, int(sync)))
 
 
+def ntt_in_len_device(d_in: int, in_stride: int, d_out: int, out_stride: int, n: int, batch: int, in_len: int,
+                      coset_shift: Optional[np.ndarray] = None) -> None:
+    """uzk_test_ntt_in_len (test hook): the forward transform of ntt_batch_strided_device with the prover's statement that every
+    input vector is zero from index in_len on (0 = no statement).  Synchronous."""
+    cs = _fr4(coset_shift) if coset_shift is not None else None
+    check(lib.uzk_test_ntt_in_len(ctypes.c_void_p(d_in), in_stride, ctypes.c_void_p(d_out), out_stride, n, batch,
+                                  _ptr(cs) if cs is not None else None, in_len))
+
+
 def msm_batch_tail_device(srs: Srs, d_scalars: int, stride: int, n: int, batch: int, tail, tail_n: int, offset: int = 0) -> np.ndarray:
     """`tail`: a host array [batch, tail_n, 4] or a device address (int) of batch * tail_n elements."""
     out = np.zeros((batch, 12), dtype=np.uint64)

@@ -1871,6 +1871,22 @@ int uzk_test_lanes(int op, const void* const* d_polys, const uint64_t* lane_stri
     UZK_TRY(require_ready());
     return lanes_test(ctx(), op, d_polys, lane_strides, count, lens, pts, as_fp(args), lanes, len, reinterpret_cast<Fp*>(out), kernel);
 } catch (...) { return uzk::on_exception("uzk_test_lanes"); }
+// uzk_ntt_fr_batch_strided_device (forward) with ntt_run's in_len, which only the prover passes (prover.cpp derive_cosets, round 3)
+int uzk_test_ntt_in_len(const void* d_in, uint64_t in_stride, void* d_out, uint64_t out_stride, uint64_t n, uint32_t batch,
+                        const uint64_t* coset_shift_mont, uint64_t in_len) try {
+    API_LOCK;
+    if (!domain_supported(n)) {
+        set_error("no evaluation domain of size %llu (need 2^k, k <= %d, or 3 * 2^k, k <= %d)", (unsigned long long)n, UZK_NTT_MAX_LOG2, UZK_NTT_MAX_LOG2_MIXED);
+        return UZK_ERR_FFT;
+    }
+    if (!d_in || !d_out) { set_error("uzk_test_ntt_in_len: null pointer"); return UZK_ERR_PARAMETER; }
+    UZK_TRY(require_ready());
+    Ctx& c = ctx();
+    UZK_TRY(ntt_run(c, static_cast<const Fp*>(d_in), static_cast<Fp*>(d_out), n, false,
+                    coset_shift_mont ? as_fp(coset_shift_mont) : nullptr, batch, in_stride, out_stride, in_len));
+    UZK_HIP(hipStreamSynchronize(c.stream));
+    return UZK_OK;
+} catch (...) { return uzk::on_exception("uzk_test_ntt_in_len"); }
 
 /* ---- measurement -------------------------------------------------------------------------- */
 int uzk_profile_enable(int on) try {
