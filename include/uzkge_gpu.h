@@ -877,6 +877,42 @@ int uzk_cp_mask_prove_batch(const uint64_t* pk_mont, const uint64_t* cards_mont,
 int uzk_cp_mask_verify_batch(const uint64_t* pk_mont, const uint64_t* cards_mont, const uint64_t* e1_mont, const uint64_t* e2_mont,
                              const uint8_t* proofs, uint32_t m, uint8_t* verdict_out, uint64_t* challenges_out);
 
+/* ---- Anemoi-Jive over BN254's scalar field: hashes, the stream cipher, their traces (uzkge/src/anemoi) -------------------------------
+ * AnemoiJive254: 2 columns, 14 rounds, alpha = 5, g = 5, delta = 1 / g, the round keys of the Anemoi paper's pi rule; a sponge of rate
+ * 3 (eval_variable_length_hash, eval_stream_cipher).  Batches run one lane per item, every item of a call with the same lengths.
+ *   element   4 Montgomery words of Fr, as everywhere in this header; a word not below r is UZK_ERR_PARAMETER before the device is
+ *             touched
+ *   padding   a nonempty input whose length is a multiple of 3 is absorbed as it is and sigma = 1; any other (the empty one too) gets
+ *             a 1 and then zeros up to a multiple of 3, and sigma = 0.  sigma is added to y1 after the last absorbing permutation
+ *   outputs   x0, x1, y0 of the state after absorbing, then of every further permutation; a hash is the first of them
+ *   trace     n x P x UZK_ANEMOI_TRACE_ELEMS elements, P = uzk_anemoi_permutations(len, out_len).  Per item its P permutations in
+ *             the order they run, and per permutation 64 elements -- the fields of AnemoiVLHTrace / AnemoiStreamCipherTrace:
+ *               [0, 4)    before_permutation                              x0 x1 y0 y1
+ *               [4, 60)   intermediate_values_before_constant_additions   round 0 .. 13, each x0 x1 y0 y1 after that round's S-box
+ *               [60, 64)  after_permutation                               x0 x1 y0 y1 (before sigma is added, as in the reference)
+ * A batch of 0 or above UZK_ANEMOI_MAX_BATCH, len above UZK_ANEMOI_MAX_INPUT and out_len outside 1 .. UZK_ANEMOI_MAX_OUTPUT are
+ * UZK_ERR_PARAMETER.  len == 0 is legal (inputs_mont may then be NULL): the single chunk (1, 0, 0). */
+#define UZK_ANEMOI_MAX_BATCH 1048576
+#define UZK_ANEMOI_MAX_INPUT 96
+#define UZK_ANEMOI_MAX_OUTPUT 96
+#define UZK_ANEMOI_TRACE_ELEMS 64
+/* states_mont, out_mont: n x (x0 x1 y0 y1).  One permutation each. */
+int uzk_anemoi_permute_batch(const uint64_t* states_mont, size_t n, uint64_t* out_mont);
+/* inputs_mont: n x len elements; out_mont: n elements; trace_out optional (layout above). */
+int uzk_anemoi_hash_batch(const uint64_t* inputs_mont, uint32_t len, size_t n, uint64_t* out_mont, uint64_t* trace_out);
+/* out_mont: n x out_len elements; trace_out optional. */
+int uzk_anemoi_stream_batch(const uint64_t* inputs_mont, uint32_t len, size_t n, uint32_t out_len, uint64_t* out_mont, uint64_t* trace_out);
+/* P: how many permutations one item runs; out_len == 0: a hash.  Pure arithmetic, no device. */
+uint32_t uzk_anemoi_permutations(uint32_t len, uint32_t out_len);
+/* The zk-friendly reveals (shuffle/src/reveal.rs reveal0 / verify_reveal0 over chaum_pedersen/dl.rs prove0 / verify0): the arguments,
+ * the blob and the verdict codes of uzk_cp_reveal_prove_batch / uzk_cp_reveal_verify_batch, with
+ * c_i = uzk_anemoi_hash(e1.x e1.y G.x G.y reveal.x reveal.y pk.x pk.y a.x a.y b.x b.y) taken as an integer below r, mod L, in place of
+ * the Keccak transcript.  A point enters the hash as into_affine().xy().unwrap_or_default() gives it: the identity (0, 1) as (0, 0) --
+ * SUPPOSED from upstream arkworks (xy() of the identity is None), not verified against the reference's fork. */
+int uzk_cp_reveal_prove0_batch(const uint64_t* sk, const uint64_t* e1_mont, const uint64_t* omegas, uint32_t m, uint64_t* reveal_out, uint64_t* pk_out,
+                               uint8_t* proofs_out);
+int uzk_cp_reveal_verify0_batch(const uint64_t* statements_mont, const uint8_t* proofs, uint32_t m, uint8_t* verdict_out, uint64_t* challenges_out);
+
 /* ---- synthetic workloads (bench / tests; generated on device, nothing uploaded) -------- */
 /* d_points[i] = (i + 1) * Q with Q = seed_scalar * G: n distinct valid G1 points whose discrete
  * logs relative to Q are known, so MSM(points, s) == (sum_i s_i (i+1)) * Q for any size. */

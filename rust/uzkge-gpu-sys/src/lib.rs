@@ -557,6 +557,81 @@ pub fn cp_reveal_verify_batch(statements: &[RevealStatement], proofs: &[u8]) -> 
     Ok(verdict)
 }
 
+/// `cp_reveal_prove_batch` with the zk-friendly challenge (`uzk_cp_reveal_prove0_batch`, dl.rs `prove0`): the Anemoi-Jive hash of the
+/// twelve coordinates in place of the Keccak transcript; the same blob.
+pub fn cp_reveal_prove0_batch(sk: &Limbs, e1: &[EdPoint], omegas: &[Limbs]) -> Result<(Vec<EdPoint>, EdPoint, Vec<u8>), Error> {
+    let m = e1.len();
+    if m == 0 || m > UZK_CP_MAX_BATCH as usize || omegas.len() != m {
+        return Err(Error::Parameter);
+    }
+    let mut reveal = vec![[[0u64; 4]; 2]; m];
+    let mut pk: EdPoint = [[0u64; 4]; 2];
+    let mut proofs = vec![0u8; m * UZK_CP_PROOF_BYTES as usize];
+    check(unsafe {
+        uzk_cp_reveal_prove0_batch(sk.as_ptr(), e1.as_ptr() as *const u64, omegas.as_ptr() as *const u64, m as u32, reveal.as_mut_ptr() as *mut u64,
+                                   pk.as_mut_ptr() as *mut u64, proofs.as_mut_ptr())
+    })?;
+    Ok((reveal, pk, proofs))
+}
+
+/// `cp_reveal_verify_batch` for the proofs of `prove0` (`uzk_cp_reveal_verify0_batch`): the same verdict bytes.
+pub fn cp_reveal_verify0_batch(statements: &[RevealStatement], proofs: &[u8]) -> Result<Vec<u8>, Error> {
+    let m = statements.len();
+    if m == 0 || m > UZK_CP_MAX_BATCH as usize || proofs.len() != m * UZK_CP_PROOF_BYTES as usize {
+        return Err(Error::Parameter);
+    }
+    let mut verdict = vec![0u8; m];
+    check(unsafe { uzk_cp_reveal_verify0_batch(statements.as_ptr() as *const u64, proofs.as_ptr(), m as u32, verdict.as_mut_ptr(), std::ptr::null_mut()) })?;
+    Ok(verdict)
+}
+
+// ---- Anemoi-Jive: hashes, the stream cipher, their traces ----------------------------------------------------------------------------
+/// One permutation's share of a trace: before (x0 x1 y0 y1), the state after each of the 14 rounds' S-boxes, after.
+pub type AnemoiTraceBlock = [Limbs; 64];
+
+/// How many permutations one item of `len` inputs runs (`uzk_anemoi_permutations`); `out_len` 0: a hash.
+pub fn anemoi_permutations(len: usize, out_len: usize) -> usize {
+    unsafe { uzk_anemoi_permutations(len as u32, out_len as u32) as usize }
+}
+
+/// One permutation of every state x0 x1 y0 y1 (`uzk_anemoi_permute_batch`).
+pub fn anemoi_permute_batch(states: &[[Limbs; 4]]) -> Result<Vec<[Limbs; 4]>, Error> {
+    if states.is_empty() || states.len() > UZK_ANEMOI_MAX_BATCH as usize {
+        return Err(Error::Parameter);
+    }
+    let mut out = vec![[[0u64; 4]; 4]; states.len()];
+    check(unsafe { uzk_anemoi_permute_batch(states.as_ptr() as *const u64, states.len(), out.as_mut_ptr() as *mut u64) })?;
+    Ok(out)
+}
+
+/// The hash of every input (`uzk_anemoi_hash_batch`): `inputs` holds n items of `len` elements each; with `want_trace` also
+/// n x P trace blocks, P = `anemoi_permutations(len, 0)`.
+pub fn anemoi_hash_batch(inputs: &[Limbs], len: usize, n: usize, want_trace: bool) -> Result<(Vec<Limbs>, Option<Vec<AnemoiTraceBlock>>), Error> {
+    if n == 0 || n > UZK_ANEMOI_MAX_BATCH as usize || len > UZK_ANEMOI_MAX_INPUT as usize || inputs.len() != n * len {
+        return Err(Error::Parameter);
+    }
+    let mut out = vec![[0u64; 4]; n];
+    let mut trace = if want_trace { Some(vec![[[0u64; 4]; 64]; n * anemoi_permutations(len, 0)]) } else { None };
+    let tp = trace.as_mut().map_or(std::ptr::null_mut(), |t| t.as_mut_ptr() as *mut u64);
+    check(unsafe { uzk_anemoi_hash_batch(inputs.as_ptr() as *const u64, len as u32, n, out.as_mut_ptr() as *mut u64, tp) })?;
+    Ok((out, trace))
+}
+
+/// `out_len` outputs of the stream cipher per input (`uzk_anemoi_stream_batch`); with `want_trace` also n x P trace blocks,
+/// P = `anemoi_permutations(len, out_len)`.
+pub fn anemoi_stream_batch(inputs: &[Limbs], len: usize, n: usize, out_len: usize, want_trace: bool) -> Result<(Vec<Limbs>, Option<Vec<AnemoiTraceBlock>>), Error> {
+    if n == 0 || n > UZK_ANEMOI_MAX_BATCH as usize || len > UZK_ANEMOI_MAX_INPUT as usize || inputs.len() != n * len || out_len == 0 ||
+        out_len > UZK_ANEMOI_MAX_OUTPUT as usize
+    {
+        return Err(Error::Parameter);
+    }
+    let mut out = vec![[0u64; 4]; n * out_len];
+    let mut trace = if want_trace { Some(vec![[[0u64; 4]; 64]; n * anemoi_permutations(len, out_len)]) } else { None };
+    let tp = trace.as_mut().map_or(std::ptr::null_mut(), |t| t.as_mut_ptr() as *mut u64);
+    check(unsafe { uzk_anemoi_stream_batch(inputs.as_ptr() as *const u64, len as u32, n, out_len as u32, out.as_mut_ptr() as *mut u64, tp) })?;
+    Ok((out, trace))
+}
+
 // ---- masking a card and the remask of a shuffle --------------------------------------------------------------------------------------
 /// One table of a remask key: [84][4] entries of (x, y, d x y).
 pub type RemarkTable = Vec<[Limbs; 3]>;

@@ -8,7 +8,8 @@ fieldops.hip is left out: it holds the test hooks, whose typed KAT ops and signa
 are generated from this very list).  The .cpp files stay in the source set: the Makefile compiles them as HIP (-x hip), so one that
 reaches lz29.hpp (api.cpp, through g2_29.hpp for its wire structs) could instantiate LzOps the day it gains a kernel.  With the G2 group law (g2_29.hpp, fq2_29.hpp) the list
 holds every typed operation of the G2 MSM's accumulator and XYZZ additions, the dual products with an un-normalised K = 4 operand
-among them.  The list is written as an X-macro next to lz29.hpp:
+among them; with Anemoi-Jive (anemoi29.hpp, reached from anemoi.hip and from edwards.hip) the sums of its linear layer, up to
+Lz<Fr29, 3, 837>.  The list is written as an X-macro next to lz29.hpp:
 
     LZ29_SIG(index, field, op, arity, Ka, Va, Kb, Vb, Kc, Vc, Kd, Vd, Kr, Vr)
 

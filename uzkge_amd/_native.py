@@ -146,6 +146,12 @@ PROTOTYPES = {
     "uzk_remark_batch": (_I, [_U64, _P, _P, _P, _P, ctypes.c_uint32, _P, _P, _P]),
     "uzk_cp_mask_prove_batch": (_I, [_P, _P, _P, _P, ctypes.c_uint32, _P, _P, _P]),
     "uzk_cp_mask_verify_batch": (_I, [_P, _P, _P, _P, _P, ctypes.c_uint32, _P, _P]),
+    "uzk_anemoi_permute_batch": (_I, [_P, _SZ, _P]),
+    "uzk_anemoi_hash_batch": (_I, [_P, ctypes.c_uint32, _SZ, _P, _P]),
+    "uzk_anemoi_stream_batch": (_I, [_P, ctypes.c_uint32, _SZ, ctypes.c_uint32, _P, _P]),
+    "uzk_anemoi_permutations": (ctypes.c_uint32, [ctypes.c_uint32, ctypes.c_uint32]),
+    "uzk_cp_reveal_prove0_batch": (_I, [_P, _P, _P, ctypes.c_uint32, _P, _P, _P]),
+    "uzk_cp_reveal_verify0_batch": (_I, [_P, _P, ctypes.c_uint32, _P, _P]),
     "uzk_synth_points_arith": (_I, [_P, _SZ, _P]),
     "uzk_synth_points_random": (_I, [_P, _SZ, _U64]),
     "uzk_synth_scalars": (_I, [_P, _SZ, _U64]),
@@ -296,6 +302,10 @@ CP_PROOF_BYTES = 160
 CP_MAX_BATCH = 65536
 ED_MAX_BATCH = 1 << 20
 REMARK_ITERATIONS = 84
+ANEMOI_MAX_BATCH = 1 << 20
+ANEMOI_MAX_INPUT = 96
+ANEMOI_MAX_OUTPUT = 96
+ANEMOI_TRACE_ELEMS = 64
 
 
 class G16VkDesc(ctypes.Structure):

@@ -1182,9 +1182,9 @@ def ed_unmask_batch(e2, reveals) -> np.ndarray:
     return out[:r.shape[1]]
 
 
-def cp_reveal_prove_batch(sk, e1, omegas):
-    """uzk_cp_reveal_prove_batch: sk [4] and omegas [m, 4] plain integers below L, e1 [m, 8] subgroup points.  Returns
-    (reveal [m, 8], pk [8], proofs: uint8 [m, 160])."""
+def cp_reveal_prove_batch(sk, e1, omegas, anemoi: bool = False):
+    """uzk_cp_reveal_prove_batch (anemoi: uzk_cp_reveal_prove0_batch, the zk-friendly challenge): sk [4] and omegas [m, 4] plain
+    integers below L, e1 [m, 8] subgroup points.  Returns (reveal [m, 8], pk [8], proofs: uint8 [m, 160])."""
     k = np.ascontiguousarray(sk, dtype=np.uint64).reshape(4)
     p = np.ascontiguousarray(e1, dtype=np.uint64).reshape(-1, 8)
     w = np.ascontiguousarray(omegas, dtype=np.uint64).reshape(-1, 4)
@@ -1192,12 +1192,13 @@ def cp_reveal_prove_batch(sk, e1, omegas):
     m = p.shape[0]
     reveal, pk = np.zeros((max(m, 1), 8), dtype=np.uint64), np.zeros(8, dtype=np.uint64)
     proofs = np.zeros((max(m, 1), N.CP_PROOF_BYTES), dtype=np.uint8)
-    check(lib.uzk_cp_reveal_prove_batch(_ptr(k), _ptr(p), _ptr(w), m, _ptr(reveal), _ptr(pk), proofs.ctypes.data_as(ctypes.c_void_p)))
+    call = lib.uzk_cp_reveal_prove0_batch if anemoi else lib.uzk_cp_reveal_prove_batch
+    check(call(_ptr(k), _ptr(p), _ptr(w), m, _ptr(reveal), _ptr(pk), proofs.ctypes.data_as(ctypes.c_void_p)))
     return reveal[:m], pk, proofs[:m]
 
 
-def cp_reveal_verify_batch(statements, proofs, want_challenges: bool = False):
-    """uzk_cp_reveal_verify_batch: statements [m, 6, 4] (e1, reveal, pk: x and y each -- the public signals of the Groth16 reveal proof
+def cp_reveal_verify_batch(statements, proofs, want_challenges: bool = False, anemoi: bool = False):
+    """uzk_cp_reveal_verify_batch (anemoi: uzk_cp_reveal_verify0_batch): statements [m, 6, 4] (e1, reveal, pk: x and y each -- the public signals of the Groth16 reveal proof
     of the same statement), proofs m blobs of 160 bytes.  Returns verdict [m] (0 accepted, 1 .. 5 the first failing check), and with
     want_challenges also c [m, 4] as plain integers."""
     raw = _u8(proofs, N.CP_PROOF_BYTES)
@@ -1206,8 +1207,52 @@ def cp_reveal_verify_batch(statements, proofs, want_challenges: bool = False):
     verdict = np.zeros(max(m, 1), dtype=np.uint8)
     ch = np.zeros((max(m, 1), 4), dtype=np.uint64) if want_challenges else None
     vp = lambda arr: arr.ctypes.data_as(ctypes.c_void_p)
-    check(lib.uzk_cp_reveal_verify_batch(_ptr(st), vp(raw), m, vp(verdict), _ptr(ch) if want_challenges else None))
+    call = lib.uzk_cp_reveal_verify0_batch if anemoi else lib.uzk_cp_reveal_verify_batch
+    check(call(_ptr(st), vp(raw), m, vp(verdict), _ptr(ch) if want_challenges else None))
     return (verdict[:m], ch[:m]) if want_challenges else verdict[:m]
+
+
+def anemoi_permutations(length: int, out_len: int = 0) -> int:
+    """uzk_anemoi_permutations: how many permutations one item of `length` inputs runs; out_len = 0: a hash."""
+    return int(lib.uzk_anemoi_permutations(length, out_len))
+
+
+def anemoi_permute_batch(states) -> np.ndarray:
+    """uzk_anemoi_permute_batch: states [n, 4, 4] (x0 x1 y0 y1, Montgomery words).  Returns [n, 4, 4]."""
+    s = np.ascontiguousarray(states, dtype=np.uint64).reshape(-1, 4, 4)
+    out = np.zeros((max(s.shape[0], 1), 4, 4), dtype=np.uint64)
+    check(lib.uzk_anemoi_permute_batch(_ptr(s), s.shape[0], _ptr(out)))
+    return out[:s.shape[0]]
+
+
+def _anemoi_inputs(inputs, length):
+    x = np.ascontiguousarray(inputs, dtype=np.uint64)
+    if length is None:
+        assert x.ndim == 3 and x.shape[2] == 4, "inputs [n, len, 4] (or pass length= with anything that reshapes to it)"
+        length = x.shape[1]
+    n = x.size // (4 * length) if length else (x.shape[0] if x.ndim else 0)
+    return x.reshape(n, length, 4), n, length
+
+
+def anemoi_hash_batch(inputs, length: int = None, want_trace: bool = False):
+    """uzk_anemoi_hash_batch: inputs [n, len, 4] (len = 0: [n, 0, 4]).  Returns out [n, 4], and with want_trace also the trace
+    [n, P, 64, 4]: per permutation before (4 elements), the 14 rounds (56), after (4)."""
+    x, n, length = _anemoi_inputs(inputs, length)
+    out = np.zeros((max(n, 1), 4), dtype=np.uint64)
+    perms = anemoi_permutations(length, 0)
+    tr = np.zeros((max(n, 1), perms, N.ANEMOI_TRACE_ELEMS, 4), dtype=np.uint64) if want_trace else None
+    check(lib.uzk_anemoi_hash_batch(_ptr(x) if x.size else None, length, n, _ptr(out), _ptr(tr) if want_trace else None))
+    return (out[:n], tr[:n]) if want_trace else out[:n]
+
+
+def anemoi_stream_batch(inputs, out_len: int, length: int = None, want_trace: bool = False):
+    """uzk_anemoi_stream_batch: inputs [n, len, 4].  Returns out [n, out_len, 4], and with want_trace also the trace [n, P, 64, 4]."""
+    x, n, length = _anemoi_inputs(inputs, length)
+    out = np.zeros((max(n, 1), max(out_len, 1), 4), dtype=np.uint64)
+    perms = anemoi_permutations(length, out_len)
+    tr = np.zeros((max(n, 1), perms, N.ANEMOI_TRACE_ELEMS, 4), dtype=np.uint64) if want_trace else None
+    check(lib.uzk_anemoi_stream_batch(_ptr(x) if x.size else None, length, n, out_len, _ptr(out), _ptr(tr) if want_trace else None))
+    return (out[:n], tr[:n]) if want_trace else out[:n]
 
 
 class RemarkKey:

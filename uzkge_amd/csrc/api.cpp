@@ -10,6 +10,7 @@
 #include <exception>
 #include <new>
 
+#include "anemoi29.hpp"
 #include "ctx.hpp"
 #include "fq12_29.hpp"
 #include "g2_29.hpp"
@@ -1481,23 +1482,85 @@ int uzk_ed_unmask_batch(const uint64_t* e2_mont, const uint64_t* reveals_mont, u
     return ed_sum_run(ctx(), as_ed(e2_mont), as_ed(reveals_mont), k, n, as_ed(out_mont));
 } catch (...) { return uzk::on_exception("uzk_ed_unmask_batch"); }
 
+// the Keccak transcript (anemoi == false) and the zk-friendly one share everything but the challenge
+static int cp_reveal_prove(const char* who, bool anemoi, const uint64_t* sk, const uint64_t* e1_mont, const uint64_t* omegas, uint32_t m, uint64_t* reveal_out,
+                           uint64_t* pk_out, uint8_t* proofs_out) {
+    if (m == 0 || m > UZK_CP_MAX_BATCH) { set_error("%s: %u cards (1 .. %d per call)", who, m, UZK_CP_MAX_BATCH); return UZK_ERR_PARAMETER; }
+    if (!sk || !e1_mont || !omegas || !reveal_out || !pk_out || !proofs_out) { set_error("%s: null pointer", who); return UZK_ERR_PARAMETER; }
+    UZK_TRY(ed_require_canonical(who, "e1", e1_mont, m));
+    UZK_TRY(require_ready());
+    return cp_prove_run(ctx(), as_fp(sk), as_ed(e1_mont), as_fp(omegas), m, as_ed(reveal_out), as_ed(pk_out), proofs_out, anemoi);
+}
+static int cp_reveal_verify(const char* who, bool anemoi, const uint64_t* statements_mont, const uint8_t* proofs, uint32_t m, uint8_t* verdict_out,
+                            uint64_t* challenges_out) {
+    if (m == 0 || m > UZK_CP_MAX_BATCH) { set_error("%s: %u proofs (1 .. %d per call)", who, m, UZK_CP_MAX_BATCH); return UZK_ERR_PARAMETER; }
+    if (!statements_mont || !proofs || !verdict_out) { set_error("%s: null pointer", who); return UZK_ERR_PARAMETER; }
+    UZK_TRY(require_ready());
+    return cp_verify_run(ctx(), as_ed(statements_mont), proofs, m, verdict_out, reinterpret_cast<Fp*>(challenges_out), anemoi);
+}
+
 int uzk_cp_reveal_prove_batch(const uint64_t* sk, const uint64_t* e1_mont, const uint64_t* omegas, uint32_t m, uint64_t* reveal_out, uint64_t* pk_out,
                               uint8_t* proofs_out) try {
     API_LOCK;
-    if (m == 0 || m > UZK_CP_MAX_BATCH) { set_error("uzk_cp_reveal_prove_batch: %u cards (1 .. %d per call)", m, UZK_CP_MAX_BATCH); return UZK_ERR_PARAMETER; }
-    if (!sk || !e1_mont || !omegas || !reveal_out || !pk_out || !proofs_out) { set_error("uzk_cp_reveal_prove_batch: null pointer"); return UZK_ERR_PARAMETER; }
-    UZK_TRY(ed_require_canonical("uzk_cp_reveal_prove_batch", "e1", e1_mont, m));
-    UZK_TRY(require_ready());
-    return cp_prove_run(ctx(), as_fp(sk), as_ed(e1_mont), as_fp(omegas), m, as_ed(reveal_out), as_ed(pk_out), proofs_out);
+    return cp_reveal_prove("uzk_cp_reveal_prove_batch", false, sk, e1_mont, omegas, m, reveal_out, pk_out, proofs_out);
 } catch (...) { return uzk::on_exception("uzk_cp_reveal_prove_batch"); }
 
 int uzk_cp_reveal_verify_batch(const uint64_t* statements_mont, const uint8_t* proofs, uint32_t m, uint8_t* verdict_out, uint64_t* challenges_out) try {
     API_LOCK;
-    if (m == 0 || m > UZK_CP_MAX_BATCH) { set_error("uzk_cp_reveal_verify_batch: %u proofs (1 .. %d per call)", m, UZK_CP_MAX_BATCH); return UZK_ERR_PARAMETER; }
-    if (!statements_mont || !proofs || !verdict_out) { set_error("uzk_cp_reveal_verify_batch: null pointer"); return UZK_ERR_PARAMETER; }
-    UZK_TRY(require_ready());
-    return cp_verify_run(ctx(), as_ed(statements_mont), proofs, m, verdict_out, reinterpret_cast<Fp*>(challenges_out));
+    return cp_reveal_verify("uzk_cp_reveal_verify_batch", false, statements_mont, proofs, m, verdict_out, challenges_out);
 } catch (...) { return uzk::on_exception("uzk_cp_reveal_verify_batch"); }
+
+int uzk_cp_reveal_prove0_batch(const uint64_t* sk, const uint64_t* e1_mont, const uint64_t* omegas, uint32_t m, uint64_t* reveal_out, uint64_t* pk_out,
+                               uint8_t* proofs_out) try {
+    API_LOCK;
+    return cp_reveal_prove("uzk_cp_reveal_prove0_batch", true, sk, e1_mont, omegas, m, reveal_out, pk_out, proofs_out);
+} catch (...) { return uzk::on_exception("uzk_cp_reveal_prove0_batch"); }
+
+int uzk_cp_reveal_verify0_batch(const uint64_t* statements_mont, const uint8_t* proofs, uint32_t m, uint8_t* verdict_out, uint64_t* challenges_out) try {
+    API_LOCK;
+    return cp_reveal_verify("uzk_cp_reveal_verify0_batch", true, statements_mont, proofs, m, verdict_out, challenges_out);
+} catch (...) { return uzk::on_exception("uzk_cp_reveal_verify0_batch"); }
+
+/* ---- Anemoi-Jive: hashes, the stream cipher, their traces ---------------------------------------- */
+// every element enters the lazy limbs as canonical words: anything else is refused before the device is touched
+static int anemoi_require_canonical(const char* who, const uint64_t* words, size_t elems, size_t per_item) {
+    const size_t bad = ed_first_noncanonical(as_fp(words), elems);
+    if (bad < elems) { set_error("%s: element %zu of item %zu is not below r", who, bad % per_item, bad / per_item); return UZK_ERR_PARAMETER; }
+    return UZK_OK;
+}
+static int anemoi_sponge(const char* who, const uint64_t* inputs_mont, uint32_t len, size_t n, uint32_t out_len, uint64_t* out_mont, uint64_t* trace_out) {
+    if (n == 0 || n > UZK_ANEMOI_MAX_BATCH) { set_error("%s: %zu items (1 .. %d per call)", who, n, UZK_ANEMOI_MAX_BATCH); return UZK_ERR_PARAMETER; }
+    if (len > UZK_ANEMOI_MAX_INPUT) { set_error("%s: %u input elements (at most %d)", who, len, UZK_ANEMOI_MAX_INPUT); return UZK_ERR_PARAMETER; }
+    if ((len > 0 && !inputs_mont) || !out_mont) { set_error("%s: null pointer", who); return UZK_ERR_PARAMETER; }
+    if (len > 0) UZK_TRY(anemoi_require_canonical(who, inputs_mont, n * len, len));
+    UZK_TRY(require_ready());
+    return anemoi_sponge_run(ctx(), as_fp(inputs_mont), len, n, out_len, reinterpret_cast<Fp*>(out_mont), reinterpret_cast<Fp*>(trace_out));
+}
+
+int uzk_anemoi_permute_batch(const uint64_t* states_mont, size_t n, uint64_t* out_mont) try {
+    API_LOCK;
+    if (n == 0 || n > UZK_ANEMOI_MAX_BATCH) { set_error("uzk_anemoi_permute_batch: %zu states (1 .. %d per call)", n, UZK_ANEMOI_MAX_BATCH); return UZK_ERR_PARAMETER; }
+    if (!states_mont || !out_mont) { set_error("uzk_anemoi_permute_batch: null pointer"); return UZK_ERR_PARAMETER; }
+    UZK_TRY(anemoi_require_canonical("uzk_anemoi_permute_batch", states_mont, 4 * n, 4));
+    UZK_TRY(require_ready());
+    return anemoi_permute_run(ctx(), as_fp(states_mont), n, reinterpret_cast<Fp*>(out_mont));
+} catch (...) { return uzk::on_exception("uzk_anemoi_permute_batch"); }
+
+int uzk_anemoi_hash_batch(const uint64_t* inputs_mont, uint32_t len, size_t n, uint64_t* out_mont, uint64_t* trace_out) try {
+    API_LOCK;
+    return anemoi_sponge("uzk_anemoi_hash_batch", inputs_mont, len, n, 0, out_mont, trace_out);
+} catch (...) { return uzk::on_exception("uzk_anemoi_hash_batch"); }
+
+int uzk_anemoi_stream_batch(const uint64_t* inputs_mont, uint32_t len, size_t n, uint32_t out_len, uint64_t* out_mont, uint64_t* trace_out) try {
+    API_LOCK;
+    if (out_len == 0 || out_len > UZK_ANEMOI_MAX_OUTPUT) {
+        set_error("uzk_anemoi_stream_batch: %u outputs (1 .. %d)", out_len, UZK_ANEMOI_MAX_OUTPUT);
+        return UZK_ERR_PARAMETER;
+    }
+    return anemoi_sponge("uzk_anemoi_stream_batch", inputs_mont, len, n, out_len, out_mont, trace_out);
+} catch (...) { return uzk::on_exception("uzk_anemoi_stream_batch"); }
+
+uint32_t uzk_anemoi_permutations(uint32_t len, uint32_t out_len) { return uzk::anemoi_permutations(len, out_len); }
 
 int uzk_remark_key_create(const uint64_t* pk_mont, uint64_t* key_out) try {
     API_LOCK;

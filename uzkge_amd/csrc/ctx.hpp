@@ -314,8 +314,11 @@ size_t ed_first_noncanonical(const Fp* words, size_t count);
 int ed_check_run(Ctx& c, const EdAffine* pts, size_t n, uint8_t* status_out);
 int ed_mul_run(Ctx& c, const EdAffine* pts, bool shared_base, const Fp* scalars, size_t n, EdAffine* out);
 int ed_sum_run(Ctx& c, const EdAffine* e2, const EdAffine* rows, uint32_t k, uint32_t n, EdAffine* out);
-int cp_verify_run(Ctx& c, const EdAffine* statements, const uint8_t* proofs, uint32_t m, uint8_t* verdict_out, Fp* challenges_out);
-int cp_prove_run(Ctx& c, const Fp* sk, const EdAffine* e1, const Fp* omegas, uint32_t m, EdAffine* reveal_out, EdAffine* pk_out, uint8_t* proofs_out);
+int cp_verify_run(Ctx& c, const EdAffine* statements, const uint8_t* proofs, uint32_t m, uint8_t* verdict_out, Fp* challenges_out, bool anemoi);
+int cp_prove_run(Ctx& c, const Fp* sk, const EdAffine* e1, const Fp* omegas, uint32_t m, EdAffine* reveal_out, EdAffine* pk_out, uint8_t* proofs_out,
+                 bool anemoi);
+int anemoi_permute_run(Ctx& c, const Fp* states, size_t n, Fp* out);                                          // anemoi.hip
+int anemoi_sponge_run(Ctx& c, const Fp* inputs, uint32_t len, size_t n, uint32_t out_len, Fp* out, Fp* trace_out);
 int ed_raw_op_device(Ctx& c, int op, const uint32_t* in, uint32_t* out, size_t n);
 // edwards.hip: the Chaum-Pedersen proofs of a mask; remask keys (process-wide handles: T_pk on the device), the tables and the remask
 int cp_mask_prove_run(Ctx& c, const EdAffine* pk, const EdAffine* cards, const Fp* rs, const Fp* omegas, uint32_t m, EdAffine* e1_out, EdAffine* e2_out,

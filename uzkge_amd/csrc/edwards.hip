@@ -6,7 +6,9 @@
 //   ed_sum          one lane per card j: sum_k P_kj over k rows of n points, or e2_j - sum_k P_kj (unmask)
 //   cp_transcript   one lane per DL proof over the parameters (g, h) and the statement (u, v): Keccak-256 of the 448-byte transcript
 //                   label | "DL" | g, h, u, v, a, b; c = digest mod L; for a prover also r = omega + c secret mod L and the proof blob.
-//                   A reveal is (e1, G; reveal, pk) under "Revealing", a mask (G, pk; e1, e2 - card) under "Masking"
+//                   A reveal is (e1, G; reveal, pk) under "Revealing", a mask (G, pk; e1, e2 - card) under "Masking".  The zk-friendly
+//                   reveal (dl.rs prove0 / verify0) is the same lane in its second transcript mode: c = the Anemoi-Jive hash of the
+//                   twelve coordinates (anemoi29.hpp, four permutations), taken as an integer below r, mod L
 //   cp_mask_diff    one lane per mask proof: e2 - card in affine, the second point of its statement
 //   cp_check        ONE launch for the two chains of a verification, each kind of lane in workgroups of its own:
 //                     one lane per point (a reveal: e1, reveal, pk; a mask: pk, card, e1, e2; then a and b from the 160-byte blob):
@@ -27,6 +29,7 @@
 #include <map>
 #include <mutex>
 
+#include "anemoi29.hpp"
 #include "ctx.hpp"
 #include "ed29.hpp"
 
@@ -94,7 +97,9 @@ struct CpStatement {
     uint32_t s_c0, s_c1, s_c2, s_c3;
     uint32_t n_cls;
     CpLabel label;
+    uint32_t transcript;               // kCpKeccak: Keccak-256 under `label`; kCpAnemoi: the Anemoi-Jive hash of the twelve coordinates
 };
+constexpr uint32_t kCpKeccak = 0, kCpAnemoi = 1;
 __device__ __forceinline__ EdAffine cp_at(const EdAffine* p, uint32_t stride, uint32_t i) { return p ? p[(size_t)i * stride] : ed_generator(); }
 
 // a (which = 0) or b (which = 1) of a blob in Montgomery words; false (and zeros) when a word is not below q
@@ -104,6 +109,22 @@ __device__ __forceinline__ bool cp_blob_point(const uint8_t* blob, uint32_t whic
     p->x = canonical ? Fr::to_mont(x) : Fr::zero();
     p->y = canonical ? Fr::to_mont(y) : Fr::zero();
     return canonical;
+}
+
+// Coordinate k (g.x g.y h.x h.y u.x u.y v.x v.y a.x a.y b.x b.y) of proof i as the Anemoi transcript takes it: canonical Montgomery
+// words, the identity as anemoi_cp_point_words encodes it.  A point with a word not below q -- a verifier's statement and blob are
+// not checked before this lane runs -- enters as zeros: the limbs' contract holds, and the point lanes of cp_check give that proof
+// verdict 1 whatever its challenge is.
+__device__ __forceinline__ Fp cp_anemoi_word(const CpStatement& s, const uint8_t* proofs_in, const EdAffine* ab, uint32_t i, uint32_t k) {
+    const uint32_t pt = k >> 1;
+    EdAffine p;
+    if (pt < 4) p = pt == 0 ? cp_at(s.g, s.s_g, i) : pt == 1 ? cp_at(s.h, s.s_h, i) : pt == 2 ? cp_at(s.u, s.s_u, i) : cp_at(s.v, s.s_v, i);
+    else if (proofs_in) (void)cp_blob_point(proofs_in + (size_t)i * UZK_CP_PROOF_BYTES, pt - 4, &p);
+    else p = ab[2 * (size_t)i + (pt - 4)];
+    if (!ed_coord_canonical(p.x) || !ed_coord_canonical(p.y)) { p.x = Fr::zero(); p.y = Fr::zero(); }
+    Fp x, y;
+    anemoi_cp_point_words(p.x, p.y, &x, &y);
+    return (k & 1) ? y : x;
 }
 
 // c_i (plain words, below L) from the statement and a, b -- read from the blobs (a verifier: plain big-endian words as they are) or,
@@ -127,7 +148,15 @@ __global__ __launch_bounds__(kEdBlock) void cp_transcript_kernel(CpStatement s, 
 #pragma unroll
         for (int k = 0; k < 2; ++k) { w[8 + 2 * k] = Fr::from_mont(ab[2 * (size_t)i + k].x); w[9 + 2 * k] = Fr::from_mont(ab[2 * (size_t)i + k].y); }
     }
-    const Fp c = ed_mod_order(cp_transcript_digest(w, s.label));
+    Fp digest;
+    if (s.transcript == kCpAnemoi) {
+        Fp h;
+        anemoi::sponge([&](uint32_t k) { return cp_anemoi_word(s, proofs_in, ab, i, k); }, 12, 0, &h, nullptr);
+        digest = Fr::from_mont(h);                                 // an integer below r: floor(r / L) = 7
+    } else {
+        digest = cp_transcript_digest(w, s.label);
+    }
+    const Fp c = ed_mod_order(digest);
     c_out[i] = c;
     if (omega) {
         const Fp r = ed_muladd_order(ed_mod_order(omega[i]), c, ed_mod_order(sk[(size_t)i * s_sk]));
@@ -510,8 +539,8 @@ static int cp_verify_launch(Ctx& c, const CpStatement& s, const uint8_t* d_proof
     return UZK_OK;
 }
 
-// statements: m x (e1, reveal, pk); proofs: m blobs; challenges_out optional (m x plain words)
-int cp_verify_run(Ctx& c, const EdAffine* statements, const uint8_t* proofs, uint32_t m, uint8_t* verdict_out, Fp* challenges_out) {
+// statements: m x (e1, reveal, pk); proofs: m blobs; challenges_out optional (m x plain words); anemoi: the zk-friendly transcript
+int cp_verify_run(Ctx& c, const EdAffine* statements, const uint8_t* proofs, uint32_t m, uint8_t* verdict_out, Fp* challenges_out, bool anemoi) {
     size_t at = 0;
     auto carve = [&](size_t bytes) { const size_t o = at; at += ed_align(bytes); return o; };
     const size_t o_stmt = carve((size_t)m * 3 * sizeof(EdAffine)), o_proofs = carve((size_t)m * UZK_CP_PROOF_BYTES), o_c = carve((size_t)m * sizeof(Fp)),
@@ -529,6 +558,7 @@ int cp_verify_run(Ctx& c, const EdAffine* statements, const uint8_t* proofs, uin
     s.s_c0 = s.s_c1 = s.s_c2 = 3;
     s.n_cls = 3;
     s.label = cp_label_revealing();
+    s.transcript = anemoi ? kCpAnemoi : kCpKeccak;
     return cp_verify_launch(c, s, d_proofs, reinterpret_cast<Fp*>(ws + o_c), reinterpret_cast<uint8_t*>(ws + o_pst), reinterpret_cast<uint8_t*>(ws + o_ok),
                             reinterpret_cast<uint8_t*>(ws + o_verdict), m, verdict_out, challenges_out);
 }
@@ -571,7 +601,8 @@ int cp_mask_verify_run(Ctx& c, const EdAffine* pk, const EdAffine* cards, const 
                             reinterpret_cast<uint8_t*>(ws + o_verdict), m, verdict_out, challenges_out);
 }
 
-int cp_prove_run(Ctx& c, const Fp* sk, const EdAffine* e1, const Fp* omegas, uint32_t m, EdAffine* reveal_out, EdAffine* pk_out, uint8_t* proofs_out) {
+int cp_prove_run(Ctx& c, const Fp* sk, const EdAffine* e1, const Fp* omegas, uint32_t m, EdAffine* reveal_out, EdAffine* pk_out, uint8_t* proofs_out,
+                 bool anemoi) {
     size_t at = 0;
     auto carve = [&](size_t bytes) { const size_t o = at; at += ed_align(bytes); return o; };
     const size_t o_e1 = carve((size_t)m * sizeof(EdAffine)), o_om = carve((size_t)m * sizeof(Fp)), o_sk = carve(sizeof(Fp)), o_rv = carve((size_t)m * sizeof(EdAffine)),
@@ -601,6 +632,7 @@ int cp_prove_run(Ctx& c, const Fp* sk, const EdAffine* e1, const Fp* omegas, uin
     s.g = d_e1; s.h = nullptr; s.u = d_rv; s.v = d_pk;
     s.s_g = s.s_u = 1; s.s_v = 0;
     s.label = cp_label_revealing();
+    s.transcript = anemoi ? kCpAnemoi : kCpKeccak;
     {
         KernelScope ks(c, "cp_transcript");
         hipLaunchKernelGGL(cp_transcript_kernel, dim3(ed_grid(m)), dim3(kEdBlock), 0, c.stream, s, nullptr, d_ab, d_c, d_om, d_sk, 0u, d_proofs, m);

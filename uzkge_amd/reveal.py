@@ -90,6 +90,25 @@ def verify_reveal(pks: Sequence[Point], masked_cards: Sequence[Tuple[Point, Poin
     return [int(v) for v in b.cp_reveal_verify_batch(st, b"".join(proofs))]
 
 
+def reveal0(sk: int, masked_cards: Sequence[Tuple[Point, Point]], omegas: Sequence[int]):
+    """The zk-friendly reveal (reveal.rs reveal0 over dl.rs prove0): `reveal` with the Anemoi-Jive hash of the twelve coordinates as
+    the challenge in place of the Keccak transcript; the same blob."""
+    if len(omegas) != len(masked_cards):
+        raise ValueError("one omega per card")
+    rv, pk, proofs = b.cp_reveal_prove_batch(scalars_to_wire([sk])[0], points_to_wire([c[0] for c in masked_cards]), scalars_to_wire(omegas), anemoi=True)
+    return points_from_wire(rv), [bytes(p) for p in proofs], points_from_wire(pk)[0]
+
+
+def verify_reveal0(pks: Sequence[Point], masked_cards: Sequence[Tuple[Point, Point]], reveal_cards: Sequence[Point], proofs: Sequence[bytes]) -> List[int]:
+    """`verify_reveal` for the proofs of reveal0 (uzk_cp_reveal_verify0_batch): the same verdict codes."""
+    if not len(pks) == len(masked_cards) == len(reveal_cards) == len(proofs):
+        raise ValueError("one key, one masked card and one proof per reveal card")
+    if any(len(p) != N.CP_PROOF_BYTES for p in proofs):
+        raise ValueError("a proof is %d bytes" % N.CP_PROOF_BYTES)
+    st = statements_to_wire(pks, [c[0] for c in masked_cards], reveal_cards)
+    return [int(v) for v in b.cp_reveal_verify_batch(st, b"".join(proofs), anemoi=True)]
+
+
 def unmask(masked_cards: Sequence[Tuple[Point, Point]], reveal_cards: Sequence[Sequence[Point]]) -> List[Point]:
     """card_j = e2_j minus every player's reveal of card j; reveal_cards[k][j] is player k's reveal of card j"""
     n = len(masked_cards)
