@@ -11,6 +11,7 @@
 // restatement on Python integers.
 #include "anemoi29.hpp"
 #include "ctx.hpp"
+#include "handles.hpp"
 
 namespace uzk {
 
@@ -42,7 +43,6 @@ __global__ __launch_bounds__(kAnemoiBlock) void anemoi_sponge_kernel(const Fp* _
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------------------
-static size_t an_align(size_t v) { return (v + 255) & ~(size_t)255; }
 static unsigned an_grid(size_t lanes) { return (unsigned)((lanes + kAnemoiBlock - 1) / kAnemoiBlock); }
 // items per launch: all of them, or as many whole workgroups as keep the launch's buffers below kAnemoiChunkBytes
 static size_t an_chunk(size_t n, size_t item_bytes) {
@@ -54,18 +54,14 @@ static size_t an_chunk(size_t n, size_t item_bytes) {
 
 int anemoi_permute_run(Ctx& c, const Fp* states, size_t n, Fp* out) {
     const size_t item = 4 * sizeof(Fp), chunk = an_chunk(n, 2 * item);
-    const size_t o_out = an_align(chunk * item);
-    UZK_TRY(c.ed_ws.reserve(o_out + an_align(chunk * item)));
-    Fp* d_in = c.ed_ws.as<Fp>();
-    Fp* d_out = reinterpret_cast<Fp*>(c.ed_ws.as<char>() + o_out);
+    WsCarver cv;
+    const auto a_in = cv.array<Fp>(chunk * 4), a_out = cv.array<Fp>(chunk * 4);
+    UZK_TRY(cv.reserve(c.ed_ws));
+    Fp *d_in = cv(a_in), *d_out = cv(a_out);
     for (size_t first = 0; first < n; first += chunk) {
         const size_t count = n - first < chunk ? n - first : chunk;
         UZK_HIP(hipMemcpyAsync(d_in, states + 4 * first, count * item, hipMemcpyHostToDevice, c.stream));
-        {
-            KernelScope ks(c, "anemoi_permute");
-            hipLaunchKernelGGL(anemoi_permute_kernel, dim3(an_grid(count)), dim3(kAnemoiBlock), 0, c.stream, d_in, d_out, (uint32_t)count);
-        }
-        UZK_HIP(hipGetLastError());
+        UZK_LAUNCH(c, "anemoi_permute", anemoi_permute_kernel, dim3(an_grid(count)), dim3(kAnemoiBlock), 0, c.stream, d_in, d_out, (uint32_t)count);
         UZK_HIP(hipMemcpyAsync(out + 4 * first, d_out, count * item, hipMemcpyDeviceToHost, c.stream));
     }
     UZK_HIP(hipStreamSynchronize(c.stream));
@@ -78,20 +74,14 @@ int anemoi_sponge_run(Ctx& c, const Fp* inputs, uint32_t len, size_t n, uint32_t
     const size_t in_item = (size_t)len * sizeof(Fp), out_item = (size_t)outs * sizeof(Fp);
     const size_t tr_item = trace_out ? (size_t)perms * kAnemoiTraceElems * sizeof(Fp) : 0;
     const size_t chunk = an_chunk(n, in_item + out_item + tr_item);
-    const size_t o_out = an_align(chunk * in_item), o_tr = o_out + an_align(chunk * out_item);
-    UZK_TRY(c.ed_ws.reserve(o_tr + an_align(chunk * tr_item)));
-    char* ws = c.ed_ws.as<char>();
-    Fp* d_in = reinterpret_cast<Fp*>(ws);
-    Fp* d_out = reinterpret_cast<Fp*>(ws + o_out);
-    Fp* d_tr = trace_out ? reinterpret_cast<Fp*>(ws + o_tr) : nullptr;
+    WsCarver cv;
+    const auto a_in = cv.array<Fp>(chunk * len), a_out = cv.array<Fp>(chunk * outs), a_tr = cv.array<Fp>(chunk * (tr_item / sizeof(Fp)));
+    UZK_TRY(cv.reserve(c.ed_ws));
+    Fp *d_in = cv(a_in), *d_out = cv(a_out), *d_tr = trace_out ? cv(a_tr) : nullptr;
     for (size_t first = 0; first < n; first += chunk) {
         const size_t count = n - first < chunk ? n - first : chunk;
         if (len) UZK_HIP(hipMemcpyAsync(d_in, inputs + first * len, count * in_item, hipMemcpyHostToDevice, c.stream));
-        {
-            KernelScope ks(c, trace_out ? "anemoi_sponge_trace" : "anemoi_sponge");
-            hipLaunchKernelGGL(anemoi_sponge_kernel, dim3(an_grid(count)), dim3(kAnemoiBlock), 0, c.stream, d_in, len, out_len, d_out, d_tr, (uint32_t)count);
-        }
-        UZK_HIP(hipGetLastError());
+        UZK_LAUNCH(c, trace_out ? "anemoi_sponge_trace" : "anemoi_sponge", anemoi_sponge_kernel, dim3(an_grid(count)), dim3(kAnemoiBlock), 0, c.stream, d_in, len, out_len, d_out, d_tr, (uint32_t)count);
         UZK_HIP(hipMemcpyAsync(out + first * outs, d_out, count * out_item, hipMemcpyDeviceToHost, c.stream));
         if (trace_out)
             UZK_HIP(hipMemcpyAsync(reinterpret_cast<char*>(trace_out) + first * tr_item, d_tr, count * tr_item, hipMemcpyDeviceToHost, c.stream));

@@ -242,6 +242,31 @@ struct KernelScope {
     ~KernelScope() { if (c.prof_on) c.prof_end(); }
 };
 
+// One launch under its own KernelScope, then the launch's error: returns UZK_ERR_DEVICE from the enclosing function like UZK_HIP.
+// The stream is the caller's to name; c.cur_stream (where the profiling events go) is left alone.
+//     UZK_LAUNCH(c, "name", kernel, grid, block, lds_bytes, stream, args...);
+#define UZK_LAUNCH(c, name, kernel, grid, block, lds, stream, ...)                        \
+    do {                                                                                   \
+        {                                                                                  \
+            ::uzk::KernelScope _ks((c), (name));                                           \
+            hipLaunchKernelGGL(kernel, grid, block, lds, stream, __VA_ARGS__);             \
+        }                                                                                  \
+        UZK_HIP(hipGetLastError());                                                        \
+    } while (0)
+
+// While one lives, the calling thread's current device is `device`; then it is what it was.  Freeing a key's memory needs the
+// key's device current, and must not leave the caller's thread on it.
+struct DeviceGuard {
+    int prev = -1;
+    explicit DeviceGuard(int device) {
+        (void)hipGetDevice(&prev);
+        (void)hipSetDevice(device);
+    }
+    ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
+    DeviceGuard(const DeviceGuard&) = delete;
+    DeviceGuard& operator=(const DeviceGuard&) = delete;
+};
+
 // entry points implemented in the .hip files
 int ntt_run(Ctx& c, const Fp* d_in, Fp* d_out, uint64_t n, bool inverse, const Fp* coset_shift_host, uint32_t batch,
             uint64_t in_stride = 0, uint64_t out_stride = 0, uint64_t in_len = 0);

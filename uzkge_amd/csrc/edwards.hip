@@ -26,12 +26,11 @@
 // (52 proofs are 104 lanes, two waves); a remask's is 84 additions.  tests/ed_ref.py and tests/shuffle_ref.py are the restatements on
 // Python integers.
 #include <cstring>
-#include <map>
-#include <mutex>
 
 #include "anemoi29.hpp"
 #include "ctx.hpp"
 #include "ed29.hpp"
+#include "handles.hpp"
 
 namespace uzk {
 
@@ -446,7 +445,6 @@ __global__ __launch_bounds__(kEdBlock) void ed_raw_kat_kernel(int op, const EdRa
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------------------
-static size_t ed_align(size_t v) { return (v + 255) & ~(size_t)255; }
 static unsigned ed_grid(size_t lanes) { return (unsigned)((lanes + kEdBlock - 1) / kEdBlock); }
 
 // the first coordinate of `count` wire elements that is not below q, or count
@@ -457,16 +455,14 @@ size_t ed_first_noncanonical(const Fp* words, size_t count) {
 }
 
 int ed_check_run(Ctx& c, const EdAffine* pts, size_t n, uint8_t* status_out) {
-    const size_t o_st = ed_align(n * sizeof(EdAffine));
-    UZK_TRY(c.ed_ws.reserve(o_st + ed_align(n)));
-    EdAffine* d_pts = c.ed_ws.as<EdAffine>();
-    uint8_t* d_st = c.ed_ws.as<uint8_t>() + o_st;
+    WsCarver cv;
+    const auto a_pts = cv.array<EdAffine>(n);
+    const auto a_st = cv.array<uint8_t>(n);
+    UZK_TRY(cv.reserve(c.ed_ws));
+    EdAffine* d_pts = cv(a_pts);
+    uint8_t* d_st = cv(a_st);
     UZK_HIP(hipMemcpyAsync(d_pts, pts, n * sizeof(EdAffine), hipMemcpyHostToDevice, c.stream));
-    {
-        KernelScope ks(c, "ed_check");
-        hipLaunchKernelGGL(ed_check_kernel, dim3(ed_grid(n)), dim3(kEdBlock), 0, c.stream, d_pts, d_st, (uint32_t)n);
-    }
-    UZK_HIP(hipGetLastError());
+    UZK_LAUNCH(c, "ed_check", ed_check_kernel, dim3(ed_grid(n)), dim3(kEdBlock), 0, c.stream, d_pts, d_st, (uint32_t)n);
     UZK_HIP(hipMemcpyAsync(status_out, d_st, n, hipMemcpyDeviceToHost, c.stream));
     UZK_HIP(hipStreamSynchronize(c.stream));
     return UZK_OK;
@@ -474,19 +470,16 @@ int ed_check_run(Ctx& c, const EdAffine* pts, size_t n, uint8_t* status_out) {
 
 int ed_mul_run(Ctx& c, const EdAffine* pts, bool shared_base, const Fp* scalars, size_t n, EdAffine* out) {
     const size_t n_pts = shared_base ? 1 : n;
-    const size_t o_sc = ed_align(n_pts * sizeof(EdAffine)), o_out = o_sc + ed_align(n * sizeof(Fp));
-    UZK_TRY(c.ed_ws.reserve(o_out + ed_align(n * sizeof(EdAffine))));
-    char* ws = c.ed_ws.as<char>();
-    EdAffine* d_pts = reinterpret_cast<EdAffine*>(ws);
-    Fp* d_sc = reinterpret_cast<Fp*>(ws + o_sc);
-    EdAffine* d_out = reinterpret_cast<EdAffine*>(ws + o_out);
+    WsCarver cv;
+    const auto a_pts = cv.array<EdAffine>(n_pts);
+    const auto a_sc = cv.array<Fp>(n);
+    const auto a_out = cv.array<EdAffine>(n);
+    UZK_TRY(cv.reserve(c.ed_ws));
+    EdAffine *d_pts = cv(a_pts), *d_out = cv(a_out);
+    Fp* d_sc = cv(a_sc);
     UZK_HIP(hipMemcpyAsync(d_pts, pts, n_pts * sizeof(EdAffine), hipMemcpyHostToDevice, c.stream));
     UZK_HIP(hipMemcpyAsync(d_sc, scalars, n * sizeof(Fp), hipMemcpyHostToDevice, c.stream));
-    {
-        KernelScope ks(c, "ed_mul");
-        hipLaunchKernelGGL(ed_mul_kernel, dim3(ed_grid(n)), dim3(kEdBlock), 0, c.stream, d_pts, shared_base ? 0u : 1u, d_sc, d_out, (uint32_t)n);
-    }
-    UZK_HIP(hipGetLastError());
+    UZK_LAUNCH(c, "ed_mul", ed_mul_kernel, dim3(ed_grid(n)), dim3(kEdBlock), 0, c.stream, d_pts, shared_base ? 0u : 1u, d_sc, d_out, (uint32_t)n);
     UZK_HIP(hipMemcpyAsync(out, d_out, n * sizeof(EdAffine), hipMemcpyDeviceToHost, c.stream));
     UZK_HIP(hipStreamSynchronize(c.stream));
     return UZK_OK;
@@ -495,19 +488,13 @@ int ed_mul_run(Ctx& c, const EdAffine* pts, bool shared_base, const Fp* scalars,
 // e2 == nullptr: the plain sum
 int ed_sum_run(Ctx& c, const EdAffine* e2, const EdAffine* rows, uint32_t k, uint32_t n, EdAffine* out) {
     const size_t row_bytes = (size_t)k * n * sizeof(EdAffine), n_bytes = (size_t)n * sizeof(EdAffine);
-    const size_t o_e2 = ed_align(row_bytes), o_out = o_e2 + ed_align(n_bytes);
-    UZK_TRY(c.ed_ws.reserve(o_out + ed_align(n_bytes)));
-    char* ws = c.ed_ws.as<char>();
-    EdAffine* d_rows = reinterpret_cast<EdAffine*>(ws);
-    EdAffine* d_e2 = reinterpret_cast<EdAffine*>(ws + o_e2);
-    EdAffine* d_out = reinterpret_cast<EdAffine*>(ws + o_out);
+    WsCarver cv;
+    const auto a_rows = cv.array<EdAffine>((size_t)k * n), a_e2 = cv.array<EdAffine>(n), a_out = cv.array<EdAffine>(n);
+    UZK_TRY(cv.reserve(c.ed_ws));
+    EdAffine *d_rows = cv(a_rows), *d_e2 = cv(a_e2), *d_out = cv(a_out);
     UZK_HIP(hipMemcpyAsync(d_rows, rows, row_bytes, hipMemcpyHostToDevice, c.stream));
     if (e2) UZK_HIP(hipMemcpyAsync(d_e2, e2, n_bytes, hipMemcpyHostToDevice, c.stream));
-    {
-        KernelScope ks(c, e2 ? "ed_unmask" : "ed_sum");
-        hipLaunchKernelGGL(ed_sum_kernel, dim3(ed_grid(n)), dim3(kEdBlock), 0, c.stream, d_rows, k, n, e2 ? d_e2 : nullptr, d_out);
-    }
-    UZK_HIP(hipGetLastError());
+    UZK_LAUNCH(c, e2 ? "ed_unmask" : "ed_sum", ed_sum_kernel, dim3(ed_grid(n)), dim3(kEdBlock), 0, c.stream, d_rows, k, n, e2 ? d_e2 : nullptr, d_out);
     UZK_HIP(hipMemcpyAsync(out, d_out, n_bytes, hipMemcpyDeviceToHost, c.stream));
     UZK_HIP(hipStreamSynchronize(c.stream));
     return UZK_OK;
@@ -517,22 +504,10 @@ int ed_sum_run(Ctx& c, const EdAffine* e2, const EdAffine* rows, uint32_t k, uin
 static int cp_verify_launch(Ctx& c, const CpStatement& s, const uint8_t* d_proofs, Fp* d_c, uint8_t* d_pst, uint8_t* d_ok, uint8_t* d_verdict, uint32_t m,
                             uint8_t* verdict_out, Fp* challenges_out) {
     const uint32_t np = s.n_cls + 2;
-    {
-        KernelScope ks(c, "cp_transcript");
-        hipLaunchKernelGGL(cp_transcript_kernel, dim3(ed_grid(m)), dim3(kEdBlock), 0, c.stream, s, d_proofs, nullptr, d_c, nullptr, nullptr, 0u, nullptr, m);
-    }
-    UZK_HIP(hipGetLastError());
-    {
-        const unsigned point_blocks = ed_grid((size_t)m * np);
-        KernelScope ks(c, "cp_check");
-        hipLaunchKernelGGL(cp_check_kernel, dim3(point_blocks + ed_grid((size_t)m * 2)), dim3(kEdBlock), 0, c.stream, s, d_proofs, d_c, d_pst, d_ok, m, point_blocks);
-    }
-    UZK_HIP(hipGetLastError());
-    {
-        KernelScope ks(c, "cp_verdict");
-        hipLaunchKernelGGL(cp_verdict_kernel, dim3(ed_grid(m)), dim3(kEdBlock), 0, c.stream, d_pst, d_ok, d_verdict, m, np);
-    }
-    UZK_HIP(hipGetLastError());
+    UZK_LAUNCH(c, "cp_transcript", cp_transcript_kernel, dim3(ed_grid(m)), dim3(kEdBlock), 0, c.stream, s, d_proofs, nullptr, d_c, nullptr, nullptr, 0u, nullptr, m);
+    const unsigned point_blocks = ed_grid((size_t)m * np);
+    UZK_LAUNCH(c, "cp_check", cp_check_kernel, dim3(point_blocks + ed_grid((size_t)m * 2)), dim3(kEdBlock), 0, c.stream, s, d_proofs, d_c, d_pst, d_ok, m, point_blocks);
+    UZK_LAUNCH(c, "cp_verdict", cp_verdict_kernel, dim3(ed_grid(m)), dim3(kEdBlock), 0, c.stream, d_pst, d_ok, d_verdict, m, np);
     UZK_HIP(hipMemcpyAsync(verdict_out, d_verdict, m, hipMemcpyDeviceToHost, c.stream));
     if (challenges_out) UZK_HIP(hipMemcpyAsync(challenges_out, d_c, (size_t)m * sizeof(Fp), hipMemcpyDeviceToHost, c.stream));
     UZK_HIP(hipStreamSynchronize(c.stream));
@@ -541,14 +516,14 @@ static int cp_verify_launch(Ctx& c, const CpStatement& s, const uint8_t* d_proof
 
 // statements: m x (e1, reveal, pk); proofs: m blobs; challenges_out optional (m x plain words); anemoi: the zk-friendly transcript
 int cp_verify_run(Ctx& c, const EdAffine* statements, const uint8_t* proofs, uint32_t m, uint8_t* verdict_out, Fp* challenges_out, bool anemoi) {
-    size_t at = 0;
-    auto carve = [&](size_t bytes) { const size_t o = at; at += ed_align(bytes); return o; };
-    const size_t o_stmt = carve((size_t)m * 3 * sizeof(EdAffine)), o_proofs = carve((size_t)m * UZK_CP_PROOF_BYTES), o_c = carve((size_t)m * sizeof(Fp)),
-                 o_pst = carve((size_t)m * 5), o_ok = carve((size_t)m * 2), o_verdict = carve(m);
-    UZK_TRY(c.ed_ws.reserve(at));
-    char* ws = c.ed_ws.as<char>();
-    EdAffine* d_stmt = reinterpret_cast<EdAffine*>(ws + o_stmt);
-    uint8_t* d_proofs = reinterpret_cast<uint8_t*>(ws + o_proofs);
+    WsCarver cv;
+    const auto a_stmt = cv.array<EdAffine>((size_t)m * 3);
+    const auto a_proofs = cv.array<uint8_t>((size_t)m * UZK_CP_PROOF_BYTES);
+    const auto a_c = cv.array<Fp>(m);
+    const auto a_pst = cv.array<uint8_t>((size_t)m * 5), a_ok = cv.array<uint8_t>((size_t)m * 2), a_verdict = cv.array<uint8_t>(m);
+    UZK_TRY(cv.reserve(c.ed_ws));
+    EdAffine* d_stmt = cv(a_stmt);
+    uint8_t* d_proofs = cv(a_proofs);
     UZK_HIP(hipMemcpyAsync(d_stmt, statements, (size_t)m * 3 * sizeof(EdAffine), hipMemcpyHostToDevice, c.stream));
     UZK_HIP(hipMemcpyAsync(d_proofs, proofs, (size_t)m * UZK_CP_PROOF_BYTES, hipMemcpyHostToDevice, c.stream));
     CpStatement s = {};
@@ -559,37 +534,28 @@ int cp_verify_run(Ctx& c, const EdAffine* statements, const uint8_t* proofs, uin
     s.n_cls = 3;
     s.label = cp_label_revealing();
     s.transcript = anemoi ? kCpAnemoi : kCpKeccak;
-    return cp_verify_launch(c, s, d_proofs, reinterpret_cast<Fp*>(ws + o_c), reinterpret_cast<uint8_t*>(ws + o_pst), reinterpret_cast<uint8_t*>(ws + o_ok),
-                            reinterpret_cast<uint8_t*>(ws + o_verdict), m, verdict_out, challenges_out);
+    return cp_verify_launch(c, s, d_proofs, cv(a_c), cv(a_pst), cv(a_ok), cv(a_verdict), m, verdict_out, challenges_out);
 }
 
 // pk: one point; cards, e1, e2: m points each; proofs: m blobs
 int cp_mask_verify_run(Ctx& c, const EdAffine* pk, const EdAffine* cards, const EdAffine* e1, const EdAffine* e2, const uint8_t* proofs, uint32_t m,
                        uint8_t* verdict_out, Fp* challenges_out) {
     const size_t pts = (size_t)m * sizeof(EdAffine);
-    size_t at = 0;
-    auto carve = [&](size_t bytes) { const size_t o = at; at += ed_align(bytes); return o; };
-    const size_t o_pk = carve(sizeof(EdAffine)), o_cards = carve(pts), o_e1 = carve(pts), o_e2 = carve(pts), o_diff = carve(pts),
-                 o_proofs = carve((size_t)m * UZK_CP_PROOF_BYTES), o_c = carve((size_t)m * sizeof(Fp)), o_pst = carve((size_t)m * 6), o_ok = carve((size_t)m * 2),
-                 o_verdict = carve(m);
-    UZK_TRY(c.ed_ws.reserve(at));
-    char* ws = c.ed_ws.as<char>();
-    EdAffine* d_pk = reinterpret_cast<EdAffine*>(ws + o_pk);
-    EdAffine* d_cards = reinterpret_cast<EdAffine*>(ws + o_cards);
-    EdAffine* d_e1 = reinterpret_cast<EdAffine*>(ws + o_e1);
-    EdAffine* d_e2 = reinterpret_cast<EdAffine*>(ws + o_e2);
-    EdAffine* d_diff = reinterpret_cast<EdAffine*>(ws + o_diff);
-    uint8_t* d_proofs = reinterpret_cast<uint8_t*>(ws + o_proofs);
+    WsCarver cv;
+    const auto a_pk = cv.array<EdAffine>(1), a_cards = cv.array<EdAffine>(m), a_e1 = cv.array<EdAffine>(m), a_e2 = cv.array<EdAffine>(m),
+               a_diff = cv.array<EdAffine>(m);
+    const auto a_proofs = cv.array<uint8_t>((size_t)m * UZK_CP_PROOF_BYTES);
+    const auto a_c = cv.array<Fp>(m);
+    const auto a_pst = cv.array<uint8_t>((size_t)m * 6), a_ok = cv.array<uint8_t>((size_t)m * 2), a_verdict = cv.array<uint8_t>(m);
+    UZK_TRY(cv.reserve(c.ed_ws));
+    EdAffine *d_pk = cv(a_pk), *d_cards = cv(a_cards), *d_e1 = cv(a_e1), *d_e2 = cv(a_e2), *d_diff = cv(a_diff);
+    uint8_t* d_proofs = cv(a_proofs);
     UZK_HIP(hipMemcpyAsync(d_pk, pk, sizeof(EdAffine), hipMemcpyHostToDevice, c.stream));
     UZK_HIP(hipMemcpyAsync(d_cards, cards, pts, hipMemcpyHostToDevice, c.stream));
     UZK_HIP(hipMemcpyAsync(d_e1, e1, pts, hipMemcpyHostToDevice, c.stream));
     UZK_HIP(hipMemcpyAsync(d_e2, e2, pts, hipMemcpyHostToDevice, c.stream));
     UZK_HIP(hipMemcpyAsync(d_proofs, proofs, (size_t)m * UZK_CP_PROOF_BYTES, hipMemcpyHostToDevice, c.stream));
-    {
-        KernelScope ks(c, "cp_mask_diff");
-        hipLaunchKernelGGL(cp_mask_diff_kernel, dim3(ed_grid(m)), dim3(kEdBlock), 0, c.stream, d_e2, d_cards, d_diff, m);
-    }
-    UZK_HIP(hipGetLastError());
+    UZK_LAUNCH(c, "cp_mask_diff", cp_mask_diff_kernel, dim3(ed_grid(m)), dim3(kEdBlock), 0, c.stream, d_e2, d_cards, d_diff, m);
     CpStatement s = {};
     s.g = nullptr; s.h = d_pk; s.u = d_e1; s.v = d_diff;
     s.s_h = 0; s.s_u = s.s_v = 1;
@@ -597,47 +563,35 @@ int cp_mask_verify_run(Ctx& c, const EdAffine* pk, const EdAffine* cards, const 
     s.s_c0 = 0; s.s_c1 = s.s_c2 = s.s_c3 = 1;
     s.n_cls = 4;
     s.label = cp_label_masking();
-    return cp_verify_launch(c, s, d_proofs, reinterpret_cast<Fp*>(ws + o_c), reinterpret_cast<uint8_t*>(ws + o_pst), reinterpret_cast<uint8_t*>(ws + o_ok),
-                            reinterpret_cast<uint8_t*>(ws + o_verdict), m, verdict_out, challenges_out);
+    return cp_verify_launch(c, s, d_proofs, cv(a_c), cv(a_pst), cv(a_ok), cv(a_verdict), m, verdict_out, challenges_out);
 }
 
 int cp_prove_run(Ctx& c, const Fp* sk, const EdAffine* e1, const Fp* omegas, uint32_t m, EdAffine* reveal_out, EdAffine* pk_out, uint8_t* proofs_out,
                  bool anemoi) {
-    size_t at = 0;
-    auto carve = [&](size_t bytes) { const size_t o = at; at += ed_align(bytes); return o; };
-    const size_t o_e1 = carve((size_t)m * sizeof(EdAffine)), o_om = carve((size_t)m * sizeof(Fp)), o_sk = carve(sizeof(Fp)), o_rv = carve((size_t)m * sizeof(EdAffine)),
-                 o_ab = carve((size_t)m * 2 * sizeof(EdAffine)), o_pk = carve(sizeof(EdAffine)), o_c = carve((size_t)m * sizeof(Fp)),
-                 o_proofs = carve((size_t)m * UZK_CP_PROOF_BYTES);
-    UZK_TRY(c.ed_ws.reserve(at));
-    char* ws = c.ed_ws.as<char>();
-    EdAffine* d_e1 = reinterpret_cast<EdAffine*>(ws + o_e1);
-    Fp* d_om = reinterpret_cast<Fp*>(ws + o_om);
-    Fp* d_sk = reinterpret_cast<Fp*>(ws + o_sk);
-    EdAffine* d_rv = reinterpret_cast<EdAffine*>(ws + o_rv);
-    EdAffine* d_ab = reinterpret_cast<EdAffine*>(ws + o_ab);
-    EdAffine* d_pk = reinterpret_cast<EdAffine*>(ws + o_pk);
-    Fp* d_c = reinterpret_cast<Fp*>(ws + o_c);
-    uint8_t* d_proofs = reinterpret_cast<uint8_t*>(ws + o_proofs);
+    WsCarver cv;
+    const auto a_e1 = cv.array<EdAffine>(m);
+    const auto a_om = cv.array<Fp>(m), a_sk = cv.array<Fp>(1);
+    const auto a_rv = cv.array<EdAffine>(m), a_ab = cv.array<EdAffine>((size_t)m * 2), a_pk = cv.array<EdAffine>(1);
+    const auto a_c = cv.array<Fp>(m);
+    const auto a_proofs = cv.array<uint8_t>((size_t)m * UZK_CP_PROOF_BYTES);
+    UZK_TRY(cv.reserve(c.ed_ws));
+    EdAffine *d_e1 = cv(a_e1), *d_rv = cv(a_rv), *d_ab = cv(a_ab), *d_pk = cv(a_pk);
+    Fp *d_om = cv(a_om), *d_sk = cv(a_sk), *d_c = cv(a_c);
+    uint8_t* d_proofs = cv(a_proofs);
     UZK_HIP(hipMemcpyAsync(d_e1, e1, (size_t)m * sizeof(EdAffine), hipMemcpyHostToDevice, c.stream));
     UZK_HIP(hipMemcpyAsync(d_om, omegas, (size_t)m * sizeof(Fp), hipMemcpyHostToDevice, c.stream));
     UZK_HIP(hipMemcpyAsync(d_sk, sk, sizeof(Fp), hipMemcpyHostToDevice, c.stream));
     {
         CpProveArgs a = {};
         a.mask = 0; a.bases = d_e1; a.secret = d_sk; a.omega = d_om; a.out0 = d_rv; a.ab = d_ab; a.extra = d_pk;
-        KernelScope ks(c, "cp_prove_mul");
-        hipLaunchKernelGGL(cp_prove_mul_kernel, dim3(ed_grid((size_t)m * 3 + 1)), dim3(kEdBlock), 0, c.stream, a, m);
+        UZK_LAUNCH(c, "cp_prove_mul", cp_prove_mul_kernel, dim3(ed_grid((size_t)m * 3 + 1)), dim3(kEdBlock), 0, c.stream, a, m);
     }
-    UZK_HIP(hipGetLastError());
     CpStatement s = {};
     s.g = d_e1; s.h = nullptr; s.u = d_rv; s.v = d_pk;
     s.s_g = s.s_u = 1; s.s_v = 0;
     s.label = cp_label_revealing();
     s.transcript = anemoi ? kCpAnemoi : kCpKeccak;
-    {
-        KernelScope ks(c, "cp_transcript");
-        hipLaunchKernelGGL(cp_transcript_kernel, dim3(ed_grid(m)), dim3(kEdBlock), 0, c.stream, s, nullptr, d_ab, d_c, d_om, d_sk, 0u, d_proofs, m);
-    }
-    UZK_HIP(hipGetLastError());
+    UZK_LAUNCH(c, "cp_transcript", cp_transcript_kernel, dim3(ed_grid(m)), dim3(kEdBlock), 0, c.stream, s, nullptr, d_ab, d_c, d_om, d_sk, 0u, d_proofs, m);
     UZK_HIP(hipMemcpyAsync(reveal_out, d_rv, (size_t)m * sizeof(EdAffine), hipMemcpyDeviceToHost, c.stream));
     UZK_HIP(hipMemcpyAsync(pk_out, d_pk, sizeof(EdAffine), hipMemcpyDeviceToHost, c.stream));
     UZK_HIP(hipMemcpyAsync(proofs_out, d_proofs, (size_t)m * UZK_CP_PROOF_BYTES, hipMemcpyDeviceToHost, c.stream));
@@ -649,22 +603,16 @@ int cp_prove_run(Ctx& c, const Fp* sk, const EdAffine* e1, const Fp* omegas, uin
 int cp_mask_prove_run(Ctx& c, const EdAffine* pk, const EdAffine* cards, const Fp* rs, const Fp* omegas, uint32_t m, EdAffine* e1_out, EdAffine* e2_out,
                       uint8_t* proofs_out) {
     const size_t pts = (size_t)m * sizeof(EdAffine), scs = (size_t)m * sizeof(Fp);
-    size_t at = 0;
-    auto carve = [&](size_t bytes) { const size_t o = at; at += ed_align(bytes); return o; };
-    const size_t o_pk = carve(sizeof(EdAffine)), o_cards = carve(pts), o_rs = carve(scs), o_om = carve(scs), o_e1 = carve(pts), o_e2 = carve(pts), o_v = carve(pts),
-                 o_ab = carve(2 * pts), o_c = carve(scs), o_proofs = carve((size_t)m * UZK_CP_PROOF_BYTES);
-    UZK_TRY(c.ed_ws.reserve(at));
-    char* ws = c.ed_ws.as<char>();
-    EdAffine* d_pk = reinterpret_cast<EdAffine*>(ws + o_pk);
-    EdAffine* d_cards = reinterpret_cast<EdAffine*>(ws + o_cards);
-    Fp* d_rs = reinterpret_cast<Fp*>(ws + o_rs);
-    Fp* d_om = reinterpret_cast<Fp*>(ws + o_om);
-    EdAffine* d_e1 = reinterpret_cast<EdAffine*>(ws + o_e1);
-    EdAffine* d_e2 = reinterpret_cast<EdAffine*>(ws + o_e2);
-    EdAffine* d_v = reinterpret_cast<EdAffine*>(ws + o_v);
-    EdAffine* d_ab = reinterpret_cast<EdAffine*>(ws + o_ab);
-    Fp* d_c = reinterpret_cast<Fp*>(ws + o_c);
-    uint8_t* d_proofs = reinterpret_cast<uint8_t*>(ws + o_proofs);
+    WsCarver cv;
+    const auto a_pk = cv.array<EdAffine>(1), a_cards = cv.array<EdAffine>(m);
+    const auto a_rs = cv.array<Fp>(m), a_om = cv.array<Fp>(m);
+    const auto a_e1 = cv.array<EdAffine>(m), a_e2 = cv.array<EdAffine>(m), a_v = cv.array<EdAffine>(m), a_ab = cv.array<EdAffine>((size_t)m * 2);
+    const auto a_c = cv.array<Fp>(m);
+    const auto a_proofs = cv.array<uint8_t>((size_t)m * UZK_CP_PROOF_BYTES);
+    UZK_TRY(cv.reserve(c.ed_ws));
+    EdAffine *d_pk = cv(a_pk), *d_cards = cv(a_cards), *d_e1 = cv(a_e1), *d_e2 = cv(a_e2), *d_v = cv(a_v), *d_ab = cv(a_ab);
+    Fp *d_rs = cv(a_rs), *d_om = cv(a_om), *d_c = cv(a_c);
+    uint8_t* d_proofs = cv(a_proofs);
     UZK_HIP(hipMemcpyAsync(d_pk, pk, sizeof(EdAffine), hipMemcpyHostToDevice, c.stream));
     UZK_HIP(hipMemcpyAsync(d_cards, cards, pts, hipMemcpyHostToDevice, c.stream));
     UZK_HIP(hipMemcpyAsync(d_rs, rs, scs, hipMemcpyHostToDevice, c.stream));
@@ -672,19 +620,13 @@ int cp_mask_prove_run(Ctx& c, const EdAffine* pk, const EdAffine* cards, const F
     {
         CpProveArgs a = {};
         a.mask = 1; a.bases = d_cards; a.secret = d_rs; a.omega = d_om; a.pk_in = d_pk; a.out0 = d_e1; a.out1 = d_e2; a.ab = d_ab; a.extra = d_v;
-        KernelScope ks(c, "cp_prove_mul");
-        hipLaunchKernelGGL(cp_prove_mul_kernel, dim3(ed_grid((size_t)m * 5)), dim3(kEdBlock), 0, c.stream, a, m);
+        UZK_LAUNCH(c, "cp_prove_mul", cp_prove_mul_kernel, dim3(ed_grid((size_t)m * 5)), dim3(kEdBlock), 0, c.stream, a, m);
     }
-    UZK_HIP(hipGetLastError());
     CpStatement s = {};
     s.g = nullptr; s.h = d_pk; s.u = d_e1; s.v = d_v;
     s.s_h = 0; s.s_u = s.s_v = 1;
     s.label = cp_label_masking();
-    {
-        KernelScope ks(c, "cp_transcript");
-        hipLaunchKernelGGL(cp_transcript_kernel, dim3(ed_grid(m)), dim3(kEdBlock), 0, c.stream, s, nullptr, d_ab, d_c, d_om, d_rs, 1u, d_proofs, m);
-    }
-    UZK_HIP(hipGetLastError());
+    UZK_LAUNCH(c, "cp_transcript", cp_transcript_kernel, dim3(ed_grid(m)), dim3(kEdBlock), 0, c.stream, s, nullptr, d_ab, d_c, d_om, d_rs, 1u, d_proofs, m);
     UZK_HIP(hipMemcpyAsync(e1_out, d_e1, pts, hipMemcpyDeviceToHost, c.stream));
     UZK_HIP(hipMemcpyAsync(e2_out, d_e2, pts, hipMemcpyDeviceToHost, c.stream));
     UZK_HIP(hipMemcpyAsync(proofs_out, d_proofs, (size_t)m * UZK_CP_PROOF_BYTES, hipMemcpyDeviceToHost, c.stream));
@@ -697,26 +639,14 @@ struct RemarkEntry {
     int device = 0;
     Fp* d_table = nullptr;             // T_pk
 };
-static std::mutex g_rk_mu;
-static std::map<uint64_t, RemarkEntry> g_rk;
-static uint64_t g_rk_next = 1;
-constexpr uint64_t kRkTag = 7ull << 59;
+static HandleTable<RemarkEntry> g_rk(7ull << 59);
 constexpr uint32_t kRemarkTraceChunk = 4096;                        // cards per launch of a remask with trace: 12 KiB of workspace per lane
 
 static void rk_free(const RemarkEntry& e) {
-    int prev = -1;
-    (void)hipGetDevice(&prev);
-    (void)hipSetDevice(e.device);
+    DeviceGuard on(e.device);
     if (e.d_table) (void)hipFree(e.d_table);
-    if (prev >= 0) (void)hipSetDevice(prev);
 }
-static bool rk_lookup(uint64_t h, RemarkEntry* out) {
-    std::lock_guard<std::mutex> lk(g_rk_mu);
-    auto it = g_rk.find(h);
-    if (it == g_rk.end()) return false;
-    *out = it->second;
-    return true;
-}
+static bool rk_lookup(uint64_t h, RemarkEntry* out) { return g_rk.get(h, out); }
 bool remark_key_known(uint64_t h, int* device) {
     RemarkEntry e;
     if (!rk_lookup(h, &e)) return false;
@@ -727,11 +657,7 @@ bool remark_key_known(uint64_t h, int* device) {
 static int remark_gen_table(Ctx& c, const Fp** out) {
     if (!c.ed_gen_ready) {
         UZK_TRY(c.ed_gen.reserve(kRemarkTableBytes));
-        {
-            KernelScope ks(c, "remark_table");
-            hipLaunchKernelGGL(remark_table_kernel, dim3(ed_grid(kRemarkIters)), dim3(kEdBlock), 0, c.stream, (const EdAffine*)nullptr, c.ed_gen.as<Fp>());
-        }
-        UZK_HIP(hipGetLastError());
+        UZK_LAUNCH(c, "remark_table", remark_table_kernel, dim3(ed_grid(kRemarkIters)), dim3(kEdBlock), 0, c.stream, (const EdAffine*)nullptr, c.ed_gen.as<Fp>());
         c.ed_gen_ready = true;
     }
     *out = c.ed_gen.as<Fp>();
@@ -741,8 +667,10 @@ static int remark_gen_table(Ctx& c, const Fp** out) {
 int remark_key_create(Ctx& c, const EdAffine* pk, uint64_t* out) {
     const Fp* d_gen = nullptr;
     UZK_TRY(remark_gen_table(c, &d_gen));
-    UZK_TRY(c.ed_ws.reserve(ed_align(sizeof(EdAffine))));
-    EdAffine* d_pk = c.ed_ws.as<EdAffine>();
+    WsCarver cv;
+    const auto a_pk = cv.array<EdAffine>(1);
+    UZK_TRY(cv.reserve(c.ed_ws));
+    EdAffine* d_pk = cv(a_pk);
     RemarkEntry e;
     e.device = c.device;
     hipError_t err = hipMalloc(reinterpret_cast<void**>(&e.d_table), kRemarkTableBytes);
@@ -759,32 +687,19 @@ int remark_key_create(Ctx& c, const EdAffine* pk, uint64_t* out) {
         set_error("uzk_remark_key_create: %s", hipGetErrorString(err));
         return UZK_ERR_DEVICE;
     }
-    std::lock_guard<std::mutex> lk(g_rk_mu);
-    const uint64_t h = kRkTag | g_rk_next++;
-    g_rk[h] = e;
-    *out = h;
+    *out = g_rk.insert(e);
     return UZK_OK;
 }
 
 // The caller makes sure no remask over this key is still running.
 int remark_key_release(uint64_t h) {
     RemarkEntry e;
-    {
-        std::lock_guard<std::mutex> lk(g_rk_mu);
-        auto it = g_rk.find(h);
-        if (it == g_rk.end()) { set_error("uzk_remark_key_release: unknown remask key %llu", (unsigned long long)h); return UZK_ERR_PARAMETER; }
-        e = it->second;
-        g_rk.erase(it);
-    }
+    if (!g_rk.take(h, &e)) { set_error("uzk_remark_key_release: unknown remask key %llu", (unsigned long long)h); return UZK_ERR_PARAMETER; }
     rk_free(e);
     return UZK_OK;
 }
 
-void remark_release_all() {
-    std::lock_guard<std::mutex> lk(g_rk_mu);
-    for (auto& kv : g_rk) rk_free(kv.second);
-    g_rk.clear();
-}
+void remark_release_all() { g_rk.drain(rk_free); }
 
 static int rk_for_ctx(Ctx& c, const char* who, uint64_t h, RemarkEntry* e) {
     if (!rk_lookup(h, e)) { set_error("%s: unknown remask key %llu", who, (unsigned long long)h); return UZK_ERR_PARAMETER; }
@@ -812,32 +727,30 @@ int remark_run(Ctx& c, uint64_t h, const EdAffine* e1, const EdAffine* e2, const
     UZK_TRY(remark_gen_table(c, &d_gen));
     const size_t pts = (size_t)n * sizeof(EdAffine), dg = (size_t)n * kRemarkIters;
     const uint32_t chunk = trace_out ? (n < kRemarkTraceChunk ? n : kRemarkTraceChunk) : n;
-    const size_t trace_card = (size_t)kRemarkIters * 4 * sizeof(Fp), ws_lane = (size_t)kRemarkIters * 36 * sizeof(uint32_t);
-    size_t at = 0;
-    auto carve = [&](size_t bytes) { const size_t o = at; at += ed_align(bytes); return o; };
-    const size_t o_e1 = carve(pts), o_e2 = carve(pts), o_dg = carve(dg), o_slot = carve((size_t)n * sizeof(uint32_t)), o_o1 = carve(pts), o_o2 = carve(pts),
-                 o_trace = carve(trace_out ? chunk * trace_card : 0), o_ws = carve(trace_out ? 2 * (size_t)chunk * ws_lane : 0);
-    UZK_TRY(c.ed_ws.reserve(at));
-    char* ws = c.ed_ws.as<char>();
+    const size_t trace_elems = (size_t)kRemarkIters * 4, trace_card = trace_elems * sizeof(Fp), ws_words = (size_t)kRemarkIters * 36;
+    WsCarver cv;
+    const auto a_e1 = cv.array<EdAffine>(n), a_e2 = cv.array<EdAffine>(n);
+    const auto a_dg = cv.array<uint8_t>(dg);
+    const auto a_slot = cv.array<uint32_t>(n);
+    const auto a_o1 = cv.array<EdAffine>(n), a_o2 = cv.array<EdAffine>(n);
+    const auto a_trace = cv.array<Fp>(trace_out ? (size_t)chunk * trace_elems : 0);
+    const auto a_ws = cv.array<uint32_t>(trace_out ? 2 * (size_t)chunk * ws_words : 0);
+    UZK_TRY(cv.reserve(c.ed_ws));
     RemarkArgs a = {};
     a.t_gen = d_gen; a.t_pk = e.d_table;
-    a.e1 = reinterpret_cast<EdAffine*>(ws + o_e1); a.e2 = reinterpret_cast<EdAffine*>(ws + o_e2);
-    a.digits = reinterpret_cast<uint8_t*>(ws + o_dg);
-    a.slot = slot ? reinterpret_cast<uint32_t*>(ws + o_slot) : nullptr;
-    a.e1_out = reinterpret_cast<EdAffine*>(ws + o_o1); a.e2_out = reinterpret_cast<EdAffine*>(ws + o_o2);
-    a.trace = trace_out ? reinterpret_cast<Fp*>(ws + o_trace) : nullptr;
-    a.ws = reinterpret_cast<uint32_t*>(ws + o_ws);
-    UZK_HIP(hipMemcpyAsync(ws + o_e1, e1, pts, hipMemcpyHostToDevice, c.stream));
-    UZK_HIP(hipMemcpyAsync(ws + o_e2, e2, pts, hipMemcpyHostToDevice, c.stream));
-    UZK_HIP(hipMemcpyAsync(ws + o_dg, digits, dg, hipMemcpyHostToDevice, c.stream));
-    if (slot) UZK_HIP(hipMemcpyAsync(ws + o_slot, slot, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, c.stream));
+    a.e1 = cv(a_e1); a.e2 = cv(a_e2);
+    a.digits = cv(a_dg);
+    a.slot = slot ? cv(a_slot) : nullptr;
+    a.e1_out = cv(a_o1); a.e2_out = cv(a_o2);
+    a.trace = trace_out ? cv(a_trace) : nullptr;
+    a.ws = cv(a_ws);
+    UZK_HIP(hipMemcpyAsync(cv(a_e1), e1, pts, hipMemcpyHostToDevice, c.stream));
+    UZK_HIP(hipMemcpyAsync(cv(a_e2), e2, pts, hipMemcpyHostToDevice, c.stream));
+    UZK_HIP(hipMemcpyAsync(cv(a_dg), digits, dg, hipMemcpyHostToDevice, c.stream));
+    if (slot) UZK_HIP(hipMemcpyAsync(cv(a_slot), slot, a_slot.bytes(), hipMemcpyHostToDevice, c.stream));
     for (uint32_t first = 0; first < n; first += chunk) {
         a.first = first; a.count = n - first < chunk ? n - first : chunk;
-        {
-            KernelScope ks(c, trace_out ? "remark_trace" : "remark");
-            hipLaunchKernelGGL(remark_kernel, dim3(ed_grid(2 * (size_t)a.count)), dim3(kEdBlock), 0, c.stream, a);
-        }
-        UZK_HIP(hipGetLastError());
+        UZK_LAUNCH(c, trace_out ? "remark_trace" : "remark", remark_kernel, dim3(ed_grid(2 * (size_t)a.count)), dim3(kEdBlock), 0, c.stream, a);
         if (trace_out) UZK_HIP(hipMemcpyAsync(reinterpret_cast<char*>(trace_out) + first * trace_card, a.trace, a.count * trace_card, hipMemcpyDeviceToHost, c.stream));
     }
     UZK_HIP(hipMemcpyAsync(e1_out, a.e1_out, pts, hipMemcpyDeviceToHost, c.stream));

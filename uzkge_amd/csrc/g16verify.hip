@@ -19,14 +19,13 @@
 // the chain would still be 254 doublings long -- the latency of a fold is the chain length, not the lane count (52 proofs are one
 // wave either way).  The shorter chain is an endomorphism criterion for B (a 127-bit multiplication); see DESIGN.md.
 #include <cstring>
-#include <map>
-#include <mutex>
 #include <vector>
 
 #include "ctx.hpp"
 #include "curvecheck.hpp"
 #include "fq12_29.hpp"
 #include "g2_29.hpp"
+#include "handles.hpp"
 #include "host_math.hpp"
 
 namespace uzk {
@@ -166,25 +165,13 @@ struct GvEntry {
     Affine alpha;
     Affine* d_ic = nullptr;        // gamma_abc_g1: n_inputs points
 };
-static std::mutex g_gv_mu;
-static std::map<uint64_t, GvEntry> g_gv;
-static uint64_t g_gv_next = 1;
-constexpr uint64_t kGvTag = 6ull << 59;
+static HandleTable<GvEntry> g_gv(6ull << 59);
 
-static bool gv_lookup(uint64_t h, GvEntry* out) {
-    std::lock_guard<std::mutex> lk(g_gv_mu);
-    auto it = g_gv.find(h);
-    if (it == g_gv.end()) return false;
-    *out = it->second;
-    return true;
-}
+static bool gv_lookup(uint64_t h, GvEntry* out) { return g_gv.get(h, out); }
 // frees the key's device memory; the calling thread's current device is left as it was
 static void gv_free(const GvEntry& e) {
-    int prev = -1;
-    (void)hipGetDevice(&prev);
-    (void)hipSetDevice(e.device);
+    DeviceGuard on(e.device);
     if (e.d_ic) (void)hipFree(e.d_ic);
-    if (prev >= 0) (void)hipSetDevice(prev);
 }
 
 int g16v_key_check(const uzk_g16_vk_desc* d) {
@@ -210,10 +197,7 @@ int g16v_key_create(Ctx& c, const uzk_g16_vk_desc* d, uint64_t* out) {
         set_error("uzk_g16_vk_create: %s", hipGetErrorString(err));
         return UZK_ERR_DEVICE;
     }
-    std::lock_guard<std::mutex> lk(g_gv_mu);
-    const uint64_t h = kGvTag | g_gv_next++;
-    g_gv[h] = e;
-    *out = h;
+    *out = g_gv.insert(e);
     return UZK_OK;
 }
 
@@ -228,26 +212,14 @@ bool g16v_key_known(uint64_t h, uint32_t* n_inputs, int* device) {
 // The caller makes sure no fold over this key is still running.
 int g16v_key_release(uint64_t h) {
     GvEntry e;
-    {
-        std::lock_guard<std::mutex> lk(g_gv_mu);
-        auto it = g_gv.find(h);
-        if (it == g_gv.end()) { set_error("uzk_g16_vk_release: unknown verifying key %llu", (unsigned long long)h); return UZK_ERR_PARAMETER; }
-        e = it->second;
-        g_gv.erase(it);
-    }
+    if (!g_gv.take(h, &e)) { set_error("uzk_g16_vk_release: unknown verifying key %llu", (unsigned long long)h); return UZK_ERR_PARAMETER; }
     gv_free(e);
     return UZK_OK;
 }
 
-void g16v_release_all() {
-    std::lock_guard<std::mutex> lk(g_gv_mu);
-    for (auto& kv : g_gv) gv_free(kv.second);
-    g_gv.clear();
-}
+void g16v_release_all() { g_gv.drain(gv_free); }
 
 // ---- the fold -----------------------------------------------------------------------------------------------------------------
-static size_t gv_align(size_t v) { return (v + 255) & ~(size_t)255; }
-
 // The G1 arguments of the last three pairs: -(t_0 alpha) from the scalar multiplications' array, -X and -C from the MSMs' Jacobian sums
 // (X / Z^2, Y / Z^3), brought to affine with the inversion in the lane.  Three lanes; no barrier.
 // out may be alpha_w: lane 0 reads its point before it writes it, the other lanes write behind it
@@ -294,11 +266,7 @@ int g16v_verify_run(Ctx& c, uint64_t h, const uint8_t* proofs, const Fp* pub, ui
     UZK_TRY(g16v_fold_impl(c, h, proofs, pub, m, weights, nullptr, nullptr, &al, &xc[0], &xc[1], status_out, &k));
     UZK_HIP(hipMemcpyAsync(k.d_xc, xc, sizeof xc, hipMemcpyHostToDevice, c.stream));
     UZK_HIP(hipMemcpyAsync(k.d_b + m, g2, 3 * sizeof(G2Affine), hipMemcpyHostToDevice, c.stream));
-    {
-        KernelScope ks(c, "g16v_tail");                            // t_0 alpha is replaced by its negative where it lies; -X and -C follow it
-        hipLaunchKernelGGL(g16v_tail_kernel, dim3(1), dim3(kGvBlock), 0, c.stream, k.d_ra + m, k.d_xc, k.d_ra + m);
-    }
-    UZK_HIP(hipGetLastError());
+    UZK_LAUNCH(c, "g16v_tail", g16v_tail_kernel, dim3(1), dim3(kGvBlock), 0, c.stream, k.d_ra + m, k.d_xc, k.d_ra + m);                            // t_0 alpha is replaced by its negative where it lies; -X and -C follow it
     uint32_t bad = m + 3;
     uint8_t bad_status = 0;
     UZK_TRY(pairing_product_run(c, k.d_ra, k.d_b, true, m + 3, gt_out, &bad, &bad_status));   // synchronises: xc and g2 were read
@@ -315,52 +283,33 @@ static int g16v_fold_impl(Ctx& c, uint64_t h, const uint8_t* proofs, const Fp* p
     if (!gv_lookup(h, &e)) { set_error("%s: unknown verifying key %llu", who, (unsigned long long)h); return UZK_ERR_PARAMETER; }
     if (e.device != c.device) { set_error("%s: the key lives on device %d, the calling context on device %d", who, e.device, c.device); return UZK_ERR_PARAMETER; }
     const uint32_t n_pub = e.n_inputs - 1;
-    size_t at = 0;
-    auto carve = [&](size_t bytes) { const size_t o = at; at += gv_align(bytes); return o; };
-    const size_t o_proofs = carve((size_t)m * UZK_G16_PROOF_BYTES), o_pub = carve((size_t)m * n_pub * sizeof(Fp)), o_rho = carve((size_t)m * sizeof(Fp)),
-                 o_wm = carve((size_t)m * sizeof(Fp)), o_status = carve(m), o_a = carve((size_t)m * sizeof(Affine)),
-                 o_b = carve(((size_t)m + 3) * sizeof(G2Affine)), o_c = carve((size_t)m * sizeof(Affine)), o_t = carve((size_t)e.n_inputs * sizeof(Fp)),
-                 o_ra = carve(((size_t)m + 3) * sizeof(Affine)), o_xc = carve(2 * sizeof(Jac));   // m + 1 of o_ra for a fold; the product's pairs lie behind
-    UZK_TRY(c.g16v_ws.reserve(at));
-    char* ws = c.g16v_ws.as<char>();
-    uint8_t* d_proofs = reinterpret_cast<uint8_t*>(ws + o_proofs);
-    Fp* d_pub = reinterpret_cast<Fp*>(ws + o_pub);
-    Fp* d_rho = reinterpret_cast<Fp*>(ws + o_rho);
-    Fp* d_wm = reinterpret_cast<Fp*>(ws + o_wm);
-    uint8_t* d_status = reinterpret_cast<uint8_t*>(ws + o_status);
-    Affine* d_a = reinterpret_cast<Affine*>(ws + o_a);
-    G2Affine* d_b = reinterpret_cast<G2Affine*>(ws + o_b);
-    Affine* d_c = reinterpret_cast<Affine*>(ws + o_c);
-    Fp* d_t = reinterpret_cast<Fp*>(ws + o_t);
-    Affine* d_ra = reinterpret_cast<Affine*>(ws + o_ra);
+    WsCarver cv;
+    const auto a_proofs = cv.array<uint8_t>((size_t)m * UZK_G16_PROOF_BYTES);
+    const auto a_pub = cv.array<Fp>((size_t)m * n_pub), a_rho = cv.array<Fp>(m), a_wm = cv.array<Fp>(m);
+    const auto a_status = cv.array<uint8_t>(m);
+    const auto a_a = cv.array<Affine>(m);
+    const auto a_b = cv.array<G2Affine>((size_t)m + 3);
+    const auto a_c = cv.array<Affine>(m);
+    const auto a_t = cv.array<Fp>(e.n_inputs);
+    const auto a_ra = cv.array<Affine>((size_t)m + 3);             // m + 1 of them for a fold; the product's pairs lie behind
+    const auto a_xc = cv.array<Jac>(2);
+    UZK_TRY(cv.reserve(c.g16v_ws));
+    uint8_t *d_proofs = cv(a_proofs), *d_status = cv(a_status);
+    Fp *d_pub = cv(a_pub), *d_rho = cv(a_rho), *d_wm = cv(a_wm), *d_t = cv(a_t);
+    Affine *d_a = cv(a_a), *d_c = cv(a_c), *d_ra = cv(a_ra);
+    G2Affine* d_b = cv(a_b);
     if (keep) {
-        keep->d_ra = d_ra; keep->d_b = d_b; keep->d_xc = reinterpret_cast<Jac*>(ws + o_xc);
+        keep->d_ra = d_ra; keep->d_b = d_b; keep->d_xc = cv(a_xc);
     }
     const Fp one = Fr::one();
     UZK_HIP(hipMemcpyAsync(d_proofs, proofs, (size_t)m * UZK_G16_PROOF_BYTES, hipMemcpyHostToDevice, c.stream));
     if (n_pub) UZK_HIP(hipMemcpyAsync(d_pub, pub, (size_t)m * n_pub * sizeof(Fp), hipMemcpyHostToDevice, c.stream));
     UZK_HIP(hipMemcpyAsync(d_rho, weights ? weights : &one, (size_t)m * sizeof(Fp), hipMemcpyHostToDevice, c.stream));
     const unsigned grid = (m + kGvBlock - 1) / kGvBlock;
-    {
-        KernelScope ks(c, "g16v_decode");
-        hipLaunchKernelGGL(g16v_decode_kernel, dim3(grid), dim3(kGvBlock), 0, c.stream, d_proofs, d_a, d_b, d_c, d_status, m);
-    }
-    UZK_HIP(hipGetLastError());
-    {
-        KernelScope ks(c, "g16v_subgroup");
-        hipLaunchKernelGGL(g16v_subgroup_kernel, dim3(grid), dim3(kGvBlock), 0, c.stream, d_a, d_b, d_c, d_rho, d_status, d_wm, m);
-    }
-    UZK_HIP(hipGetLastError());
-    {
-        KernelScope ks(c, "g16v_reduce");
-        hipLaunchKernelGGL(g16v_reduce_kernel, dim3(e.n_inputs), dim3(256), 0, c.stream, d_wm, d_pub, m, n_pub, d_t);
-    }
-    UZK_HIP(hipGetLastError());
-    {
-        KernelScope ks(c, "g16v_amul");
-        hipLaunchKernelGGL(g16v_amul_kernel, dim3((m + 1 + kGvBlock - 1) / kGvBlock), dim3(kGvBlock), 0, c.stream, d_a, d_wm, d_t, e.alpha, d_ra, m);
-    }
-    UZK_HIP(hipGetLastError());
+    UZK_LAUNCH(c, "g16v_decode", g16v_decode_kernel, dim3(grid), dim3(kGvBlock), 0, c.stream, d_proofs, d_a, d_b, d_c, d_status, m);
+    UZK_LAUNCH(c, "g16v_subgroup", g16v_subgroup_kernel, dim3(grid), dim3(kGvBlock), 0, c.stream, d_a, d_b, d_c, d_rho, d_status, d_wm, m);
+    UZK_LAUNCH(c, "g16v_reduce", g16v_reduce_kernel, dim3(e.n_inputs), dim3(256), 0, c.stream, d_wm, d_pub, m, n_pub, d_t);
+    UZK_LAUNCH(c, "g16v_amul", g16v_amul_kernel, dim3((m + 1 + kGvBlock - 1) / kGvBlock), dim3(kGvBlock), 0, c.stream, d_a, d_wm, d_t, e.alpha, d_ra, m);
     Affine alpha_w;                                                // t_0 alpha, read after the last synchronisation
     UZK_HIP(hipMemcpyAsync(status_out, d_status, m, hipMemcpyDeviceToHost, c.stream));
     if (a_out) UZK_HIP(hipMemcpyAsync(a_out, d_ra, (size_t)m * sizeof(Affine), hipMemcpyDeviceToHost, c.stream));

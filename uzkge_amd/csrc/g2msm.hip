@@ -17,6 +17,7 @@
 
 #include "ctx.hpp"
 #include "g2_29.hpp"
+#include "handles.hpp"
 #include "host_g2.hpp"
 
 namespace uzk {
@@ -41,10 +42,14 @@ struct G2Entry {
     size_t n = 0;
     int device = 0;
 };
-std::mutex g_mu;
-std::map<uint64_t, G2Entry> g_reg;
-uint64_t g_next = 1;
-constexpr uint64_t kHandleTag = 1ull << 59;
+HandleTable<G2Entry> g_reg(1ull << 59);
+
+// frees the set's device memory; the calling thread's current device is left as it was
+void g2_entry_free(const G2Entry& e) {
+    if (!e.d_points) return;
+    DeviceGuard on(e.device);
+    (void)hipFree(e.d_points);
+}
 }  // namespace
 
 // ---- kernels ----------------------------------------------------------------------------------------------------------------
@@ -310,39 +315,24 @@ int g2_register(Ctx& c, const G2Affine* points, size_t n, uint64_t* handle_out) 
         if (err == hipSuccess) err = hipStreamSynchronize(c.stream);
         if (err != hipSuccess) { (void)hipFree(e.d_points); UZK_HIP(err); }
     }
-    std::lock_guard<std::mutex> lk(g_mu);
-    const uint64_t h = kHandleTag | g_next++;
-    g_reg[h] = e;
-    *handle_out = h;
+    *handle_out = g_reg.insert(e);
     return UZK_OK;
 }
 bool g2_lookup(uint64_t handle, const G2Affine** d_points, size_t* n, int* device) {
-    std::lock_guard<std::mutex> lk(g_mu);
-    auto it = g_reg.find(handle);
-    if (it == g_reg.end()) return false;
-    if (d_points) *d_points = it->second.d_points;
-    if (n) *n = it->second.n;
-    if (device) *device = it->second.device;
+    G2Entry e;
+    if (!g_reg.get(handle, &e)) return false;
+    if (d_points) *d_points = e.d_points;
+    if (n) *n = e.n;
+    if (device) *device = e.device;
     return true;
 }
 bool g2_release(uint64_t handle) {
     G2Entry e;
-    {
-        std::lock_guard<std::mutex> lk(g_mu);
-        auto it = g_reg.find(handle);
-        if (it == g_reg.end()) return false;
-        e = it->second;
-        g_reg.erase(it);
-    }
-    if (e.d_points) { (void)hipSetDevice(e.device); (void)hipFree(e.d_points); }
+    if (!g_reg.take(handle, &e)) return false;
+    g2_entry_free(e);
     return true;
 }
-void g2_release_all() {
-    std::lock_guard<std::mutex> lk(g_mu);
-    for (auto& kv : g_reg)
-        if (kv.second.d_points) { (void)hipSetDevice(kv.second.device); (void)hipFree(kv.second.d_points); }
-    g_reg.clear();
-}
+void g2_release_all() { g_reg.drain(g2_entry_free); }
 
 // window sums of `batch` vectors over n <= 2^15 points: out[b * 32 + w], wire XYZZ on the host
 static int g2_pass(Ctx& c, const G2Affine* d_points, const Fp* d_scalars, uint32_t n, uint32_t batch, G2XYZZ* out) {
@@ -356,30 +346,14 @@ static int g2_pass(Ctx& c, const G2Affine* d_points, const Fp* d_scalars, uint32
     UZK_TRY(w.segs.reserve((size_t)slots * kSegs * sizeof(G2XYZZ)));
     UZK_TRY(w.wsum.reserve((size_t)slots * sizeof(G2XYZZ)));
     c.cur_stream = c.stream;
-    {
-        KernelScope ks(c, "g2_digits");
-        hipLaunchKernelGGL(g2_digits_kernel, dim3((n + 255) / 256, batch), dim3(256), 0, c.stream, d_scalars, w.digits.as<uint8_t>(), n);
-    }
-    {
-        KernelScope ks(c, "g2_sort");
-        hipLaunchKernelGGL(g2_sort_kernel, dim3(kW, batch), dim3(256), 0, c.stream, w.digits.as<uint8_t>(), w.sorted.as<uint16_t>(), w.tstart.as<uint32_t>(),
-                           w.tasks.as<uint32_t>(), n, cap);
-    }
-    {
-        KernelScope ks(c, "g2_accumulate");
-        hipLaunchKernelGGL(g2_accumulate_kernel, dim3((cap + 63) / 64, kW, batch), dim3(64), 0, c.stream, d_points, w.sorted.as<uint16_t>(),
-                           w.tstart.as<uint32_t>(), w.tasks.as<uint32_t>(), w.tpart.as<G2XYZZ>(), n, cap);
-    }
-    {
-        KernelScope ks(c, "g2_segments");
-        hipLaunchKernelGGL(g2_segments_kernel, dim3((slots * kSegs + 63) / 64), dim3(64), 0, c.stream, w.tstart.as<uint32_t>(), w.tpart.as<G2XYZZ>(),
-                           w.segs.as<G2XYZZ>(), slots, cap);
-    }
-    {
-        KernelScope ks(c, "g2_windows");
-        hipLaunchKernelGGL(g2_windows_kernel, dim3((slots + 63) / 64), dim3(64), 0, c.stream, w.segs.as<G2XYZZ>(), w.wsum.as<G2XYZZ>(), slots);
-    }
-    UZK_HIP(hipGetLastError());
+    UZK_LAUNCH(c, "g2_digits", g2_digits_kernel, dim3((n + 255) / 256, batch), dim3(256), 0, c.stream, d_scalars, w.digits.as<uint8_t>(), n);
+    UZK_LAUNCH(c, "g2_sort", g2_sort_kernel, dim3(kW, batch), dim3(256), 0, c.stream, w.digits.as<uint8_t>(), w.sorted.as<uint16_t>(), w.tstart.as<uint32_t>(),
+               w.tasks.as<uint32_t>(), n, cap);
+    UZK_LAUNCH(c, "g2_accumulate", g2_accumulate_kernel, dim3((cap + 63) / 64, kW, batch), dim3(64), 0, c.stream, d_points, w.sorted.as<uint16_t>(),
+               w.tstart.as<uint32_t>(), w.tasks.as<uint32_t>(), w.tpart.as<G2XYZZ>(), n, cap);
+    UZK_LAUNCH(c, "g2_segments", g2_segments_kernel, dim3((slots * kSegs + 63) / 64), dim3(64), 0, c.stream, w.tstart.as<uint32_t>(), w.tpart.as<G2XYZZ>(),
+               w.segs.as<G2XYZZ>(), slots, cap);
+    UZK_LAUNCH(c, "g2_windows", g2_windows_kernel, dim3((slots + 63) / 64), dim3(64), 0, c.stream, w.segs.as<G2XYZZ>(), w.wsum.as<G2XYZZ>(), slots);
     UZK_HIP(hipMemcpyAsync(out, w.wsum.p, (size_t)slots * sizeof(G2XYZZ), hipMemcpyDeviceToHost, c.stream));
     UZK_HIP(hipStreamSynchronize(c.stream));
     return UZK_OK;

@@ -19,6 +19,7 @@
 
 #include "ctx.hpp"
 #include "g2_29.hpp"
+#include "handles.hpp"
 #include "host_ec64.hpp"
 #include "host_g2.hpp"
 #include "host_math.hpp"
@@ -50,14 +51,12 @@ struct G16Work {
     DevBuf z_in, zT, part, abc, tail_a, row_b, row_k, rs;
 };
 
-std::mutex g_mu;
-std::map<uint64_t, G16Key> g_reg;
-uint64_t g_next = 1;
-constexpr uint64_t kHandleTag = 1ull << 58;
+HandleTable<G16Key> g_reg(1ull << 58);
 static_assert(sizeof(uzk_g16_key_desc) == 592 && sizeof(uzk_g16_proof) == 256, "the layouts the Python and Rust bindings mirror");
 
-void key_free(G16Key& k) {
-    (void)hipSetDevice(k.device);
+// frees the key's device memory; the calling thread's current device is left as it was
+void key_free(const G16Key& k) {
+    DeviceGuard on(k.device);
     void* ptrs[] = {k.ga, k.gb1, k.gk, k.gb2, k.col, k.row_slice, k.val, k.slices};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
@@ -229,20 +228,11 @@ int g16_key_create(Ctx& c, const uzk_g16_key_desc* d, uint64_t* out) {
     k.zh_inv = fr_inv(Fr::sub(f_pow_u64<Fr>(k.shift, k.n), Fr::one()));
     const int rc = key_upload(c, d, k);
     if (rc != UZK_OK) { (void)hipStreamSynchronize(c.stream); key_free(k); return rc; }
-    std::lock_guard<std::mutex> lk(g_mu);
-    const uint64_t h = kHandleTag | g_next++;
-    g_reg[h] = k;
-    *out = h;
+    *out = g_reg.insert(k);
     return UZK_OK;
 }
 
-static bool key_lookup(uint64_t h, G16Key* out) {
-    std::lock_guard<std::mutex> lk(g_mu);
-    auto it = g_reg.find(h);
-    if (it == g_reg.end()) return false;
-    *out = it->second;
-    return true;
-}
+static bool key_lookup(uint64_t h, G16Key* out) { return g_reg.get(h, out); }
 bool g16_key_known(uint64_t h, uint32_t* n_vars, uint32_t* n_inputs, uint32_t* n_constraints, uint64_t* domain, int* device) {
     G16Key k;
     if (!key_lookup(h, &k)) return false;
@@ -255,21 +245,11 @@ bool g16_key_known(uint64_t h, uint32_t* n_vars, uint32_t* n_inputs, uint32_t* n
 }
 bool g16_key_release(uint64_t h) {
     G16Key k;
-    {
-        std::lock_guard<std::mutex> lk(g_mu);
-        auto it = g_reg.find(h);
-        if (it == g_reg.end()) return false;
-        k = it->second;
-        g_reg.erase(it);
-    }
+    if (!g_reg.take(h, &k)) return false;
     key_free(k);
     return true;
 }
-void g16_release_all() {
-    std::lock_guard<std::mutex> lk(g_mu);
-    for (auto& kv : g_reg) key_free(kv.second);
-    g_reg.clear();
-}
+void g16_release_all() { g_reg.drain(key_free); }
 
 // ---- the prover -------------------------------------------------------------------------------------------------------------
 
@@ -297,27 +277,14 @@ static int h_group(Ctx& c, const G16Key& k, const Fp* d_z, uint32_t nb) {
     UZK_TRY(w.abc.reserve((size_t)3 * n * nb * sizeof(Fp)));
     Fp* abc = w.abc.as<Fp>();
     c.cur_stream = c.stream;
-    {
-        KernelScope ks(c, "g16_transpose");
-        hipLaunchKernelGGL(g16_transpose_kernel, dim3(blocks((uint64_t)k.m * nb)), dim3(256), 0, c.stream, d_z, w.zT.as<Fp>(), k.m, nb);
-    }
-    if (k.n_slices > 0) {
-        KernelScope ks(c, "g16_spmv_slices");
-        hipLaunchKernelGGL(g16_spmv_slices_kernel, dim3(blocks((uint64_t)k.n_slices * nb)), dim3(256), 0, c.stream, k.slices, k.col, k.val, w.zT.as<Fp>(),
-                           w.part.as<Fp>(), k.n_slices, nb);
-    }
-    {
-        KernelScope ks(c, "g16_spmv_rows");
-        hipLaunchKernelGGL(g16_spmv_rows_kernel, dim3(blocks(3 * n * nb)), dim3(256), 0, c.stream, k.row_slice, w.part.as<Fp>(), w.zT.as<Fp>(), abc, k.nc, k.l, n, nb);
-    }
-    UZK_HIP(hipGetLastError());
+    UZK_LAUNCH(c, "g16_transpose", g16_transpose_kernel, dim3(blocks((uint64_t)k.m * nb)), dim3(256), 0, c.stream, d_z, w.zT.as<Fp>(), k.m, nb);
+    if (k.n_slices > 0)
+        UZK_LAUNCH(c, "g16_spmv_slices", g16_spmv_slices_kernel, dim3(blocks((uint64_t)k.n_slices * nb)), dim3(256), 0, c.stream, k.slices, k.col, k.val,
+                   w.zT.as<Fp>(), w.part.as<Fp>(), k.n_slices, nb);
+    UZK_LAUNCH(c, "g16_spmv_rows", g16_spmv_rows_kernel, dim3(blocks(3 * n * nb)), dim3(256), 0, c.stream, k.row_slice, w.part.as<Fp>(), w.zT.as<Fp>(), abc, k.nc, k.l, n, nb);
     UZK_TRY(ntt_run(c, abc, abc, n, true, nullptr, 3 * nb));
     UZK_TRY(ntt_run(c, abc, abc, n, false, &k.shift, 3 * nb));
-    {
-        KernelScope ks(c, "g16_pointwise");
-        hipLaunchKernelGGL(g16_pointwise_kernel, dim3(blocks(n * nb)), dim3(256), 0, c.stream, abc, n * nb, k.zh_inv);
-    }
-    UZK_HIP(hipGetLastError());
+    UZK_LAUNCH(c, "g16_pointwise", g16_pointwise_kernel, dim3(blocks(n * nb)), dim3(256), 0, c.stream, abc, n * nb, k.zh_inv);
     UZK_TRY(ntt_run(c, abc, abc, n, true, &k.shift_inv, nb));
     return UZK_OK;
 }
@@ -375,12 +342,8 @@ int g16_prove_run(Ctx& c, uint64_t h, const Fp* z, bool z_on_device, const Fp* r
             UZK_TRY(w.tail_a.reserve((size_t)2 * nb * sizeof(Fp)));
             UZK_TRY(w.row_b.reserve((size_t)len_b * nb * sizeof(Fp)));
             UZK_TRY(w.row_k.reserve((size_t)len_k * nb * sizeof(Fp)));
-            {
-                KernelScope ks(c, "g16_scalar_rows");
-                hipLaunchKernelGGL(g16_scalar_rows_kernel, dim3(blocks(std::max(len_b, len_k)), nb), dim3(256), 0, c.stream, d_z, w.abc.as<Fp>(), w.rs.as<Fp>(),
-                                   w.tail_a.as<Fp>(), w.row_b.as<Fp>(), w.row_k.as<Fp>(), m, k.l, n, nb);
-            }
-            UZK_HIP(hipGetLastError());
+            UZK_LAUNCH(c, "g16_scalar_rows", g16_scalar_rows_kernel, dim3(blocks(std::max(len_b, len_k)), nb), dim3(256), 0, c.stream, d_z, w.abc.as<Fp>(), w.rs.as<Fp>(),
+                       w.tail_a.as<Fp>(), w.row_b.as<Fp>(), w.row_k.as<Fp>(), m, k.l, n, nb);
             if (c.prof_on) UZK_HIP(hipStreamSynchronize(c.stream));     // so that the stage timers below hold one stage each
         }
         {

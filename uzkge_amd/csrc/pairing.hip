@@ -23,6 +23,7 @@
 #include "ctx.hpp"
 #include "curvecheck.hpp"
 #include "fq12_29.hpp"
+#include "handles.hpp"
 #include "host_g2.hpp"
 
 namespace uzk {
@@ -395,8 +396,6 @@ const Fq12Consts& pairing_consts() {
     return c;
 }
 
-static size_t pr_align(size_t v) { return (v + 255) & ~(size_t)255; }
-
 struct PairWs {
     Fq12Consts* cst;
     Affine* p;
@@ -407,20 +406,16 @@ struct PairWs {
 };
 // the arrays of a product over n pairs, carved from the context's grow-only block; the constants are queued for upload
 static int pairing_carve(Ctx& c, uint32_t n, PairWs* w) {
-    size_t at = 0;
-    auto carve = [&](size_t bytes) { const size_t o = at; at += pr_align(bytes); return o; };
     const size_t nn = n ? n : 1;
-    const size_t o_cst = carve(sizeof(Fq12Consts)), o_p = carve(nn * sizeof(Affine)), o_q = carve(nn * sizeof(G2Affine)), o_st = carve(nn),
-                 o_f0 = carve(nn * sizeof(Fq12w)), o_f1 = carve(((nn + kProdRadix - 1) / kProdRadix) * sizeof(Fq12w)), o_gt = carve(sizeof(Fq12w));
-    UZK_TRY(c.pairing_ws.reserve(at));
-    char* ws = c.pairing_ws.as<char>();
-    w->cst = reinterpret_cast<Fq12Consts*>(ws + o_cst);
-    w->p = reinterpret_cast<Affine*>(ws + o_p);
-    w->q = reinterpret_cast<G2Affine*>(ws + o_q);
-    w->status = reinterpret_cast<uint8_t*>(ws + o_st);
-    w->f[0] = reinterpret_cast<Fq12w*>(ws + o_f0);
-    w->f[1] = reinterpret_cast<Fq12w*>(ws + o_f1);
-    w->gt = reinterpret_cast<Fq12w*>(ws + o_gt);
+    WsCarver cv;
+    const auto a_cst = cv.array<Fq12Consts>(1);
+    const auto a_p = cv.array<Affine>(nn);
+    const auto a_q = cv.array<G2Affine>(nn);
+    const auto a_st = cv.array<uint8_t>(nn);
+    const auto a_f0 = cv.array<Fq12w>(nn), a_f1 = cv.array<Fq12w>((nn + kProdRadix - 1) / kProdRadix), a_gt = cv.array<Fq12w>(1);
+    UZK_TRY(cv.reserve(c.pairing_ws));
+    w->cst = cv(a_cst); w->p = cv(a_p); w->q = cv(a_q); w->status = cv(a_st);
+    w->f[0] = cv(a_f0); w->f[1] = cv(a_f1); w->gt = cv(a_gt);
     UZK_HIP(hipMemcpyAsync(w->cst, &pairing_consts(), sizeof(Fq12Consts), hipMemcpyHostToDevice, c.stream));
     return UZK_OK;
 }
@@ -435,11 +430,7 @@ static Fq12w gt_one() {
 // Miller loops of w.p, w.q (n >= 1; w.status from the check kernel or null), the tree and the final exponentiation, all queued on the
 // context's stream; the result is left in w.gt
 static int pairing_queue(Ctx& c, const PairWs& w, const uint8_t* d_status, uint32_t n) {
-    {
-        KernelScope ks(c, "pairing_miller");
-        hipLaunchKernelGGL(pairing_miller_kernel, dim3((n + kPairsPerBlock - 1) / kPairsPerBlock), dim3(kPairBlock), 0, c.stream, w.p, w.q, d_status, n, w.cst, w.f[0]);
-    }
-    UZK_HIP(hipGetLastError());
+    UZK_LAUNCH(c, "pairing_miller", pairing_miller_kernel, dim3((n + kPairsPerBlock - 1) / kPairsPerBlock), dim3(kPairBlock), 0, c.stream, w.p, w.q, d_status, n, w.cst, w.f[0]);
     uint32_t cnt = n;
     int cur = 0;
     {
@@ -452,11 +443,7 @@ static int pairing_queue(Ctx& c, const PairWs& w, const uint8_t* d_status, uint3
         }
     }
     UZK_HIP(hipGetLastError());
-    {
-        KernelScope ks(c, "pairing_finalexp");
-        hipLaunchKernelGGL(pairing_finalexp_kernel, dim3(1), dim3(8), 0, c.stream, w.f[cur], w.cst, w.gt);
-    }
-    UZK_HIP(hipGetLastError());
+    UZK_LAUNCH(c, "pairing_finalexp", pairing_finalexp_kernel, dim3(1), dim3(8), 0, c.stream, w.f[cur], w.cst, w.gt);
     return UZK_OK;
 }
 
@@ -473,11 +460,7 @@ int pairing_product_run(Ctx& c, const Affine* p, const G2Affine* q, bool on_devi
         UZK_HIP(hipMemcpyAsync(w.p, p, (size_t)n * sizeof(Affine), hipMemcpyHostToDevice, c.stream));
         UZK_HIP(hipMemcpyAsync(w.q, q, (size_t)n * sizeof(G2Affine), hipMemcpyHostToDevice, c.stream));
     }
-    {
-        KernelScope ks(c, "pairing_check");
-        hipLaunchKernelGGL(pairing_check_kernel, dim3((n + kPairBlock - 1) / kPairBlock), dim3(kPairBlock), 0, c.stream, w.p, w.q, w.status, n);
-    }
-    UZK_HIP(hipGetLastError());
+    UZK_LAUNCH(c, "pairing_check", pairing_check_kernel, dim3((n + kPairBlock - 1) / kPairBlock), dim3(kPairBlock), 0, c.stream, w.p, w.q, w.status, n);
     UZK_TRY(pairing_queue(c, w, w.status, n));
     if (c.pairing_status.size() < n) c.pairing_status.resize(n);          // grow-only, like the device block
     uint8_t* st = c.pairing_status.data();
@@ -499,11 +482,12 @@ bool gt_is_one(const Fq12w& a) {
 int pairing_kat_device(Ctx& c, int op, const Fq12w* a, const Fq12w* b, Fq12w* out, uint32_t n) {
     if (n == 0) return UZK_OK;
     const size_t bytes = (size_t)n * sizeof(Fq12w);
-    const size_t o_cst = 0, o_a = pr_align(sizeof(Fq12Consts)), o_b = o_a + pr_align(bytes), o_o = o_b + pr_align(bytes);
-    UZK_TRY(c.pairing_ws.reserve(o_o + pr_align(bytes)));
-    char* ws = c.pairing_ws.as<char>();
-    Fq12Consts* d_cst = reinterpret_cast<Fq12Consts*>(ws + o_cst);
-    Fq12w *da = reinterpret_cast<Fq12w*>(ws + o_a), *db = reinterpret_cast<Fq12w*>(ws + o_b), *dout = reinterpret_cast<Fq12w*>(ws + o_o);
+    WsCarver cv;
+    const auto a_cst = cv.array<Fq12Consts>(1);
+    const auto a_a = cv.array<Fq12w>(n), a_b = cv.array<Fq12w>(n), a_o = cv.array<Fq12w>(n);
+    UZK_TRY(cv.reserve(c.pairing_ws));
+    Fq12Consts* d_cst = cv(a_cst);
+    Fq12w *da = cv(a_a), *db = cv(a_b), *dout = cv(a_o);
     UZK_HIP(hipMemcpyAsync(d_cst, &pairing_consts(), sizeof(Fq12Consts), hipMemcpyHostToDevice, c.stream));
     UZK_HIP(hipMemcpyAsync(da, a, bytes, hipMemcpyHostToDevice, c.stream));
     UZK_HIP(hipMemcpyAsync(db, b, bytes, hipMemcpyHostToDevice, c.stream));

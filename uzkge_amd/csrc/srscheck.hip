@@ -142,11 +142,7 @@ int srs_weights_run(Ctx& c, const uint8_t seed[32], uint64_t first, uint64_t cou
     const uint64_t blocks = srs_weight_blocks(first, count);
     const uint64_t grid = (blocks + kSrsBlock - 1) / kSrsBlock;
     if (grid > 0x7fffffffull) { set_error("srs weights: %llu weights in one launch", (unsigned long long)count); return UZK_ERR_PARAMETER; }
-    {
-        KernelScope ks(c, "srs_weights");
-        hipLaunchKernelGGL(srs_weights_kernel, dim3((unsigned)grid), dim3(kSrsBlock), 0, c.stream, srs_seed_of(seed), first, count, blocks, d_out);
-    }
-    UZK_HIP(hipGetLastError());
+    UZK_LAUNCH(c, "srs_weights", srs_weights_kernel, dim3((unsigned)grid), dim3(kSrsBlock), 0, c.stream, srs_seed_of(seed), first, count, blocks, d_out);
     return UZK_OK;
 }
 
@@ -159,11 +155,7 @@ int srs_curve_run(Ctx& c, const Affine* d_points, uint64_t count, uzk_srs_curve_
     const unsigned grid = (unsigned)(want < cap ? want : cap);
     UZK_TRY(c.srs_records.reserve((size_t)grid * sizeof(SrsCurveRecord)));
     SrsCurveRecord* d_rec = c.srs_records.as<SrsCurveRecord>();
-    {
-        KernelScope ks(c, "srs_curve");
-        hipLaunchKernelGGL(srs_curve_kernel, dim3(grid), dim3(kSrsBlock), 0, c.stream, d_points, count, d_rec);
-    }
-    UZK_HIP(hipGetLastError());
+    UZK_LAUNCH(c, "srs_curve", srs_curve_kernel, dim3(grid), dim3(kSrsBlock), 0, c.stream, d_points, count, d_rec);
     std::vector<SrsCurveRecord> rec(grid);
     UZK_HIP(hipMemcpyAsync(rec.data(), d_rec, (size_t)grid * sizeof(SrsCurveRecord), hipMemcpyDeviceToHost, c.stream));
     UZK_HIP(hipStreamSynchronize(c.stream));

@@ -18,10 +18,9 @@
 // goes through cross-lane moves, no LDS.  Per-lane form: the state in registers (static indices only), the lanes waiting to be
 // absorbed in the LDS, one column per thread, the permutation inlined at two places.
 #include <cstring>
-#include <map>
-#include <mutex>
 
 #include "ctx.hpp"
+#include "handles.hpp"
 #include "host_math.hpp"
 #include "keccak.hpp"
 
@@ -618,27 +617,15 @@ struct VfEntry {
     Fp* d_consts = nullptr;        // pi_root_powers (n_pi), pi_lagrange (n_pi)
     Affine* d_bases = nullptr;     // kVfFixed points
 };
-static std::mutex g_vf_mu;
-static std::map<uint64_t, VfEntry> g_vf;
-static uint64_t g_vf_next = 1;
-constexpr uint64_t kVfTag = 5ull << 59;
+static HandleTable<VfEntry> g_vf(5ull << 59);
 
-static bool vf_lookup(uint64_t h, VfEntry* out) {
-    std::lock_guard<std::mutex> lk(g_vf_mu);
-    auto it = g_vf.find(h);
-    if (it == g_vf.end()) return false;
-    *out = it->second;
-    return true;
-}
+static bool vf_lookup(uint64_t h, VfEntry* out) { return g_vf.get(h, out); }
 // frees the key's device memory; the calling thread's current device is left as it was
 static void vf_free(const VfEntry& e) {
-    int prev = -1;
-    (void)hipGetDevice(&prev);
-    (void)hipSetDevice(e.device);
+    DeviceGuard on(e.device);
     if (e.d_key) (void)hipFree(e.d_key);
     if (e.d_consts) (void)hipFree(e.d_consts);
     if (e.d_bases) (void)hipFree(e.d_bases);
-    if (prev >= 0) (void)hipSetDevice(prev);
 }
 static uint32_t vf_proof_bytes(uint32_t shuffle) { return 32u * (uint32_t)vf_layout(shuffle != 0).n_words; }
 
@@ -749,10 +736,7 @@ int vf_key_create(Ctx& c, const uzk_vk_desc* d, uint64_t* out) {
         set_error("uzk_vk_create: %s", hipGetErrorString(err));
         return UZK_ERR_DEVICE;
     }
-    std::lock_guard<std::mutex> lk(g_vf_mu);
-    const uint64_t h = kVfTag | g_vf_next++;
-    g_vf[h] = e;
-    *out = h;
+    *out = g_vf.insert(e);
     return UZK_OK;
 }
 
@@ -769,22 +753,12 @@ bool vf_key_known(uint64_t h, uint32_t* cs_size, uint32_t* n_pi, uint32_t* proof
 // The caller makes sure no fold over this key is still running.
 int vf_key_release(uint64_t h) {
     VfEntry e;
-    {
-        std::lock_guard<std::mutex> lk(g_vf_mu);
-        auto it = g_vf.find(h);
-        if (it == g_vf.end()) { set_error("uzk_vk_release: unknown verifier key %llu", (unsigned long long)h); return UZK_ERR_PARAMETER; }
-        e = it->second;
-        g_vf.erase(it);
-    }
+    if (!g_vf.take(h, &e)) { set_error("uzk_vk_release: unknown verifier key %llu", (unsigned long long)h); return UZK_ERR_PARAMETER; }
     vf_free(e);
     return UZK_OK;
 }
 
-void vf_release_all() {
-    std::lock_guard<std::mutex> lk(g_vf_mu);
-    for (auto& kv : g_vf) vf_free(kv.second);
-    g_vf.clear();
-}
+void vf_release_all() { g_vf.drain(vf_free); }
 
 int vf_key_set_public_key(Ctx& c, uint64_t h, const Affine* pk) {
     VfEntry e;
@@ -802,8 +776,6 @@ int vf_key_set_public_key(Ctx& c, uint64_t h, const Affine* pk) {
 static bool vf_transcript_spread(const Ctx& c) { return c.tune_verify_transcript != 1; }
 
 // ---- the fold -----------------------------------------------------------------------------------------------------------------
-static size_t vf_align(size_t v) { return (v + 255) & ~(size_t)255; }
-
 int vf_fold_run(Ctx& c, uint64_t h, const uint8_t* proofs, const Fp* pi, uint32_t m, const Fp* weights, Jac* left_out, Jac* right_out,
                 uint8_t* status_out, Fp* challenges_out) {
     VfEntry e;
@@ -811,58 +783,36 @@ int vf_fold_run(Ctx& c, uint64_t h, const uint8_t* proofs, const Fp* pi, uint32_
     if (e.device != c.device) { set_error("uzk_verify_fold: the key lives on device %d, the calling context on device %d", e.device, c.device); return UZK_ERR_PARAMETER; }
     const uint32_t pb = vf_proof_bytes(e.shuffle);
     const size_t n_r = kVfFixed + (size_t)kVfPerProof * m, n_l = (size_t)2 * m;
-    size_t at = 0;
-    auto carve = [&](size_t bytes) { const size_t o = at; at += vf_align(bytes); return o; };
-    const size_t o_proofs = carve((size_t)m * pb), o_pi = carve((size_t)m * e.n_pi * sizeof(Fp)), o_rho = carve((size_t)m * sizeof(Fp)),
-                 o_words = carve((size_t)m * kVfWords * sizeof(Fp)), o_chal = carve((size_t)m * kVfChallenges * sizeof(Fp)), o_status = carve(m),
-                 o_prefix = carve((size_t)m * (e.n_pi + 1) * sizeof(Fp)), o_fixed = carve((size_t)m * kVfFixed * sizeof(Fp)),
-                 o_pts_r = carve(n_r * sizeof(Affine)), o_sc_r = carve(n_r * sizeof(Fp)), o_pts_l = carve(n_l * sizeof(Affine)),
-                 o_sc_l = carve(n_l * sizeof(Fp));
-    UZK_TRY(c.verify_ws.reserve(at));
-    char* ws = c.verify_ws.as<char>();
-    uint8_t* d_proofs = reinterpret_cast<uint8_t*>(ws + o_proofs);
-    Fp* d_pi = reinterpret_cast<Fp*>(ws + o_pi);
-    Fp* d_rho = reinterpret_cast<Fp*>(ws + o_rho);
-    Fp* d_words = reinterpret_cast<Fp*>(ws + o_words);
-    Fp* d_chal = reinterpret_cast<Fp*>(ws + o_chal);
-    uint8_t* d_status = reinterpret_cast<uint8_t*>(ws + o_status);
-    Fp* d_prefix = reinterpret_cast<Fp*>(ws + o_prefix);
-    Fp* d_fixed = reinterpret_cast<Fp*>(ws + o_fixed);
-    Affine* d_pts_r = reinterpret_cast<Affine*>(ws + o_pts_r);
-    Fp* d_sc_r = reinterpret_cast<Fp*>(ws + o_sc_r);
-    Affine* d_pts_l = reinterpret_cast<Affine*>(ws + o_pts_l);
-    Fp* d_sc_l = reinterpret_cast<Fp*>(ws + o_sc_l);
+    WsCarver cv;
+    const auto a_proofs = cv.array<uint8_t>((size_t)m * pb);
+    const auto a_pi = cv.array<Fp>((size_t)m * e.n_pi), a_rho = cv.array<Fp>(m), a_words = cv.array<Fp>((size_t)m * kVfWords),
+               a_chal = cv.array<Fp>((size_t)m * kVfChallenges);
+    const auto a_status = cv.array<uint8_t>(m);
+    const auto a_prefix = cv.array<Fp>((size_t)m * (e.n_pi + 1)), a_fixed = cv.array<Fp>((size_t)m * kVfFixed);
+    const auto a_pts_r = cv.array<Affine>(n_r);
+    const auto a_sc_r = cv.array<Fp>(n_r);
+    const auto a_pts_l = cv.array<Affine>(n_l);
+    const auto a_sc_l = cv.array<Fp>(n_l);
+    UZK_TRY(cv.reserve(c.verify_ws));
+    uint8_t *d_proofs = cv(a_proofs), *d_status = cv(a_status);
+    Fp *d_pi = cv(a_pi), *d_rho = cv(a_rho), *d_words = cv(a_words), *d_chal = cv(a_chal), *d_prefix = cv(a_prefix), *d_fixed = cv(a_fixed);
+    Affine *d_pts_r = cv(a_pts_r), *d_pts_l = cv(a_pts_l);
+    Fp *d_sc_r = cv(a_sc_r), *d_sc_l = cv(a_sc_l);
     const Fp one = Fr::one();
     UZK_HIP(hipMemcpyAsync(d_proofs, proofs, (size_t)m * pb, hipMemcpyHostToDevice, c.stream));
     if (e.n_pi) UZK_HIP(hipMemcpyAsync(d_pi, pi, (size_t)m * e.n_pi * sizeof(Fp), hipMemcpyHostToDevice, c.stream));
     UZK_HIP(hipMemcpyAsync(d_rho, weights ? weights : &one, (size_t)m * sizeof(Fp), hipMemcpyHostToDevice, c.stream));
     UZK_HIP(hipMemcpyAsync(d_pts_r, e.d_bases, kVfFixed * sizeof(Affine), hipMemcpyDeviceToDevice, c.stream));
     const unsigned lanes_grid = (m + kVfBlock - 1) / kVfBlock;
-    {
-        KernelScope ks(c, "verify_decode");
-        hipLaunchKernelGGL(vf_decode_kernel, dim3(m), dim3(kVfBlock), 0, c.stream, d_proofs, pb, (int)e.shuffle, d_words, d_pts_r, d_pts_l, d_status);
-    }
-    UZK_HIP(hipGetLastError());
-    if (vf_transcript_spread(c)) {
-        KernelScope ks(c, "verify_transcript_lanes");
-        hipLaunchKernelGGL(vf_transcript_lanes_kernel, dim3((m * kVfGroup + kVfBlock - 1) / kVfBlock), dim3(kVfBlock), 0, c.stream, e.d_key, d_proofs, pb, d_pi,
-                           d_status, d_chal, m);
-    } else {
-        KernelScope ks(c, "verify_transcript");
-        hipLaunchKernelGGL(vf_transcript_kernel, dim3(lanes_grid), dim3(kVfBlock), 0, c.stream, e.d_key, d_proofs, pb, d_pi, d_status, d_chal, m);
-    }
-    UZK_HIP(hipGetLastError());
-    {
-        KernelScope ks(c, "verify_scalars");
-        hipLaunchKernelGGL(vf_scalars_kernel, dim3(lanes_grid), dim3(kVfBlock), 0, c.stream, e.d_key, d_words, d_chal, d_pi, e.d_consts, e.d_consts + e.n_pi,
-                           d_rho, d_status, d_prefix, d_fixed, d_sc_r, d_sc_l, m);
-    }
-    UZK_HIP(hipGetLastError());
-    {
-        KernelScope ks(c, "verify_reduce");
-        hipLaunchKernelGGL(vf_reduce_kernel, dim3(kVfFixed), dim3(256), 0, c.stream, d_fixed, m, d_sc_r);
-    }
-    UZK_HIP(hipGetLastError());
+    UZK_LAUNCH(c, "verify_decode", vf_decode_kernel, dim3(m), dim3(kVfBlock), 0, c.stream, d_proofs, pb, (int)e.shuffle, d_words, d_pts_r, d_pts_l, d_status);
+    if (vf_transcript_spread(c))
+        UZK_LAUNCH(c, "verify_transcript_lanes", vf_transcript_lanes_kernel, dim3((m * kVfGroup + kVfBlock - 1) / kVfBlock), dim3(kVfBlock), 0, c.stream, e.d_key,
+                   d_proofs, pb, d_pi, d_status, d_chal, m);
+    else
+        UZK_LAUNCH(c, "verify_transcript", vf_transcript_kernel, dim3(lanes_grid), dim3(kVfBlock), 0, c.stream, e.d_key, d_proofs, pb, d_pi, d_status, d_chal, m);
+    UZK_LAUNCH(c, "verify_scalars", vf_scalars_kernel, dim3(lanes_grid), dim3(kVfBlock), 0, c.stream, e.d_key, d_words, d_chal, d_pi, e.d_consts, e.d_consts + e.n_pi,
+               d_rho, d_status, d_prefix, d_fixed, d_sc_r, d_sc_l, m);
+    UZK_LAUNCH(c, "verify_reduce", vf_reduce_kernel, dim3(kVfFixed), dim3(256), 0, c.stream, d_fixed, m, d_sc_r);
     UZK_HIP(hipMemcpyAsync(status_out, d_status, m, hipMemcpyDeviceToHost, c.stream));
     if (challenges_out) UZK_HIP(hipMemcpyAsync(challenges_out, d_chal, (size_t)m * kVfChallenges * sizeof(Fp), hipMemcpyDeviceToHost, c.stream));
     if (c.prof_on) UZK_HIP(hipStreamSynchronize(c.stream));        // so that the two host sections below time the MSMs alone
@@ -884,20 +834,18 @@ int vf_fold_run(Ctx& c, uint64_t h, const uint8_t* proofs, const Fp* pi, uint32_
 
 int vf_keccak_test(Ctx& c, const uint8_t* msgs, const uint64_t* offsets, uint32_t count, uint8_t* out) {
     const size_t total = offsets[count];
-    size_t at = 0;
-    auto carve = [&](size_t bytes) { const size_t o = at; at += vf_align(bytes); return o; };
-    const size_t o_msg = carve(total + 8), o_off = carve((size_t)(count + 1) * 8), o_out = carve((size_t)count * 32);
-    UZK_TRY(c.verify_ws.reserve(at));
-    char* ws = c.verify_ws.as<char>();
-    if (total) UZK_HIP(hipMemcpyAsync(ws + o_msg, msgs, total, hipMemcpyHostToDevice, c.stream));
-    UZK_HIP(hipMemcpyAsync(ws + o_off, offsets, (size_t)(count + 1) * 8, hipMemcpyHostToDevice, c.stream));
-    {
-        KernelScope ks(c, "verify_keccak_test");
-        hipLaunchKernelGGL(vf_keccak_kernel, dim3((count + kVfBlock - 1) / kVfBlock), dim3(kVfBlock), 0, c.stream, reinterpret_cast<const uint8_t*>(ws + o_msg),
-                           reinterpret_cast<const uint64_t*>(ws + o_off), count, reinterpret_cast<uint8_t*>(ws + o_out));
-    }
-    UZK_HIP(hipGetLastError());
-    UZK_HIP(hipMemcpyAsync(out, ws + o_out, (size_t)count * 32, hipMemcpyDeviceToHost, c.stream));
+    WsCarver cv;
+    const auto a_msg = cv.array<uint8_t>(total + 8);
+    const auto a_off = cv.array<uint64_t>((size_t)(count + 1));
+    const auto a_out = cv.array<uint8_t>((size_t)count * 32);
+    UZK_TRY(cv.reserve(c.verify_ws));
+    uint8_t *d_msg = cv(a_msg), *d_out = cv(a_out);
+    uint64_t* d_off = cv(a_off);
+    if (total) UZK_HIP(hipMemcpyAsync(d_msg, msgs, total, hipMemcpyHostToDevice, c.stream));
+    UZK_HIP(hipMemcpyAsync(d_off, offsets, a_off.bytes(), hipMemcpyHostToDevice, c.stream));
+    UZK_LAUNCH(c, "verify_keccak_test", vf_keccak_kernel, dim3((count + kVfBlock - 1) / kVfBlock), dim3(kVfBlock), 0, c.stream, d_msg, d_off, count,
+               d_out);
+    UZK_HIP(hipMemcpyAsync(out, d_out, a_out.bytes(), hipMemcpyDeviceToHost, c.stream));
     UZK_HIP(hipStreamSynchronize(c.stream));
     return UZK_OK;
 }
