@@ -853,7 +853,8 @@ int uzk_cp_reveal_verify_batch(const uint64_t* statements_mont, const uint8_t* p
  *   trace     the affine (c2.x, c2.y, c1.x, c1.y) after every step, c1 from e1 and c2 from e2 (RemarkTrace::intermediate_values: the
  *             witness of the shuffle circuit's remark gates); entry 83 is the remasked card; the identity is (0, 1)
  *   tables    x, y, d x y of every entry, [84][4][3] elements: what compute_shuffle_public_key_selectors /
- *             load_shuffle_remark_parameters put into the circuit; laying them out over the size-n domain stays with the caller
+ *             load_shuffle_remark_parameters put into the circuit; uzk_shuffle_circuit_create / _set_key (below) lay them out over
+ *             the size-n domain
  * The computing calls (key_create, remark_batch, mask_prove) refuse a coordinate that is not below q, a batch of 0 or above the
  * maximum, a perm that is no permutation, a digit above 7 and an unknown key with UZK_ERR_PARAMETER before the device is touched;
  * they check neither the curve nor the subgroup (uzk_ed_check_points does; off the curve the outputs are unspecified).  The library
@@ -876,6 +877,55 @@ int uzk_cp_mask_prove_batch(const uint64_t* pk_mont, const uint64_t* cards_mont,
  * challenges_out  optional, m x 4 words: c_i as plain integers below L (undefined for a verdict of 1) */
 int uzk_cp_mask_verify_batch(const uint64_t* pk_mont, const uint64_t* cards_mont, const uint64_t* e1_mont, const uint64_t* e2_mont,
                              const uint8_t* proofs, uint32_t m, uint8_t* verdict_out, uint64_t* challenges_out);
+
+/* ---- the shuffle circuit: zshuffle's constraint system and its witness on the device ------------------------------------------------
+ * build_cs (shuffle/src/build_cs.rs:26-55) drives a TurboCS through new(), per card new_card_variable / prepare_pi_card_variable /
+ * eval_card_remark, then shuffle_card, the new deck's prepare_pi_card_variable and pad.  For a deck of N cards the resulting circuit is
+ * a pure function of N:
+ *   size      2 + 89 N + 2 N (ceil(N/3) + 1) + 4 N (ceil(N/2) + ceil(ceil(N/2)/3)) + 4 N gates, padded to n = the next power of two
+ *             (N = 52: 14 094 -> 16 384; N = 20: 3 302 -> 4 096; N = UZK_SHUFFLE_CS_MAX_CARDS = 64: 20 322 -> 32 768)
+ *   tables    the indexer's evaluation vectors (indexer.rs:301-478): nine selectors, s = k[perm / n] omega^(perm mod n) over
+ *             compute_permutation, qb on the row-sum gates, q_prk zero, q_ecc = the marker of the 84 constrained rows of every card's
+ *             remark block (NOT selector 7, which is zero), and x, y, d x y of the remask tables T_G / T_pk on those rows
+ *   witness   every variable's value follows from the deck, its remark trace and the permutation; extend_witness gathers them by the
+ *             wiring, compute_witness_selectors lays the digits' bits (bit 0, bit 1, +-1 by bit 2) over the remark blocks
+ * The 32 key commitments come in the order of the reference's verifier key: cm_q (9), cm_s (5), cm_qb, cm_prk (4, the point at
+ * infinity), cm_q_ecc, cm_shuffle_generator (12).  tests/test_shuffle_cs_ref_host.py and tests/test_gpu_shuffle_cs.py hold the layout
+ * to the keys the reference generated for 52 and 20 cards, bit for bit. */
+#define UZK_SHUFFLE_CS_MAX_CARDS 64
+#define UZK_SHUFFLE_CS_MAX_BATCH 64
+#define UZK_SHUFFLE_CS_KEY_COMMITMENTS 32
+/* Host only.  Every output optional (NULL); pi_rows_out: 8 cards rows (verifier_params.public_vars_constraint_indices: the deck's
+ * cards as e2.x, e2.y, e1.x, e1.y, then the new deck's).  cards outside 1 .. UZK_SHUFFLE_CS_MAX_CARDS: UZK_ERR_PARAMETER. */
+int uzk_shuffle_cs_info(uint32_t cards, uint32_t* size_out, uint32_t* n_out, uint32_t* num_vars_out, uint32_t* pi_count_out, uint32_t* pi_rows_out);
+typedef struct {
+    uint32_t cards;                       /* 1 .. UZK_SHUFFLE_CS_MAX_CARDS */
+    uint32_t precompute;                  /* as uzk_circuit_desc.precompute */
+    const uzk_g1_affine* lagrange_bases;  /* n points, n = the padded size (uzk_shuffle_cs_info) */
+    const uzk_g1_affine* blind_bases;     /* 6 points, as uzk_circuit_desc.blind_bases */
+    uint64_t k[5][4];                     /* verifier_params.k */
+    uint64_t group_gen[4];                /* must equal uzk_domain_group_gen(n), else UZK_ERR_FFT */
+} uzk_shuffle_circuit_desc;
+/* Builds the layout, writes the evaluation vectors with one kernel pass and runs them through the path of uzk_circuit_refresh_tables
+ * (iFFT -> coset FFT -> Lagrange commit).  The handle is an ordinary circuit with shuffle = 1: uzk_prove_round1..5, uzk_circuit_info,
+ * uzk_circuit_table and uzk_circuit_release take it unchanged.  Until the first uzk_shuffle_circuit_set_key the public-key tables hold
+ * the generator's (indexer.rs:472-478 does the same).  commitments_out: optional, UZK_SHUFFLE_CS_KEY_COMMITMENTS points. */
+int uzk_shuffle_circuit_create(const uzk_shuffle_circuit_desc* desc, uint64_t* circuit_out, uzk_g1_jac* commitments_out);
+/* refresh_prover_params_public_key (shuffle/src/gen_params/params.rs:57-129) from a remask key's resident T_pk: slots UZK_CS_QPK .. + 12,
+ * copy on write as uzk_circuit_update_tables.  commitments_out: optional, the 12 cm_shuffle_public_key of the game. */
+int uzk_shuffle_circuit_set_key(uint64_t circuit, uint64_t remark_key, uzk_g1_jac* commitments_out);
+/* Remasks and permutes `batch` decks of the circuit's size and leaves their witnesses on the device, ready for uzk_prove_round1 with
+ * inputs_on_device = 1.  The remark trace never leaves the device.
+ *   e1_mont, e2_mont  batch x cards points;  digits  batch x cards x 84 bytes;  perms  batch x cards, each a permutation (as
+ *                     uzk_remark_batch: out[i] = remasked[perm[i]]), or NULL for identities
+ *   d_witness         device, batch x 5 n elements: extend_witness;  d_wsel  device, batch x 3 n: compute_witness_selectors
+ *   pi_values_out     host, batch x 8 cards elements in the order of the PI rows: verify_shuffle's online inputs
+ *   e1_out, e2_out    host, batch x cards points: the new decks
+ * UZK_ERR_PARAMETER before the device is touched: a circuit not made by uzk_shuffle_circuit_create, `cards` (the size of the decks the
+ * caller's arrays hold) other than the circuit's, batch outside 1 .. UZK_SHUFFLE_CS_MAX_BATCH, an unknown key, a coordinate not below q, a digit above 7, a perm that is no permutation. */
+int uzk_shuffle_witness_batch(uint64_t circuit, uint64_t remark_key, const uint64_t* e1_mont, const uint64_t* e2_mont, const uint8_t* digits,
+                              const uint32_t* perms, uint32_t cards, uint32_t batch, void* d_witness, void* d_wsel, uint64_t* pi_values_out,
+                              uint64_t* e1_out, uint64_t* e2_out);
 
 /* ---- Anemoi-Jive over BN254's scalar field: hashes, the stream cipher, their traces (uzkge/src/anemoi) -------------------------------
  * AnemoiJive254: 2 columns, 14 rounds, alpha = 5, g = 5, delta = 1 / g, the round keys of the Anemoi paper's pi rule; a sponge of rate

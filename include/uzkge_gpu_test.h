@@ -129,6 +129,12 @@ int uzk_test_ed_raw_kat(int op, const uint32_t* in, uint32_t* out, size_t n);
  * tests/chain_oracle.py does, and the unsatisfied-witness check is off.  Never set it on a real circuit. */
 int uzk_test_circuit_truncate_t(uint64_t circuit, int on);
 
+/* The shuffle circuit as the library holds it: the wiring the witness kernel gathers by and the permutation round 2 walks (5 n
+ * words each, downloaded from the device), and the 44 evaluation vectors the table kernels write, in slot order without l1 and
+ * coset_quotient: q (9), s (5), qb, q_prk (4), q_shuffle_public_key (12), q_shuffle_generator (12), q_ecc -- 44 n elements.  The
+ * public-key columns are laid out from `remark_key`'s T_pk, or from T_G when it is 0.  Every output optional (NULL). */
+int uzk_test_shuffle_cs_tables(uint64_t circuit, uint64_t remark_key, uint32_t* wiring_out, uint32_t* perm_out, uint64_t* evals_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -137,3 +137,32 @@ pub fn gpu_remark_deck(
     let new_deck = o1.iter().zip(o2.iter()).map(|(a, b)| MaskedCard { e1: point_from_wire(a), e2: point_from_wire(b) }).collect();
     Some((traces, new_deck))
 }
+
+/// `build_cs` + `get_and_clear_witness` + `extend_witness` for one deck without leaving the device: the remask, the circuit's
+/// variables and the gather by the wiring run as kernels over `circuit`'s resident layout (`uzk_shuffle_witness_batch`).  Returns
+/// the device witness (for `uzk_prove_round1` with `inputs_on_device`; its `pi_values` are `verify_shuffle`'s online inputs) and the
+/// new deck.  `None` when the device cannot serve the call: the caller then runs `build_cs` as before.
+pub fn gpu_shuffle_witness(
+    circuit: &sys::ShuffleCircuit,
+    key: &sys::RemarkKey,
+    deck: &[MaskedCard],
+    bits: &[Vec<[bool; N_WIRE_SELECTORS]>],
+    permutation: &Permutation<Fq>,
+) -> Option<(sys::ShuffleWitness, Vec<MaskedCard>)> {
+    let n = deck.len();
+    let iters = sys::UZK_REMARK_ITERATIONS as usize;
+    let matrix = permutation.get_matrix();
+    if n == 0 || bits.len() != n || bits.iter().any(|b| b.len() != iters) || matrix.len() != n {
+        return None;
+    }
+    let mut perm: Vec<u32> = Vec::with_capacity(n);
+    for row in matrix.iter() {
+        perm.push(row.iter().position(|v| *v == Fq::ONE)? as u32);
+    }
+    let e1: Vec<sys::EdPoint> = deck.iter().map(|c| point_to_wire(&c.e1)).collect();
+    let e2: Vec<sys::EdPoint> = deck.iter().map(|c| point_to_wire(&c.e2)).collect();
+    let digits: Vec<u8> = bits.iter().flat_map(|card| card.iter().map(digit_of)).collect();
+    let w = circuit.witness_batch(key, &e1, &e2, &digits, Some(&perm)).ok()?;
+    let new_deck = w.e1_out.iter().zip(w.e2_out.iter()).map(|(a, b)| MaskedCard { e1: point_from_wire(a), e2: point_from_wire(b) }).collect();
+    Some((w, new_deck))
+}

@@ -684,6 +684,88 @@ impl Drop for RemarkKey {
     }
 }
 
+/// The shape of zshuffle's circuit for a deck of `cards` (`uzk_shuffle_cs_info`, host only): (size, n, num_vars, the public-input rows).
+pub fn shuffle_cs_info(cards: u32) -> Result<(u32, u32, u32, Vec<u32>), Error> {
+    let (mut size, mut n, mut vars, mut pis) = (0u32, 0u32, 0u32, 0u32);
+    check(unsafe { uzk_shuffle_cs_info(cards, &mut size, &mut n, &mut vars, &mut pis, std::ptr::null_mut()) })?;
+    let mut rows = vec![0u32; pis as usize];
+    check(unsafe { uzk_shuffle_cs_info(cards, std::ptr::null_mut(), std::ptr::null_mut(), std::ptr::null_mut(), std::ptr::null_mut(), rows.as_mut_ptr()) })?;
+    Ok((size, n, vars, rows))
+}
+
+/// The witnesses of a batch of decks, resident on the device until dropped: what `uzk_prove_round1` takes with `inputs_on_device`.
+pub struct ShuffleWitness {
+    pub d_witness: *mut std::os::raw::c_void,
+    pub d_wsel: *mut std::os::raw::c_void,
+    /// batch x 8 cards online inputs, in the order of `verify_shuffle`
+    pub pi_values: Vec<Limbs>,
+    pub e1_out: Vec<EdPoint>,
+    pub e2_out: Vec<EdPoint>,
+}
+impl Drop for ShuffleWitness {
+    fn drop(&mut self) {
+        unsafe {
+            uzk_dev_free(self.d_witness);
+            uzk_dev_free(self.d_wsel);
+        }
+    }
+}
+
+/// zshuffle's circuit for one deck size, laid out and preprocessed on the device (`uzk_shuffle_circuit_create`): an ordinary circuit
+/// handle for the five rounds, plus the layout the witness kernels read.  Released on drop.
+pub struct ShuffleCircuit {
+    handle: u64,
+    cards: u32,
+    n: u32,
+    /// the 32 commitments of the verifier key: cm_q (9), cm_s (5), cm_qb, cm_prk (4), cm_q_ecc, cm_shuffle_generator (12)
+    pub commitments: Vec<uzk_g1_jac>,
+}
+impl ShuffleCircuit {
+    /// `desc` and everything it points to are read before this returns.
+    pub fn create(desc: &uzk_shuffle_circuit_desc) -> Result<Self, Error> {
+        let (_, n, _, _) = shuffle_cs_info(desc.cards)?;
+        let mut handle = 0u64;
+        let mut commitments = vec![uzk_g1_jac::default(); UZK_SHUFFLE_CS_KEY_COMMITMENTS as usize];
+        check(unsafe { uzk_shuffle_circuit_create(desc, &mut handle, commitments.as_mut_ptr()) })?;
+        Ok(Self { handle, cards: desc.cards, n, commitments })
+    }
+    pub fn handle(&self) -> u64 { self.handle }
+    pub fn n(&self) -> u32 { self.n }
+    /// The game's public-key tables from the key's resident T_pk (`uzk_shuffle_circuit_set_key`): their 12 commitments.
+    pub fn set_key(&self, key: &RemarkKey) -> Result<Vec<uzk_g1_jac>, Error> {
+        let mut cms = vec![uzk_g1_jac::default(); 12];
+        check(unsafe { uzk_shuffle_circuit_set_key(self.handle, key.handle, cms.as_mut_ptr()) })?;
+        Ok(cms)
+    }
+    /// Remasks and permutes `e1.len() / cards` decks and leaves their witnesses on the device (`uzk_shuffle_witness_batch`).
+    pub fn witness_batch(&self, key: &RemarkKey, e1: &[EdPoint], e2: &[EdPoint], digits: &[u8], perms: Option<&[u32]>) -> Result<ShuffleWitness, Error> {
+        let cards = self.cards as usize;
+        let total = e1.len();
+        let iters = UZK_REMARK_ITERATIONS as usize;
+        if total == 0 || total % cards != 0 || e2.len() != total || digits.len() != total * iters || perms.map_or(false, |p| p.len() != total) {
+            return Err(Error::Parameter);
+        }
+        let batch = total / cards;
+        let n = self.n as usize;
+        let mut w = ShuffleWitness { d_witness: std::ptr::null_mut(), d_wsel: std::ptr::null_mut(), pi_values: vec![[0u64; 4]; 8 * total],
+                                     e1_out: vec![[[0u64; 4]; 2]; total], e2_out: vec![[[0u64; 4]; 2]; total] };
+        check(unsafe { uzk_dev_alloc(32 * 5 * n * batch, &mut w.d_witness) })?;
+        check(unsafe { uzk_dev_alloc(32 * 3 * n * batch, &mut w.d_wsel) })?;
+        let perm_ptr = perms.map_or(std::ptr::null(), |p| p.as_ptr());
+        check(unsafe {
+            uzk_shuffle_witness_batch(self.handle, key.handle, e1.as_ptr() as *const u64, e2.as_ptr() as *const u64, digits.as_ptr(), perm_ptr, self.cards,
+                                      batch as u32, w.d_witness, w.d_wsel, w.pi_values.as_mut_ptr() as *mut u64, w.e1_out.as_mut_ptr() as *mut u64,
+                                      w.e2_out.as_mut_ptr() as *mut u64)
+        })?;
+        Ok(w)
+    }
+}
+impl Drop for ShuffleCircuit {
+    fn drop(&mut self) {
+        unsafe { uzk_circuit_release(self.handle) };
+    }
+}
+
 /// m cards masked under the joint key (`uzk_cp_mask_prove_batch`): (e1, e2, m proof blobs of UZK_CP_PROOF_BYTES).  `rs` and `omegas`
 /// are plain integers below the subgroup order, drawn by the caller.
 pub fn cp_mask_prove_batch(pk: &EdPoint, cards: &[EdPoint], rs: &[Limbs], omegas: &[Limbs]) -> Result<(Vec<EdPoint>, Vec<EdPoint>, Vec<u8>), Error> {

@@ -144,6 +144,10 @@ PROTOTYPES = {
     "uzk_remark_key_release": (_I, [_U64]),
     "uzk_remark_key_tables": (_I, [_U64, _P, _P]),
     "uzk_remark_batch": (_I, [_U64, _P, _P, _P, _P, ctypes.c_uint32, _P, _P, _P]),
+    "uzk_shuffle_cs_info": (_I, [ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32), _P]),
+    "uzk_shuffle_circuit_create": (_I, [_P, ctypes.POINTER(_U64), _P]),
+    "uzk_shuffle_circuit_set_key": (_I, [_U64, _U64, _P]),
+    "uzk_shuffle_witness_batch": (_I, [_U64, _U64, _P, _P, _P, _P, ctypes.c_uint32, ctypes.c_uint32, _P, _P, _P, _P, _P]),
     "uzk_cp_mask_prove_batch": (_I, [_P, _P, _P, _P, ctypes.c_uint32, _P, _P, _P]),
     "uzk_cp_mask_verify_batch": (_I, [_P, _P, _P, _P, _P, ctypes.c_uint32, _P, _P]),
     "uzk_anemoi_permute_batch": (_I, [_P, _SZ, _P]),
@@ -177,6 +181,7 @@ TEST_PROTOTYPES = {
     "uzk_test_g1_kat": (_I, [_I, _P, _P, _P, _SZ]),
     "uzk_test_g2_kat": (_I, [_I, _P, _P, _P, _SZ]),
     "uzk_test_circuit_truncate_t": (_I, [_U64, _I]),
+    "uzk_test_shuffle_cs_tables": (_I, [_U64, _U64, _P, _P, _P]),
     "uzk_test_l29_kat": (_I, [_I, _I, ctypes.c_uint32, _P, _P, _SZ]),
     "uzk_test_p29_kat": (_I, [_I, _P, _P, _SZ]),
     "uzk_test_g2_raw_kat": (_I, [_I, _P, _P, _SZ]),
@@ -258,6 +263,22 @@ class CircuitDesc(ctypes.Structure):
         ("group_gen", ctypes.c_uint64 * 4),
         ("polys", ctypes.c_void_p * CIRCUIT_SLOTS),
         ("poly_lens", ctypes.c_uint64 * CIRCUIT_SLOTS),
+    ]
+
+
+SHUFFLE_CS_MAX_CARDS = 64
+SHUFFLE_CS_MAX_BATCH = 64
+SHUFFLE_CS_KEY_COMMITMENTS = 32
+SHUFFLE_CS_TABLES = 44            # uzk_test_shuffle_cs_tables: the evaluation vectors in slot order without l1 and coset_quotient
+
+
+class ShuffleCircuitDesc(ctypes.Structure):
+    """uzk_shuffle_circuit_desc (include/uzkge_gpu.h)."""
+    _fields_ = [
+        ("cards", ctypes.c_uint32), ("precompute", ctypes.c_uint32),
+        ("lagrange_bases", ctypes.c_void_p), ("blind_bases", ctypes.c_void_p),
+        ("k", (ctypes.c_uint64 * 4) * 5),
+        ("group_gen", ctypes.c_uint64 * 4),
     ]
 
 

@@ -987,6 +987,75 @@ class Circuit:
             self.handle = 0
 
 
+def shuffle_cs_info(cards: int) -> dict:
+    """uzk_shuffle_cs_info (host only): the shape of zshuffle's circuit for a deck of `cards`, and its public-input rows."""
+    v = [ctypes.c_uint32(0) for _ in range(4)]
+    check(lib.uzk_shuffle_cs_info(cards, *[ctypes.byref(x) for x in v], None))
+    rows = np.zeros(v[3].value, dtype=np.uint32)
+    check(lib.uzk_shuffle_cs_info(cards, None, None, None, None, rows.ctypes.data_as(ctypes.c_void_p)))
+    return dict(size=v[0].value, n=v[1].value, num_vars=v[2].value, pi_count=v[3].value, pi_rows=rows)
+
+
+class ShuffleCircuit(Circuit):
+    """uzk_shuffle_circuit_create: zshuffle's circuit for a deck of `cards`, laid out and preprocessed on the device.  A Circuit in
+    every respect (the rounds, info, table, release take it); `commitments` are the 32 of the verifier key ([32, 12] Jacobian)."""
+
+    def __init__(self, cards: int, lagrange_bases: np.ndarray, blind_bases: np.ndarray, k: np.ndarray, precompute: bool = False, group_gen=None):
+        info = shuffle_cs_info(cards)
+        n = info["n"]
+        d = N.ShuffleCircuitDesc()
+        d.cards, d.precompute = cards, int(precompute)
+        lag = np.ascontiguousarray(lagrange_bases, dtype=np.uint64).reshape(-1, 8)
+        bb = np.ascontiguousarray(blind_bases, dtype=np.uint64).reshape(-1, 8)
+        assert lag.shape[0] == n and bb.shape[0] == 6, "n Lagrange bases and 6 blind bases"
+        d.lagrange_bases, d.blind_bases = lag.ctypes.data, bb.ctypes.data
+        kk = np.ascontiguousarray(k, dtype=np.uint64).reshape(5, 4)
+        gg = np.ascontiguousarray(domain_group_gen(n) if group_gen is None else group_gen, dtype=np.uint64).reshape(4)
+        for j in range(5):
+            for w in range(4):
+                d.k[j][w] = int(kk[j, w])
+        for w in range(4):
+            d.group_gen[w] = int(gg[w])
+        h = ctypes.c_uint64(0)
+        self.commitments = np.zeros((N.SHUFFLE_CS_KEY_COMMITMENTS, 12), dtype=np.uint64)
+        check(lib.uzk_shuffle_circuit_create(ctypes.byref(d), ctypes.byref(h), _ptr(self.commitments)))
+        self.handle, self.n, self.shuffle, self.n_slots = h.value, n, True, N.CIRCUIT_SLOTS
+        self.cards, self.size, self.num_vars, self.pi_rows = cards, info["size"], info["num_vars"], info["pi_rows"]
+
+    def set_key(self, key: "RemarkKey") -> np.ndarray:
+        """uzk_shuffle_circuit_set_key: the game's public-key tables from the key's T_pk; returns their 12 commitments [12, 12]."""
+        cms = np.zeros((12, 12), dtype=np.uint64)
+        check(lib.uzk_shuffle_circuit_set_key(self.handle, key.handle, _ptr(cms)))
+        return cms
+
+    def witness_batch(self, key: "RemarkKey", e1, e2, digits, perms, d_witness: int, d_wsel: int):
+        """uzk_shuffle_witness_batch: e1, e2 [batch, cards, 8]; digits uint8 [batch, cards, 84]; perms uint32 [batch, cards] or None;
+        d_witness / d_wsel: device addresses of batch x 5n / 3n elements.  Returns (pi_values [batch, 8 cards, 4], e1_out, e2_out
+        [batch, cards, 8])."""
+        a = np.ascontiguousarray(e1, dtype=np.uint64)
+        cards = a.shape[-2] if a.ndim >= 2 else self.cards             # the decks' own size: the library refuses any but the circuit's
+        a = a.reshape(-1, cards, 8)
+        c = np.ascontiguousarray(e2, dtype=np.uint64).reshape(-1, cards, 8)
+        batch = a.shape[0]
+        dg = np.ascontiguousarray(digits, dtype=np.uint8).reshape(-1, cards, N.REMARK_ITERATIONS)
+        pm = None if perms is None else np.ascontiguousarray(perms, dtype=np.uint32).reshape(-1, cards)
+        assert c.shape[0] == batch and dg.shape[0] == batch and (pm is None or pm.shape[0] == batch), "one e2, digit row and perm per deck"
+        pi = np.zeros((max(batch, 1), 8 * cards, 4), dtype=np.uint64)
+        o1, o2 = np.zeros((max(batch, 1), cards, 8), dtype=np.uint64), np.zeros((max(batch, 1), cards, 8), dtype=np.uint64)
+        vp = lambda arr: arr.ctypes.data_as(ctypes.c_void_p)
+        check(lib.uzk_shuffle_witness_batch(self.handle, key.handle, _ptr(a), _ptr(c), vp(dg), None if pm is None else vp(pm), cards, batch,
+                                            ctypes.c_void_p(d_witness), ctypes.c_void_p(d_wsel), _ptr(pi), _ptr(o1), _ptr(o2)))
+        return pi[:batch], o1[:batch], o2[:batch]
+
+    def test_tables(self, key: "RemarkKey" = None):
+        """uzk_test_shuffle_cs_tables (test hook): (wiring [5, n], permutation [5, n], evaluation vectors [44, n, 4])."""
+        wiring, perm = np.zeros((5, self.n), dtype=np.uint32), np.zeros((5, self.n), dtype=np.uint32)
+        evals = np.zeros((N.SHUFFLE_CS_TABLES, self.n, 4), dtype=np.uint64)
+        vp = lambda arr: arr.ctypes.data_as(ctypes.c_void_p)
+        check(lib.uzk_test_shuffle_cs_tables(self.handle, key.handle if key is not None else 0, vp(wiring), vp(perm), _ptr(evals)))
+        return wiring, perm, evals
+
+
 class VerifierKey:
     """A verifier key resident on the device (uzk_vk_create).  Points are wire rows of 8 words ((0,0) = infinity), scalars rows of 4;
     `prefix`: the caller's transcript bytes in front of transcript_init_plonk."""

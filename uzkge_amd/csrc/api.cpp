@@ -16,6 +16,7 @@
 #include "g2_29.hpp"
 #include "host_ec64.hpp"
 #include "host_math.hpp"
+#include "shufflecs_dev.hpp"
 
 namespace uzk {
 
@@ -232,6 +233,7 @@ static void ctx_release(Ctx& c) {
     c.verify_ws.release();
     c.g16v_ws.release();
     c.ed_ws.release();
+    c.shuffle_ws.release();
     c.ed_gen.release();
     c.ed_gen_ready = false;
     c.pairing_ws.release();
@@ -1606,6 +1608,29 @@ int uzk_remark_batch(uint64_t key, const uint64_t* e1_mont, const uint64_t* e2_m
     UZK_TRY(require_ready());
     return remark_run(ctx(), key, as_ed(e1_mont), as_ed(e2_mont), digits, perm ? slot.data() : nullptr, n, as_ed(e1_out), as_ed(e2_out), reinterpret_cast<Fp*>(trace_out));
 } catch (...) { return uzk::on_exception("uzk_remark_batch"); }
+
+/* ---- the shuffle circuit (shufflecs.cpp takes the context lock itself) ---------------------------- */
+int uzk_shuffle_cs_info(uint32_t cards, uint32_t* size_out, uint32_t* n_out, uint32_t* num_vars_out, uint32_t* pi_count_out, uint32_t* pi_rows_out) try {
+    return shcs_info(cards, size_out, n_out, num_vars_out, pi_count_out, pi_rows_out);
+} catch (...) { return uzk::on_exception("uzk_shuffle_cs_info"); }
+
+int uzk_shuffle_circuit_create(const uzk_shuffle_circuit_desc* desc, uint64_t* circuit_out, uzk_g1_jac* commitments_out) try {
+    return shcs_circuit_create(desc, circuit_out, commitments_out);
+} catch (...) { return uzk::on_exception("uzk_shuffle_circuit_create"); }
+
+int uzk_shuffle_circuit_set_key(uint64_t circuit, uint64_t remark_key, uzk_g1_jac* commitments_out) try {
+    return shcs_circuit_set_key(circuit, remark_key, commitments_out);
+} catch (...) { return uzk::on_exception("uzk_shuffle_circuit_set_key"); }
+
+int uzk_shuffle_witness_batch(uint64_t circuit, uint64_t remark_key, const uint64_t* e1_mont, const uint64_t* e2_mont, const uint8_t* digits,
+                              const uint32_t* perms, uint32_t cards, uint32_t batch, void* d_witness, void* d_wsel, uint64_t* pi_values_out,
+                              uint64_t* e1_out, uint64_t* e2_out) try {
+    return shcs_witness_batch(circuit, remark_key, e1_mont, e2_mont, digits, perms, cards, batch, d_witness, d_wsel, pi_values_out, e1_out, e2_out);
+} catch (...) { return uzk::on_exception("uzk_shuffle_witness_batch"); }
+
+int uzk_test_shuffle_cs_tables(uint64_t circuit, uint64_t remark_key, uint32_t* wiring_out, uint32_t* perm_out, uint64_t* evals_out) try {
+    return shcs_test_tables(circuit, remark_key, wiring_out, perm_out, evals_out);
+} catch (...) { return uzk::on_exception("uzk_test_shuffle_cs_tables"); }
 
 int uzk_cp_mask_prove_batch(const uint64_t* pk_mont, const uint64_t* cards_mont, const uint64_t* rs, const uint64_t* omegas, uint32_t m, uint64_t* e1_out,
                             uint64_t* e2_out, uint8_t* proofs_out) try {

@@ -155,6 +155,8 @@ struct Ctx {
     DevBuf ed_ws;
     DevBuf ed_gen;                    // T_G, the generator's half of the remask tables: a constant, built once per context
     bool ed_gen_ready = false;
+    // shufflecs.hip: one block carved into the arrays of a shuffle witness (decks, digits, the remark trace, variable values)
+    DevBuf shuffle_ws;
     int tune_verify_transcript = 0;   // which transcript kernel a fold runs: 1 one proof per lane; 0 / 2 a proof's state spread over a half wave (the default)
     // an entry of the process-wide SRS registry
     struct Srs {
@@ -357,6 +359,12 @@ void remark_release_all();
 int remark_tables_run(Ctx& c, uint64_t h, Fp* pk_tables_out, Fp* gen_tables_out);
 int remark_run(Ctx& c, uint64_t h, const EdAffine* e1, const EdAffine* e2, const uint8_t* digits, const uint32_t* slot, uint32_t n, EdAffine* e1_out,
                EdAffine* e2_out, Fp* trace_out);
+// the same remask over arrays that are already on the device and stay there (shufflecs.cpp): n <= 4096 cards, one launch, nothing is
+// copied and nothing waited for; the tables of a key as device addresses ([84][4][3] elements each; either output optional, and T_G
+// alone needs no key)
+int remark_device_run(Ctx& c, uint64_t h, const EdAffine* d_e1, const EdAffine* d_e2, const uint8_t* d_digits, const uint32_t* d_slot, uint32_t n,
+                      EdAffine* d_e1_out, EdAffine* d_e2_out, Fp* d_trace);
+int remark_device_tables(Ctx& c, uint64_t h, const Fp** d_pk_out, const Fp** d_gen_out);
 void msm_plan_info(Ctx& c, size_t n, int* window_bits, int* windows);
 int msm_run(Ctx& c, const Affine* points, const ScalarView& scalars, size_t n, uint32_t batch, Jac* out_host, int pre_c,
             uint32_t pre_stride, uint32_t pre_off);

@@ -759,6 +759,32 @@ int remark_run(Ctx& c, uint64_t h, const EdAffine* e1, const EdAffine* e2, const
     return UZK_OK;
 }
 
+int remark_device_tables(Ctx& c, uint64_t h, const Fp** d_pk_out, const Fp** d_gen_out) {
+    if (d_pk_out) {                                                // T_G alone needs no key
+        RemarkEntry e;
+        UZK_TRY(rk_for_ctx(c, "remask tables", h, &e));
+        *d_pk_out = e.d_table;
+    }
+    if (d_gen_out) UZK_TRY(remark_gen_table(c, d_gen_out));
+    return UZK_OK;
+}
+
+// every array on the device, the trace included: trace[k 84 + i] of card k, the new deck at the cards' slots
+int remark_device_run(Ctx& c, uint64_t h, const EdAffine* d_e1, const EdAffine* d_e2, const uint8_t* d_digits, const uint32_t* d_slot, uint32_t n,
+                      EdAffine* d_e1_out, EdAffine* d_e2_out, Fp* d_trace) {
+    if (n == 0 || n > kRemarkTraceChunk) { set_error("remask on the device: %u cards (1 .. %u per call)", n, kRemarkTraceChunk); return UZK_ERR_PARAMETER; }
+    RemarkArgs a = {};
+    UZK_TRY(remark_device_tables(c, h, &a.t_pk, &a.t_gen));
+    WsCarver cv;
+    const auto a_ws = cv.array<uint32_t>(2 * (size_t)n * kRemarkIters * 36);
+    UZK_TRY(cv.reserve(c.ed_ws));
+    a.e1 = d_e1; a.e2 = d_e2; a.digits = d_digits; a.slot = d_slot;
+    a.e1_out = d_e1_out; a.e2_out = d_e2_out; a.trace = d_trace; a.ws = cv(a_ws);
+    a.first = 0; a.count = n;
+    UZK_LAUNCH(c, "remark_trace", remark_kernel, dim3(ed_grid(2 * (size_t)n)), dim3(kEdBlock), 0, c.stream, a);
+    return UZK_OK;
+}
+
 // n records of EdRawIn (72 words) -> n records of EdRawOut (37 words), both on the host
 int ed_raw_op_device(Ctx& c, int op, const uint32_t* in, uint32_t* out, size_t n) {
     if (n == 0) return UZK_OK;

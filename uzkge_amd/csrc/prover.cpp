@@ -116,10 +116,11 @@ int derive_and_install(Ctx& c, Circuit& cir, std::shared_ptr<DevBlock> blk, uint
 // `count` evaluation vectors (host) -> coefficient forms in d_polys ([count][n]: batched iFFT), their trimmed lengths
 // (FpPolynomial::from_coefs after ifft_with_domain, field_polynomial.rs:594-597) and, optionally, the Lagrange commitments of the
 // evaluations (the commit closure's Lagrange branch, indexer.rs:284-299) over `srs`.
-int polys_from_evals(Ctx& c, const Ctx::Srs* srs, uint32_t n, uint32_t count, const uint64_t* evals, Fp* d_polys, std::vector<uint64_t>& lens, Jac* cms) {
+int polys_from_evals(Ctx& c, const Ctx::Srs* srs, uint32_t n, uint32_t count, const void* evals, Fp* d_polys, std::vector<uint64_t>& lens, Jac* cms,
+                     bool on_device = false) {
     UZK_TRY(c.poly_io.reserve((size_t)count * n * sizeof(Fp)));
     Fp* d_evals = c.poly_io.as<Fp>();
-    UZK_HIP(hipMemcpyAsync(d_evals, evals, (size_t)count * n * sizeof(Fp), hipMemcpyHostToDevice, c.stream));
+    UZK_HIP(hipMemcpyAsync(d_evals, evals, (size_t)count * n * sizeof(Fp), on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c.stream));
     UZK_TRY(ntt_run(c, d_evals, d_polys, n, true, nullptr, count));
     lens.assign(count, 0);
     std::vector<uint64_t> cap(16, n);
@@ -254,6 +255,19 @@ std::shared_ptr<Circuit> find_circuit(uint64_t h) {
     auto it = r.circuits.find(h);
     return it == r.circuits.end() ? nullptr : it->second;
 }
+int circuit_refresh_device(Ctx& c, Circuit& cir, uint32_t first_slot, uint32_t count, const Fp* d_evals, Jac* cms) {
+    if (!slot_range_ok(cir, first_slot, count) || (first_slot <= UZK_CS_COSET_QUOTIENT && UZK_CS_COSET_QUOTIENT < first_slot + count)) {
+        set_error("circuit refresh: slots %u .. %u of %u", first_slot, first_slot + count, cir.n_slots);
+        return UZK_ERR_PARAMETER;
+    }
+    std::shared_ptr<DevBlock> blk;
+    UZK_TRY(dev_block((size_t)count * ((size_t)cir.n + cir.m) * sizeof(Fp), &blk));
+    const Ctx::Srs& srs = count >= 2 && cir.bases->wide.d_table ? cir.bases->wide : cir.bases->plain;
+    std::vector<uint64_t> lens;
+    UZK_TRY(polys_from_evals(c, &srs, cir.n, count, d_evals, static_cast<Fp*>(blk->p), lens, cms, true));
+    return derive_and_install(c, cir, blk, first_slot, count, lens.data());
+}
+
 uint32_t evals_per_proof(const Circuit& cir) { return cir.shuffle ? 19 : 15; }
 uint32_t r_scalars_per_proof(const Circuit& cir) { return cir.shuffle ? 43 : 19; }
 

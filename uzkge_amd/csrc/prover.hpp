@@ -51,6 +51,7 @@ struct Circuit {
     int truncate_t = 0;                                            // uzk_test_circuit_truncate_t: a synthetic circuit no witness satisfies
     std::mutex mu;                                                 // guards `tables`
     std::shared_ptr<const TableSet> tables;
+    std::shared_ptr<void> ext;                                     // what the module that built the circuit keeps with it (shufflecs.cpp: the layout); set once, before the handle is handed out
 };
 
 // The buffers of up to B proofs that advance in lockstep.  Layouts are per lane: lane b's part of every buffer lies a fixed
@@ -121,5 +122,7 @@ uint32_t evals_per_proof(const Circuit& cir);                      // 15 or 19
 uint32_t r_scalars_per_proof(const Circuit& cir);                  // 19 or 43
 
 std::shared_ptr<Circuit> find_circuit(uint64_t h);
+// uzk_circuit_refresh_tables with the `count` evaluation vectors already on the device ([count][n]); cms: count commitments or null
+int circuit_refresh_device(Ctx& c, Circuit& cir, uint32_t first_slot, uint32_t count, const Fp* d_evals, Jac* cms);
 
 }  // namespace uzk
