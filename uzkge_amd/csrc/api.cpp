@@ -358,6 +358,7 @@ static void copy_tuning(const Ctx& from, Ctx& to) {
     to.tune_no_precompute = from.tune_no_precompute; to.tune_ntt_tile = from.tune_ntt_tile; to.tune_ntt_two_pass = from.tune_ntt_two_pass; to.tune_small = from.tune_small;
     to.tune_chunk_log = from.tune_chunk_log; to.tune_verify_transcript = from.tune_verify_transcript; to.tune_stream_log = from.tune_stream_log; to.tune_stream_min_log = from.tune_stream_min_log;
     to.tune_seg_sort = from.tune_seg_sort; to.tune_arith29 = from.tune_arith29;
+    to.tune_msm_taper = from.tune_msm_taper;
 }
 }  // namespace uzk
 int uzk_ctx_create(uint64_t* ctx_out) try {
@@ -2052,6 +2053,7 @@ int uzk_tune(const char* key, int value) try {
     else if (!std::strcmp(key, "msm_chunk_log")) c.tune_chunk_log = (value >= 8 && value <= 26) ? value : 26;
     else if (!std::strcmp(key, "msm_small")) c.tune_small = value ? 1 : 0;
     else if (!std::strcmp(key, "msm_seg_sort")) c.tune_seg_sort = value;
+    else if (!std::strcmp(key, "msm_taper")) c.tune_msm_taper = (value >= 0 && value <= 2) ? value : 1;
     else if (!std::strcmp(key, "ntt_tile")) c.tune_ntt_tile = (value == 1024 || value == 2048) ? value : 0;
     else if (!std::strcmp(key, "ntt_two_pass")) c.tune_ntt_two_pass = value ? 1 : 0;
     else if (!std::strcmp(key, "arith29")) c.tune_arith29 = value & 7;

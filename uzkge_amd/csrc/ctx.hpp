@@ -120,6 +120,7 @@ struct Ctx {
         return v;
     }
     int tune_seg_sort = 1;         // 1: last pass of a packed two-pass sort = one workgroup per segment (msm_radix_segment_kernel); 0: the generic kernels; 10 + k: instantiation k whatever the size (tests)
+    int tune_msm_taper = 1;        // the end of the accumulator's task schedule is made of short tasks (msm_cut.hpp): 0 never, 1 where the task list is several times the resident lanes, 2 at any size (tests)
     // poly.hip workspaces (grow-only)
     DevBuf poly_tmp, poly_tmp2, poly_io, zpoly_tmp, open_tmp, poly_args;
     DevBuf poly_cnt;                 // per-polynomial arrival counters of poly_eval_small (zero between calls); trimmed-length results

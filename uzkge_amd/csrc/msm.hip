@@ -49,6 +49,7 @@
 #include "ec29l.hpp"
 #include "host_ec64.hpp"
 #include "host_math.hpp"
+#include "msm_cut.hpp"
 
 namespace uzk {
 
@@ -625,7 +626,7 @@ __global__ __launch_bounds__(1024) void msm_scan_win_kernel(const uint32_t* __re
                                                             uint32_t* __restrict__ off_out,
                                                             uint32_t* __restrict__ win_total,
                                                             uint32_t* __restrict__ max_out, uint32_t NB,
-                                                            uint32_t* __restrict__ len_hist = nullptr) {
+                                                            uint32_t* __restrict__ len_hist = nullptr, MsmCut cut = MsmCut()) {
     __shared__ uint32_t part[1024];
     __shared__ uint32_t lh[256];
     extern __shared__ uint32_t stage[];
@@ -644,11 +645,18 @@ __global__ __launch_bounds__(1024) void msm_scan_win_kernel(const uint32_t* __re
         return (c + div - 1) / div;
     };
     auto pad = [](uint32_t i) -> uint32_t { return i + (i >> 5); };
-    uint32_t mx = 0;
+    // level 0 with a tapered schedule (cut.n8 != 0): the bucket's own cut length (msm_cut.hpp) instead of div
+    const bool taper = cut.n8 != 0;
+    auto tasks = [&](uint32_t i, uint32_t c) -> uint32_t {
+        return taper ? msm_task_count(cut, w, i, c) : val(c);
+    };
+    uint32_t mx = 0, mt = 0;
     for (uint32_t i = tid; i < NB; i += 1024) {
         const uint32_t c = cnt[i];
         mx = max(mx, c);
-        const uint32_t T = val(c);
+        const uint32_t T = tasks(i, c);
+        // (a short-cut bucket's count is bounded by design, kCutMaxTasks: no fold level, no wave of its own is ever needed for it)
+        if (!taper || !msm_cut_short(cut, w, i, c)) mt = max(mt, T);
         stage[pad(i)] = T;
         // level 0 (div = task length): the bucket's T tasks are r of q + 1 points and T - r of q (balanced split, task_extent):
         // their lengths go into the schedule's histogram here, in O(1) per bucket whatever T is
@@ -681,12 +689,15 @@ __global__ __launch_bounds__(1024) void msm_scan_win_kernel(const uint32_t* __re
     uint32_t* v_o = v_out ? v_out + (size_t)w * NB : nullptr;
     for (uint32_t i = tid; i < NB; i += 1024) {
         off_o[i] = stage[pad(i)];
-        if (v_o) v_o[i] = val(cnt[i]);
+        if (v_o) v_o[i] = tasks(i, cnt[i]);
     }
     if (tid == 1023) win_total[w] = part[1023];
-    if (max_out) {
-        for (int o = 32; o > 0; o >>= 1) mx = max(mx, (uint32_t)__shfl_down((int)mx, o));
-        if ((tid & 63) == 0 && mx) atomicMax(max_out, mx);
+    if (max_out) {            // [0] the largest bucket population, [1] the largest task count of any bucket not cut short
+        for (int o = 32; o > 0; o >>= 1) {
+            mx = max(mx, (uint32_t)__shfl_down((int)mx, o));
+            mt = max(mt, (uint32_t)__shfl_down((int)mt, o));
+        }
+        if ((tid & 63) == 0 && mx) { atomicMax(max_out, mx); atomicMax(max_out + 1, mt); }
     }
 }
 // dynamic LDS of msm_scan_win_kernel for windows of NB buckets (above 64 KiB the runtime wants to be told once)
@@ -775,7 +786,8 @@ __global__ __launch_bounds__(256) void msm_bucket_fill_kernel(const uint32_t* __
                                                               const uint32_t* __restrict__ bucket_start,
                                                               const uint32_t* __restrict__ bucket_count, uint32_t NB, uint64_t TBK,
                                                               uint32_t* __restrict__ cursor, TaskDesc* __restrict__ desc,
-                                                              uint32_t* __restrict__ big_count, BigBucket* __restrict__ big, uint32_t direct) {
+                                                              uint32_t* __restrict__ big_count, BigBucket* __restrict__ big, uint32_t direct,
+                                                              MsmCut cut = MsmCut()) {
     __shared__ uint32_t h[kLenBins], base[kLenBins];
     h[threadIdx.x] = 0;
     __syncthreads();
@@ -789,7 +801,9 @@ __global__ __launch_bounds__(256) void msm_bucket_fill_kernel(const uint32_t* __
             start = bucket_start[t];
             tid0 = win_base[t / NB] + task_off[t];
             q = total / T; r = total - q * T;
-            if (T <= kFillInline) {
+            // short-cut buckets are neighbours: whole waves write their (bounded) descriptor runs side by side
+            const uint32_t inl = cut.n8 ? max(kFillInline, msm_cut_max_tasks(cut, (uint32_t)(t / NB), (uint32_t)(t % NB))) : kFillInline;
+            if (T <= inl) {
                 inline_fill = true;
                 if (r) rank_hi = atomicAdd(&h[min(q + 1, kLenBins - 1)], r);
                 rank_lo = atomicAdd(&h[min(q, kLenBins - 1)], T - r);
@@ -997,14 +1011,18 @@ __global__ __launch_bounds__(256) void msm_finalize_kernel(const XYZZ* __restric
                                                            const uint32_t* __restrict__ in_base,
                                                            XYZZ* __restrict__ buckets, uint32_t NB, uint32_t W, int accumulate,
                                                            uint32_t* __restrict__ big_count, BigFold* __restrict__ big, uint32_t big_thresh,
-                                                           int skip_single, int arith29) {
+                                                           int skip_single, int arith29, MsmCut cut = MsmCut()) {
     const size_t gt = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const size_t t = gt / GS;
+    size_t t = gt / GS;
     const uint32_t sub = (uint32_t)(gt % GS);
     if (t >= (size_t)W * NB) return;
+    if (GS == 1) t = (size_t)msm_cut_order(cut, W, t);            // tapered schedule: the buckets with many partial sums first
     const uint32_t w = (uint32_t)(t / NB);
     const uint32_t cnt = in_cnt[t];
     if (skip_single && cnt == 1) return;                          // the accumulator wrote this bucket itself (task_dst)
+    // Short-cut buckets (tapered schedule, level-0 partial sums) have up to msm_cut_max_tasks partial sums by design: they are
+    // neighbours in the bucket array, so whole waves fold that many side by side and none of them is a straggler to hand on.
+    if (cut.n8 != 0) big_thresh = max(big_thresh, msm_cut_max_tasks(cut, w, (uint32_t)(t - (size_t)w * NB)));
     if (GS == 1 && big != nullptr && cnt > big_thresh) {          // msm_fold_big_kernel writes (or adds onto) this bucket
         BigFold e; e.src = in_base[w] + in_off[t]; e.cnt = cnt; e.dst = (uint32_t)t; e.pad = 0;
         big[atomicAdd(big_count, 1u)] = e;
@@ -1922,6 +1940,7 @@ struct MsmGroup {
     uint32_t class_s = 0, nb2 = 0;                          // > 0: class-sum reduction (msm_class_sums_kernel), 2 * nb2 class sums per window
     uint32_t rl = 256;                                      // reduction lanes (quads) per workgroup
     uint32_t pk_bits = 0;   // > 0: 4-byte packed entries between the two sort passes (index bits)
+    MsmCut cut;             // how buckets are cut into tasks (msm_cut.hpp)
     SortPass sp[kMaxPasses];
     // state carried from phase 1 to phase 2
     uint32_t *cnt_cur = nullptr, *off_cur = nullptr, *base_cur = nullptr;
@@ -1985,7 +2004,8 @@ static int msm_group_plan(Ctx& c, MsmGroup& g, size_t n, uint32_t batch, int cb,
     // (measured: task-length sweeps at 2^14 .. 2^24, profiles/r01*_sweep*.txt).  Larger buckets are split evenly.
     const uint64_t mean_pop = (pre ? (uint64_t)W_total * n : (uint64_t)n) >> g.kb;
     g.L = (uint32_t)std::max<uint64_t>(16, std::min<uint64_t>(256, std::min<uint64_t>(4 * mean_pop, all_entries / 200000)));
-    g.bound0 = g.entries / g.L + g.TBK;                     // upper bound on level-0 tasks
+    g.cut = msm_cut_plan(g.L, g.NB, g.entries, c.tune_msm_taper);
+    g.bound0 = msm_task_bound(g.cut, g.Wd, g.entries);      // upper bound on level-0 tasks (entries / L + TBK without a taper)
     g.part_cap = g.bound0 + 2 * g.TBK;                      // every later level fits too
     g.P = g.kb <= 9 ? 1 : (g.kb <= 18 ? 2 : 3);             // radix passes of <= 9 bits, high bits first
     // Two-pass sorts: take 9 bits first when that lets {remaining key bits, sign, index} fit 32 bits --
@@ -2066,7 +2086,8 @@ static int msm_group_phase1(Ctx& c, MsmGroup& g, const Affine* points, const Sca
     uint32_t* win_tot = sm;
     uint32_t* d_max = sm + 3200;
     // ONE fill for everything this phase counts in: [3200] max, [3328, 3584) the task-length histogram, [3584, 3840) its cursors,
-    // [3900] the exception count, [3908] the big-bucket count (four fills before round 5: three launches less per MSM)
+    // [3900] the exception count, [3908] the big-bucket count (four fills before round 5: three launches less per MSM);
+    // [3201] the largest task count of a bucket rides beside the max
     UZK_HIP(hipMemsetAsync(d_max, 0, (3912 - 3200) * 4, st));
     // general mode, whole window range, chunks of >= 32768 scalars: digits and pass-0 histograms in one kernel
     const bool fused_hist = !g.pre && g.w0 == 0 && g.W == g.W_total && g.sp[0].nch >= 256 &&
@@ -2193,7 +2214,7 @@ static int msm_group_phase1(Ctx& c, MsmGroup& g, const Affine* points, const Sca
     {
         KernelScope ks(c, "msm_scan_win");
         hipLaunchKernelGGL(msm_scan_win_kernel, dim3(g.Wd), dim3(1024), scan_win_lds(g.NB), st, bcount, g.L, g.cnt_cur, g.off_cur, win_tot,
-                           d_max, g.NB, len_hist);
+                           d_max, g.NB, len_hist, g.cut);
         hipLaunchKernelGGL(msm_win_base_kernel, dim3(1), dim3(1024), 0, st, win_tot, g.base_cur, g.Wd);
     }
     TaskDesc* desc = m.task_desc.as<TaskDesc>();
@@ -2204,7 +2225,7 @@ static int msm_group_phase1(Ctx& c, MsmGroup& g, const Affine* points, const Sca
         UZK_TRY(m.big.reserve((size_t)(g.TBK + 1) * sizeof(BigBucket)));        // (shared with the fold lists of phase 2)
         hipLaunchKernelGGL(msm_task_scan_kernel, dim3(1), dim3(256), 0, st, len_hist, len_cur);
         hipLaunchKernelGGL(msm_bucket_fill_kernel, dim3((unsigned)((g.TBK + 255) / 256)), dim3(256), 0, st, g.base_cur, g.cnt_cur, g.off_cur,
-                           bstart, bcount, g.NB, g.TBK, len_cur, desc, big_count, m.big.as<BigBucket>(), g.direct ? 1u : 0u);
+                           bstart, bcount, g.NB, g.TBK, len_cur, desc, big_count, m.big.as<BigBucket>(), g.direct ? 1u : 0u, g.cut);
         hipLaunchKernelGGL(msm_task_fill_big_kernel, dim3(1024), dim3(64), 0, st, big_count, m.big.as<BigBucket>(), len_cur, desc);
     }
     {
@@ -2221,8 +2242,9 @@ static int msm_group_phase1(Ctx& c, MsmGroup& g, const Affine* points, const Sca
                            exc_count, exc_list, direct_buckets);
     }
     UZK_HIP(hipGetLastError());
-    // the largest bucket decides how many fold levels are needed (one tiny read-back)
-    UZK_HIP(hipMemcpyAsync(m.h_max, d_max, 4, hipMemcpyDeviceToHost, st));
+    // the bucket cut into the most tasks decides how many fold levels are needed (one tiny read-back: [0] the largest bucket
+    // population, [1] the largest task count, msm_scan_win_kernel)
+    UZK_HIP(hipMemcpyAsync(m.h_max, d_max, 8, hipMemcpyDeviceToHost, st));
     return UZK_OK;
 }
 
@@ -2241,7 +2263,10 @@ static int msm_group_phase2(Ctx& c, MsmGroup& g, bool accumulate = false, bool r
     XYZZ* partials = m.partials.as<XYZZ>();
     XYZZ* win_sums = m.win_sums.as<XYZZ>();
     const uint32_t G = kCombineFan;
-    uint64_t tmax = ((uint64_t)m.h_max[0] + g.L - 1) / g.L;
+    // the largest task count of any bucket, short-cut ones aside (msm_scan_win_kernel): those have at most kCutMaxTasks partial sums,
+    // which the last level folds in place; without a taper this is ceil(largest population / L)
+    static_assert(kCutMaxTasks <= kCombineFan, "a short-cut bucket must never need a fold level of its own");
+    uint64_t tmax = m.h_max[1];
     // lanes per fold group: latency mode for small problems, one lane per bucket for large ones
     // (measured at n = 2^14, batch 1..8: four lanes per bucket beat sixteen by 2..20 %)
     const uint32_t gs = g.TBK >= (1u << 18) ? 1u : (tmax > 2 ? 4u : 1u);
@@ -2266,6 +2291,7 @@ static int msm_group_phase2(Ctx& c, MsmGroup& g, bool accumulate = false, bool r
     const int skip_single = g.direct ? 1 : 0;
     int lvl = 0;
     uint64_t bound_prev = g.bound0;
+    const MsmCut fin_cut = tmax > G ? MsmCut() : g.cut;    // the last level folds level-0 partial sums: short-cut buckets have many
     while (tmax > G) {
         const int nx = (lvl + 1) & 1;
         UZK_TRY(m.lvl_part[nx].reserve((size_t)g.part_cap * sizeof(XYZZ)));   // no-op for buffer 0
@@ -2307,15 +2333,15 @@ static int msm_group_phase2(Ctx& c, MsmGroup& g, bool accumulate = false, bool r
         const dim3 grid((unsigned)((g.TBK * gs + 255) / 256));
         if (gs == 16)
             hipLaunchKernelGGL(msm_finalize_kernel<16>, grid, dim3(256), 0, st, g.part_cur, g.cnt_cur, g.off_cur, g.base_cur,
-                               buckets, g.NB, g.Wd, accumulate ? 1 : 0, (uint32_t*)nullptr, (BigFold*)nullptr, 0u, skip_single, a29);
+                               buckets, g.NB, g.Wd, accumulate ? 1 : 0, (uint32_t*)nullptr, (BigFold*)nullptr, 0u, skip_single, a29, fin_cut);
         else if (gs == 4)
             hipLaunchKernelGGL(msm_finalize_kernel<4>, grid, dim3(256), 0, st, g.part_cur, g.cnt_cur, g.off_cur, g.base_cur,
-                               buckets, g.NB, g.Wd, accumulate ? 1 : 0, (uint32_t*)nullptr, (BigFold*)nullptr, 0u, skip_single, a29);
+                               buckets, g.NB, g.Wd, accumulate ? 1 : 0, (uint32_t*)nullptr, (BigFold*)nullptr, 0u, skip_single, a29, fin_cut);
         else {
             const bool big_last = big_mode && tmax > kBigThresh;
             if (big_last) UZK_HIP(hipMemsetAsync(big_count, 0, 4, st));
             hipLaunchKernelGGL(msm_finalize_kernel<1>, grid, dim3(256), 0, st, g.part_cur, g.cnt_cur, g.off_cur, g.base_cur,
-                               buckets, g.NB, g.Wd, accumulate ? 1 : 0, big_count, big_last ? big_list : (BigFold*)nullptr, kBigThresh, skip_single, a29);
+                               buckets, g.NB, g.Wd, accumulate ? 1 : 0, big_count, big_last ? big_list : (BigFold*)nullptr, kBigThresh, skip_single, a29, fin_cut);
             if (big_last)
                 hipLaunchKernelGGL(msm_fold_big_kernel, dim3(2048), dim3(64), 0, st, g.part_cur, big_count, big_list, buckets, accumulate ? 1 : 0);
         }
