@@ -927,6 +927,56 @@ int uzk_shuffle_witness_batch(uint64_t circuit, uint64_t remark_key, const uint6
                               const uint32_t* perms, uint32_t cards, uint32_t batch, void* d_witness, void* d_wsel, uint64_t* pi_values_out,
                               uint64_t* e1_out, uint64_t* e2_out);
 
+/* ---- the matchmaking circuit: zmatchmaking's constraint system and its witness on the device ------------------------------------------
+ * build_cs (matchmaking/src/build_cs.rs:27-66) drives a TurboCS through new(), the variables of a match (N inputs, the random number,
+ * the committed seed and its Anemoi hash), Matchmaking::generate_constraints (matchmaking.rs:42-229: the constants 2 .. N - 1, the hash
+ * of the seed, the stream cipher over (seed, random number) with N - 1 outputs, then for i = 1 .. N - 1 the division of output i - 1 by
+ * i + 1, the one-hot bits of the remainder and the exchange of positions i and remainder of the running output vector), the 2 N + 2
+ * public inputs and pad.  For N players the resulting circuit is a pure function of N:
+ *   size      N + 15 + (14 P + N - 1 + [P > 1]) + sum_{i=1}^{N-1} (3 i + 4 + 2 ceil((i + 1) / 3)) + 2 N + 2 gates with P = 1 for
+ *             N <= 4 and ceil((N - 1) / 3) otherwise, padded to n = the next power of two (N = 50: 5 208 -> 8 192, 6 027 variables;
+ *             N = UZK_MATCH_CS_MAX_PLAYERS = 64: 8 295 -> 16 384)
+ *   tables    the indexer's evaluation vectors (indexer.rs:301-478) of a circuit without the "shuffle" feature: nine selectors (the
+ *             ninth, q_ecc, all zero), s = k[perm / n] omega^(perm mod n), qb on the running sums of the bits, q_prk = the round keys
+ *             after the linear layer on the 14 rows of each of the 1 + P permutation blocks
+ *   witness   every variable's value follows from the match, the traces of the two sponges and the remainders; extend_witness gathers
+ *             them by the wiring.  There are no wire selectors.
+ * The 19 key commitments come in the order of the reference's verifier key: cm_q (9, the eighth the point at infinity), cm_s (5), cm_qb,
+ * cm_prk (4).  tests/test_match_cs_ref_host.py and tests/test_gpu_match_cs.py hold the layout to the key the reference ships for 50
+ * players, bit for bit. */
+#define UZK_MATCH_CS_MIN_PLAYERS 3
+#define UZK_MATCH_CS_MAX_PLAYERS 64
+#define UZK_MATCH_CS_MAX_BATCH 1024
+#define UZK_MATCH_CS_KEY_COMMITMENTS 19
+/* Host only.  Every output optional (NULL); pi_rows_out: 2 players + 2 rows (verifier_params.public_vars_constraint_indices: the inputs,
+ * the outputs, the random number, the commitment).  players outside 3 .. UZK_MATCH_CS_MAX_PLAYERS: UZK_ERR_PARAMETER. */
+int uzk_match_cs_info(uint32_t players, uint32_t* size_out, uint32_t* n_out, uint32_t* num_vars_out, uint32_t* pi_count_out, uint32_t* pi_rows_out);
+typedef struct {
+    uint32_t players;                     /* UZK_MATCH_CS_MIN_PLAYERS .. UZK_MATCH_CS_MAX_PLAYERS */
+    uint32_t precompute;                  /* as uzk_circuit_desc.precompute */
+    const uzk_g1_affine* lagrange_bases;  /* n points, n = the padded size (uzk_match_cs_info) */
+    const uzk_g1_affine* blind_bases;     /* 6 points, as uzk_circuit_desc.blind_bases */
+    uint64_t k[5][4];                     /* verifier_params.k */
+    uint64_t group_gen[4];                /* must equal uzk_domain_group_gen(n), else UZK_ERR_FFT */
+} uzk_match_circuit_desc;
+/* Builds the layout, writes the evaluation vectors with one kernel and runs them through the path of uzk_circuit_refresh_tables
+ * (iFFT -> coset FFT -> Lagrange commit).  The handle is an ordinary circuit with shuffle = 0 and the Anemoi generator 5:
+ * uzk_prove_round1..5 (no wire selectors, 15 evaluations, 19 r_poly scalars), uzk_circuit_info, uzk_circuit_table and uzk_circuit_release
+ * take it unchanged.  commitments_out: optional, UZK_MATCH_CS_KEY_COMMITMENTS points. */
+int uzk_match_circuit_create(const uzk_match_circuit_desc* desc, uint64_t* circuit_out, uzk_g1_jac* commitments_out);
+/* Hashes the seeds, runs the stream ciphers and leaves the witnesses of `batch` matches on the device, ready for uzk_prove_round1 with
+ * inputs_on_device = 1 and no wire selectors.  The Anemoi traces never leave the device.
+ *   inputs_mont       batch x players elements;  seeds_mont, randoms_mont  batch elements each
+ *   d_witness         device, batch x 5 n elements: extend_witness (the rows behind the pad hold variable 0's value, zero)
+ *   pi_values_out     host, batch x (2 players + 2) elements in the order of the PI rows: verify_matchmaking's online inputs (inputs,
+ *                     outputs, random number, commitment)
+ *   outputs_out       host, batch x players elements: the matched order
+ *   commitments_out   host, batch elements: the Anemoi hash of every seed
+ * UZK_ERR_PARAMETER before the device is touched: a circuit not made by uzk_match_circuit_create, `players` (the size of the matches the
+ * caller's arrays hold) other than the circuit's, batch outside 1 .. UZK_MATCH_CS_MAX_BATCH, a null pointer, an element not below r. */
+int uzk_match_witness_batch(uint64_t circuit, const uint64_t* inputs_mont, const uint64_t* seeds_mont, const uint64_t* randoms_mont, uint32_t players,
+                            uint32_t batch, void* d_witness, uint64_t* pi_values_out, uint64_t* outputs_out, uint64_t* commitments_out);
+
 /* ---- Anemoi-Jive over BN254's scalar field: hashes, the stream cipher, their traces (uzkge/src/anemoi) -------------------------------
  * AnemoiJive254: 2 columns, 14 rounds, alpha = 5, g = 5, delta = 1 / g, the round keys of the Anemoi paper's pi rule; a sponge of rate
  * 3 (eval_variable_length_hash, eval_stream_cipher).  Batches run one lane per item, every item of a call with the same lengths.

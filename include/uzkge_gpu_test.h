@@ -135,6 +135,14 @@ int uzk_test_circuit_truncate_t(uint64_t circuit, int on);
  * public-key columns are laid out from `remark_key`'s T_pk, or from T_G when it is 0.  Every output optional (NULL). */
 int uzk_test_shuffle_cs_tables(uint64_t circuit, uint64_t remark_key, uint32_t* wiring_out, uint32_t* perm_out, uint64_t* evals_out);
 
+/* The matchmaking circuit as the library holds it: the wiring and the permutation (5 n words each, downloaded from the device), and
+ * the 19 evaluation vectors the table kernel writes, in slot order without l1 and coset_quotient: q (9), s (5), qb, q_prk (4) -- 19 n
+ * elements.  Every output optional (NULL). */
+int uzk_test_match_cs_tables(uint64_t circuit, uint32_t* wiring_out, uint32_t* perm_out, uint64_t* evals_out);
+/* The witness kernel's own division: `count` plain integers below r (4 words each, NOT Montgomery form) by m, 2 <= m <= 64.
+ * quot_out: count x 4 words, plain; rem_out: count words. */
+int uzk_test_match_divrem(const uint64_t* values, uint32_t m, uint32_t count, uint64_t* quot_out, uint32_t* rem_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -766,6 +766,79 @@ impl Drop for ShuffleCircuit {
     }
 }
 
+/// The shape of zmatchmaking's circuit for `players` (`uzk_match_cs_info`, host only): (gates, n, variables, the public-input rows).
+pub fn match_cs_info(players: u32) -> Result<(u32, u32, u32, Vec<u32>), Error> {
+    let (mut size, mut n, mut vars, mut pis) = (0u32, 0u32, 0u32, 0u32);
+    check(unsafe { uzk_match_cs_info(players, &mut size, &mut n, &mut vars, &mut pis, std::ptr::null_mut()) })?;
+    let mut rows = vec![0u32; pis as usize];
+    check(unsafe { uzk_match_cs_info(players, std::ptr::null_mut(), std::ptr::null_mut(), std::ptr::null_mut(), std::ptr::null_mut(), rows.as_mut_ptr()) })?;
+    Ok((size, n, vars, rows))
+}
+
+/// The witnesses of a batch of matches, resident on the device until dropped: what `uzk_prove_round1` takes with `inputs_on_device`
+/// and no wire selectors.
+pub struct MatchWitness {
+    pub d_witness: *mut std::os::raw::c_void,
+    /// batch x (2 players + 2) online inputs, in the order of `verify_matchmaking`: inputs, outputs, random number, commitment
+    pub pi_values: Vec<Limbs>,
+    /// batch x players: the matched order
+    pub outputs: Vec<Limbs>,
+    /// batch: the Anemoi hash of every seed
+    pub commitments: Vec<Limbs>,
+}
+impl Drop for MatchWitness {
+    fn drop(&mut self) {
+        unsafe { uzk_dev_free(self.d_witness) };
+    }
+}
+
+/// zmatchmaking's circuit for one number of players, laid out and preprocessed on the device (`uzk_match_circuit_create`): an ordinary
+/// circuit handle without the shuffle feature for the five rounds, plus the layout the witness kernels read.  Released on drop.
+pub struct MatchCircuit {
+    handle: u64,
+    players: u32,
+    n: u32,
+    /// the 19 commitments of the verifier key: cm_q (9), cm_s (5), cm_qb, cm_prk (4)
+    pub commitments: Vec<uzk_g1_jac>,
+}
+impl MatchCircuit {
+    /// `desc` and everything it points to are read before this returns.
+    pub fn create(desc: &uzk_match_circuit_desc) -> Result<Self, Error> {
+        let (_, n, _, _) = match_cs_info(desc.players)?;
+        let mut handle = 0u64;
+        let mut commitments = vec![uzk_g1_jac::default(); UZK_MATCH_CS_KEY_COMMITMENTS as usize];
+        check(unsafe { uzk_match_circuit_create(desc, &mut handle, commitments.as_mut_ptr()) })?;
+        Ok(Self { handle, players: desc.players, n, commitments })
+    }
+    pub fn handle(&self) -> u64 { self.handle }
+    pub fn n(&self) -> u32 { self.n }
+    pub fn players(&self) -> u32 { self.players }
+    /// Hashes the seeds, runs the stream ciphers and leaves the witnesses of `seeds.len()` matches on the device
+    /// (`uzk_match_witness_batch`).  Elements are Montgomery limbs below r.
+    pub fn witness_batch(&self, inputs: &[Limbs], seeds: &[Limbs], randoms: &[Limbs]) -> Result<MatchWitness, Error> {
+        let players = self.players as usize;
+        let batch = seeds.len();
+        if batch == 0 || batch > UZK_MATCH_CS_MAX_BATCH as usize || randoms.len() != batch || inputs.len() != batch * players {
+            return Err(Error::Parameter);
+        }
+        let n = self.n as usize;
+        let mut w = MatchWitness { d_witness: std::ptr::null_mut(), pi_values: vec![[0u64; 4]; batch * (2 * players + 2)],
+                                   outputs: vec![[0u64; 4]; batch * players], commitments: vec![[0u64; 4]; batch] };
+        check(unsafe { uzk_dev_alloc(32 * 5 * n * batch, &mut w.d_witness) })?;
+        check(unsafe {
+            uzk_match_witness_batch(self.handle, inputs.as_ptr() as *const u64, seeds.as_ptr() as *const u64, randoms.as_ptr() as *const u64, self.players,
+                                    batch as u32, w.d_witness, w.pi_values.as_mut_ptr() as *mut u64, w.outputs.as_mut_ptr() as *mut u64,
+                                    w.commitments.as_mut_ptr() as *mut u64)
+        })?;
+        Ok(w)
+    }
+}
+impl Drop for MatchCircuit {
+    fn drop(&mut self) {
+        unsafe { uzk_circuit_release(self.handle) };
+    }
+}
+
 /// m cards masked under the joint key (`uzk_cp_mask_prove_batch`): (e1, e2, m proof blobs of UZK_CP_PROOF_BYTES).  `rs` and `omegas`
 /// are plain integers below the subgroup order, drawn by the caller.
 pub fn cp_mask_prove_batch(pk: &EdPoint, cards: &[EdPoint], rs: &[Limbs], omegas: &[Limbs]) -> Result<(Vec<EdPoint>, Vec<EdPoint>, Vec<u8>), Error> {

@@ -148,6 +148,9 @@ PROTOTYPES = {
     "uzk_shuffle_circuit_create": (_I, [_P, ctypes.POINTER(_U64), _P]),
     "uzk_shuffle_circuit_set_key": (_I, [_U64, _U64, _P]),
     "uzk_shuffle_witness_batch": (_I, [_U64, _U64, _P, _P, _P, _P, ctypes.c_uint32, ctypes.c_uint32, _P, _P, _P, _P, _P]),
+    "uzk_match_cs_info": (_I, [ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32), _P]),
+    "uzk_match_circuit_create": (_I, [_P, ctypes.POINTER(_U64), _P]),
+    "uzk_match_witness_batch": (_I, [_U64, _P, _P, _P, ctypes.c_uint32, ctypes.c_uint32, _P, _P, _P, _P]),
     "uzk_cp_mask_prove_batch": (_I, [_P, _P, _P, _P, ctypes.c_uint32, _P, _P, _P]),
     "uzk_cp_mask_verify_batch": (_I, [_P, _P, _P, _P, _P, ctypes.c_uint32, _P, _P]),
     "uzk_anemoi_permute_batch": (_I, [_P, _SZ, _P]),
@@ -182,6 +185,8 @@ TEST_PROTOTYPES = {
     "uzk_test_g2_kat": (_I, [_I, _P, _P, _P, _SZ]),
     "uzk_test_circuit_truncate_t": (_I, [_U64, _I]),
     "uzk_test_shuffle_cs_tables": (_I, [_U64, _U64, _P, _P, _P]),
+    "uzk_test_match_cs_tables": (_I, [_U64, _P, _P, _P]),
+    "uzk_test_match_divrem": (_I, [_P, ctypes.c_uint32, ctypes.c_uint32, _P, _P]),
     "uzk_test_l29_kat": (_I, [_I, _I, ctypes.c_uint32, _P, _P, _SZ]),
     "uzk_test_p29_kat": (_I, [_I, _P, _P, _SZ]),
     "uzk_test_g2_raw_kat": (_I, [_I, _P, _P, _SZ]),
@@ -276,6 +281,22 @@ class ShuffleCircuitDesc(ctypes.Structure):
     """uzk_shuffle_circuit_desc (include/uzkge_gpu.h)."""
     _fields_ = [
         ("cards", ctypes.c_uint32), ("precompute", ctypes.c_uint32),
+        ("lagrange_bases", ctypes.c_void_p), ("blind_bases", ctypes.c_void_p),
+        ("k", (ctypes.c_uint64 * 4) * 5),
+        ("group_gen", ctypes.c_uint64 * 4),
+    ]
+
+
+MATCH_CS_MIN_PLAYERS = 3
+MATCH_CS_MAX_PLAYERS = 64
+MATCH_CS_MAX_BATCH = 1024
+MATCH_CS_KEY_COMMITMENTS = 19     # also uzk_test_match_cs_tables' evaluation vectors: q (9), s (5), qb, q_prk (4)
+
+
+class MatchCircuitDesc(ctypes.Structure):
+    """uzk_match_circuit_desc (include/uzkge_gpu.h)."""
+    _fields_ = [
+        ("players", ctypes.c_uint32), ("precompute", ctypes.c_uint32),
         ("lagrange_bases", ctypes.c_void_p), ("blind_bases", ctypes.c_void_p),
         ("k", (ctypes.c_uint64 * 4) * 5),
         ("group_gen", ctypes.c_uint64 * 4),

@@ -1056,6 +1056,74 @@ class ShuffleCircuit(Circuit):
         return wiring, perm, evals
 
 
+def match_cs_info(players: int) -> dict:
+    """uzk_match_cs_info (host only): the shape of zmatchmaking's circuit for `players`, and its public-input rows."""
+    v = [ctypes.c_uint32(0) for _ in range(4)]
+    check(lib.uzk_match_cs_info(players, *[ctypes.byref(x) for x in v], None))
+    rows = np.zeros(v[3].value, dtype=np.uint32)
+    check(lib.uzk_match_cs_info(players, None, None, None, None, rows.ctypes.data_as(ctypes.c_void_p)))
+    return dict(size=v[0].value, n=v[1].value, num_vars=v[2].value, pi_count=v[3].value, pi_rows=rows)
+
+
+class MatchCircuit(Circuit):
+    """uzk_match_circuit_create: zmatchmaking's circuit for `players`, laid out and preprocessed on the device.  A Circuit without the
+    shuffle feature in every respect (the rounds, info, table, release take it); `commitments` are the 19 of the verifier key
+    ([19, 12] Jacobian: cm_q (9), cm_s (5), cm_qb, cm_prk (4))."""
+
+    def __init__(self, players: int, lagrange_bases: np.ndarray, blind_bases: np.ndarray, k: np.ndarray, precompute: bool = False, group_gen=None):
+        info = match_cs_info(players)
+        n = info["n"]
+        d = N.MatchCircuitDesc()
+        d.players, d.precompute = players, int(precompute)
+        lag = np.ascontiguousarray(lagrange_bases, dtype=np.uint64).reshape(-1, 8)
+        bb = np.ascontiguousarray(blind_bases, dtype=np.uint64).reshape(-1, 8)
+        assert lag.shape[0] == n and bb.shape[0] == 6, "n Lagrange bases and 6 blind bases"
+        d.lagrange_bases, d.blind_bases = lag.ctypes.data, bb.ctypes.data
+        kk = np.ascontiguousarray(k, dtype=np.uint64).reshape(5, 4)
+        gg = np.ascontiguousarray(domain_group_gen(n) if group_gen is None else group_gen, dtype=np.uint64).reshape(4)
+        for j in range(5):
+            for w in range(4):
+                d.k[j][w] = int(kk[j, w])
+        for w in range(4):
+            d.group_gen[w] = int(gg[w])
+        h = ctypes.c_uint64(0)
+        self.commitments = np.zeros((N.MATCH_CS_KEY_COMMITMENTS, 12), dtype=np.uint64)
+        check(lib.uzk_match_circuit_create(ctypes.byref(d), ctypes.byref(h), _ptr(self.commitments)))
+        self.handle, self.n, self.shuffle, self.n_slots = h.value, n, False, CS_QPK
+        self.players, self.size, self.num_vars, self.pi_rows = players, info["size"], info["num_vars"], info["pi_rows"]
+
+    def witness_batch(self, inputs, seeds, randoms, d_witness: int):
+        """uzk_match_witness_batch: inputs [batch, players, 4]; seeds, randoms [batch, 4]; d_witness: the device address of batch x 5n
+        elements.  Returns (pi_values [batch, 2 players + 2, 4], outputs [batch, players, 4], commitments [batch, 4])."""
+        a = np.ascontiguousarray(inputs, dtype=np.uint64)
+        players = a.shape[-2] if a.ndim >= 2 else self.players         # the matches' own size: the library refuses any but the circuit's
+        a = a.reshape(-1, players, 4)
+        batch = a.shape[0]
+        sd = np.ascontiguousarray(seeds, dtype=np.uint64).reshape(-1, 4)
+        rn = np.ascontiguousarray(randoms, dtype=np.uint64).reshape(-1, 4)
+        assert sd.shape[0] == batch and rn.shape[0] == batch, "one seed and one random number per match"
+        pi = np.zeros((max(batch, 1), 2 * players + 2, 4), dtype=np.uint64)
+        out, cm = np.zeros((max(batch, 1), players, 4), dtype=np.uint64), np.zeros((max(batch, 1), 4), dtype=np.uint64)
+        check(lib.uzk_match_witness_batch(self.handle, _ptr(a), _ptr(sd), _ptr(rn), players, batch, ctypes.c_void_p(d_witness), _ptr(pi), _ptr(out), _ptr(cm)))
+        return pi[:batch], out[:batch], cm[:batch]
+
+    def test_tables(self):
+        """uzk_test_match_cs_tables (test hook): (wiring [5, n], permutation [5, n], evaluation vectors [19, n, 4])."""
+        wiring, perm = np.zeros((5, self.n), dtype=np.uint32), np.zeros((5, self.n), dtype=np.uint32)
+        evals = np.zeros((N.MATCH_CS_KEY_COMMITMENTS, self.n, 4), dtype=np.uint64)
+        vp = lambda arr: arr.ctypes.data_as(ctypes.c_void_p)
+        check(lib.uzk_test_match_cs_tables(self.handle, vp(wiring), vp(perm), _ptr(evals)))
+        return wiring, perm, evals
+
+
+def match_divrem(values, m: int):
+    """uzk_test_match_divrem (test hook): the witness kernel's division of plain integers [count, 4] by m -> (quotients [count, 4], remainders)."""
+    v = np.ascontiguousarray(values, dtype=np.uint64).reshape(-1, 4)
+    q, r = np.zeros_like(v), np.zeros(v.shape[0], dtype=np.uint32)
+    check(lib.uzk_test_match_divrem(_ptr(v), m, v.shape[0], _ptr(q), r.ctypes.data_as(ctypes.c_void_p)))
+    return q, r
+
+
 class VerifierKey:
     """A verifier key resident on the device (uzk_vk_create).  Points are wire rows of 8 words ((0,0) = infinity), scalars rows of 4;
     `prefix`: the caller's transcript bytes in front of transcript_init_plonk."""

@@ -90,4 +90,9 @@ int anemoi_sponge_run(Ctx& c, const Fp* inputs, uint32_t len, size_t n, uint32_t
     return UZK_OK;
 }
 
+int anemoi_sponge_device(Ctx& c, const Fp* d_inputs, uint32_t len, uint32_t n, uint32_t out_len, Fp* d_out, Fp* d_trace) {
+    UZK_LAUNCH(c, d_trace ? "anemoi_sponge_trace" : "anemoi_sponge", anemoi_sponge_kernel, dim3(an_grid(n)), dim3(kAnemoiBlock), 0, c.stream, d_inputs, len, out_len, d_out, d_trace, n);
+    return UZK_OK;
+}
+
 }  // namespace uzk

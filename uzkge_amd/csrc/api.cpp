@@ -17,6 +17,7 @@
 #include "host_ec64.hpp"
 #include "host_math.hpp"
 #include "shufflecs_dev.hpp"
+#include "matchcs_dev.hpp"
 
 namespace uzk {
 
@@ -234,6 +235,7 @@ static void ctx_release(Ctx& c) {
     c.g16v_ws.release();
     c.ed_ws.release();
     c.shuffle_ws.release();
+    c.match_ws.release();
     c.ed_gen.release();
     c.ed_gen_ready = false;
     c.pairing_ws.release();
@@ -1632,6 +1634,28 @@ int uzk_shuffle_witness_batch(uint64_t circuit, uint64_t remark_key, const uint6
 int uzk_test_shuffle_cs_tables(uint64_t circuit, uint64_t remark_key, uint32_t* wiring_out, uint32_t* perm_out, uint64_t* evals_out) try {
     return shcs_test_tables(circuit, remark_key, wiring_out, perm_out, evals_out);
 } catch (...) { return uzk::on_exception("uzk_test_shuffle_cs_tables"); }
+
+/* ---- the matchmaking circuit (matchcs.cpp takes the context lock itself) -------------------------- */
+int uzk_match_cs_info(uint32_t players, uint32_t* size_out, uint32_t* n_out, uint32_t* num_vars_out, uint32_t* pi_count_out, uint32_t* pi_rows_out) try {
+    return mcs_info(players, size_out, n_out, num_vars_out, pi_count_out, pi_rows_out);
+} catch (...) { return uzk::on_exception("uzk_match_cs_info"); }
+
+int uzk_match_circuit_create(const uzk_match_circuit_desc* desc, uint64_t* circuit_out, uzk_g1_jac* commitments_out) try {
+    return mcs_circuit_create(desc, circuit_out, commitments_out);
+} catch (...) { return uzk::on_exception("uzk_match_circuit_create"); }
+
+int uzk_match_witness_batch(uint64_t circuit, const uint64_t* inputs_mont, const uint64_t* seeds_mont, const uint64_t* randoms_mont, uint32_t players,
+                            uint32_t batch, void* d_witness, uint64_t* pi_values_out, uint64_t* outputs_out, uint64_t* commitments_out) try {
+    return mcs_witness_batch(circuit, inputs_mont, seeds_mont, randoms_mont, players, batch, d_witness, pi_values_out, outputs_out, commitments_out);
+} catch (...) { return uzk::on_exception("uzk_match_witness_batch"); }
+
+int uzk_test_match_cs_tables(uint64_t circuit, uint32_t* wiring_out, uint32_t* perm_out, uint64_t* evals_out) try {
+    return mcs_test_tables(circuit, wiring_out, perm_out, evals_out);
+} catch (...) { return uzk::on_exception("uzk_test_match_cs_tables"); }
+
+int uzk_test_match_divrem(const uint64_t* values, uint32_t m, uint32_t count, uint64_t* quot_out, uint32_t* rem_out) try {
+    return mcs_test_divrem(values, m, count, quot_out, rem_out);
+} catch (...) { return uzk::on_exception("uzk_test_match_divrem"); }
 
 int uzk_cp_mask_prove_batch(const uint64_t* pk_mont, const uint64_t* cards_mont, const uint64_t* rs, const uint64_t* omegas, uint32_t m, uint64_t* e1_out,
                             uint64_t* e2_out, uint8_t* proofs_out) try {

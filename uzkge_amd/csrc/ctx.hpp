@@ -158,6 +158,8 @@ struct Ctx {
     bool ed_gen_ready = false;
     // shufflecs.hip: one block carved into the arrays of a shuffle witness (decks, digits, the remark trace, variable values)
     DevBuf shuffle_ws;
+    // matchcs.hip: one block carved into the arrays of a matchmaking witness (matches, the two Anemoi traces, steps, variable values)
+    DevBuf match_ws;
     int tune_verify_transcript = 0;   // which transcript kernel a fold runs: 1 one proof per lane; 0 / 2 a proof's state spread over a half wave (the default)
     // an entry of the process-wide SRS registry
     struct Srs {
@@ -347,6 +349,9 @@ int cp_prove_run(Ctx& c, const Fp* sk, const EdAffine* e1, const Fp* omegas, uin
                  bool anemoi);
 int anemoi_permute_run(Ctx& c, const Fp* states, size_t n, Fp* out);                                          // anemoi.hip
 int anemoi_sponge_run(Ctx& c, const Fp* inputs, uint32_t len, size_t n, uint32_t out_len, Fp* out, Fp* trace_out);
+// the same sponge over inputs that are already on the device, with outputs and trace left there (matchcs.cpp): one launch, nothing is
+// copied and nothing waited for.  d_trace: null or n x P x 64 elements
+int anemoi_sponge_device(Ctx& c, const Fp* d_inputs, uint32_t len, uint32_t n, uint32_t out_len, Fp* d_out, Fp* d_trace);
 int ed_raw_op_device(Ctx& c, int op, const uint32_t* in, uint32_t* out, size_t n);
 // edwards.hip: the Chaum-Pedersen proofs of a mask; remask keys (process-wide handles: T_pk on the device), the tables and the remask
 int cp_mask_prove_run(Ctx& c, const EdAffine* pk, const EdAffine* cards, const Fp* rs, const Fp* omegas, uint32_t m, EdAffine* e1_out, EdAffine* e2_out,

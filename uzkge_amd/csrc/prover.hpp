@@ -40,6 +40,8 @@ struct CommitBases {
     ~CommitBases();
 };
 
+enum : uint32_t { kExtNone = 0, kExtShuffle = 1, kExtMatch = 2 };   // Circuit::ext_kind: uzk_circuit_create, uzk_shuffle_circuit_create, uzk_match_circuit_create
+
 struct Circuit {
     uint32_t n = 0, m = 0, shuffle = 0, n_slots = 0;
     int device = 0;
@@ -51,7 +53,10 @@ struct Circuit {
     int truncate_t = 0;                                            // uzk_test_circuit_truncate_t: a synthetic circuit no witness satisfies
     std::mutex mu;                                                 // guards `tables`
     std::shared_ptr<const TableSet> tables;
-    std::shared_ptr<void> ext;                                     // what the module that built the circuit keeps with it (shufflecs.cpp: the layout); set once, before the handle is handed out
+    // what the module that built the circuit keeps with it (shufflecs.cpp, matchcs.cpp: the layout) and whose it is: both set once,
+    // before the handle is handed out.  A module casts `ext` only after it has found its own tag in `ext_kind`.
+    std::shared_ptr<void> ext;
+    uint32_t ext_kind = kExtNone;
 };
 
 // The buffers of up to B proofs that advance in lockstep.  Layouts are per lane: lane b's part of every buffer lies a fixed

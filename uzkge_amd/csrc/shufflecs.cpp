@@ -24,7 +24,7 @@ struct ShuffleCs {
 };
 
 std::shared_ptr<ShuffleCs> shuffle_of(const std::shared_ptr<Circuit>& cir) {
-    return cir ? std::static_pointer_cast<ShuffleCs>(cir->ext) : nullptr;          // nothing else sets ext
+    return cir && cir->ext_kind == kExtShuffle ? std::static_pointer_cast<ShuffleCs>(cir->ext) : nullptr;      // the tag says whose ext is
 }
 
 struct Whole {                                                     // a block of exactly the carver's total, as the carver sees a buffer
@@ -134,7 +134,7 @@ int shcs_circuit_create(const uzk_shuffle_circuit_desc* desc, uint64_t* circuit_
         Ctx& c = ctx();
         rc = make_resident(c, *s);
         if (rc == UZK_OK) rc = install_tables(c, *cir, *s, reinterpret_cast<Jac*>(commitments_out));
-        if (rc == UZK_OK) cir->ext = s;
+        if (rc == UZK_OK) { cir->ext = s; cir->ext_kind = kExtShuffle; }
     }
     if (rc != UZK_OK) { (void)uzk_circuit_release(h); return rc; }
     *circuit_out = h;

@@ -4,6 +4,8 @@
 
 #include <algorithm>
 
+#include "csperm.hpp"
+
 namespace uzk {
 
 namespace {
@@ -126,17 +128,7 @@ bool shuffle_layout_build(uint32_t cards, ShuffleLayout* out) {
     L.sel.assign((size_t)kShcsSelectors * n, 0);
     for (uint32_t i = 0; i < kShcsWires; ++i) std::copy(B.w[i].begin(), B.w[i].end(), L.wiring.begin() + (size_t)i * n);
     for (uint32_t i = 0; i < kShcsSelectors; ++i) std::copy(B.q[i].begin(), B.q[i].end(), L.sel.begin() + (size_t)i * n);
-    // compute_permutation (constraint_system/mod.rs:64-92): every position points to the next later one that holds the same variable,
-    // the last back to the first.  Positions are bucketed per variable by a counting sort: O(5 n), where the reference scans.
-    const size_t total = (size_t)kShcsWires * n;
-    std::vector<uint32_t> start(L.num_vars + 1, 0), order(total);
-    for (size_t p = 0; p < total; ++p) ++start[L.wiring[p] + 1];
-    for (uint32_t v = 0; v < L.num_vars; ++v) start[v + 1] += start[v];
-    std::vector<uint32_t> fill(start.begin(), start.end() - 1);
-    for (size_t p = 0; p < total; ++p) order[fill[L.wiring[p]]++] = (uint32_t)p;
-    L.perm.assign(total, 0);
-    for (uint32_t v = 0; v < L.num_vars; ++v)
-        for (uint32_t s = start[v]; s < start[v + 1]; ++s) L.perm[order[s]] = order[s + 1 < start[v + 1] ? s + 1 : start[v]];
+    cs_compute_permutation(L.wiring, L.num_vars, &L.perm);
     return true;
 }
 
