@@ -191,6 +191,23 @@ static void test_carver_mixed_types() {
     CHECK(cv2.reserve(bad) == 3);
 }
 
+static void test_carver_bound_to_a_block_of_its_total() {
+    WsCarver cv;
+    const auto a = cv.array<uint32_t>(65);      // 260 bytes -> 512
+    const auto b = cv.array<uint16_t>(0);       // nothing
+    const auto c = cv.array<uint8_t>(7);        // 7 bytes -> 256
+    CHECK(cv.total() == 768);
+    std::vector<char> block(cv.total());        // exactly the total: the sanitizers see a write past any array's room
+    cv.bind(block.data());
+    CHECK(reinterpret_cast<char*>(cv(a)) == block.data() && reinterpret_cast<char*>(cv(b)) == block.data() + 512 &&
+          reinterpret_cast<char*>(cv(c)) == block.data() + 512);
+    cv(a)[64] = 5; cv(c)[6] = 9;
+    CHECK(reinterpret_cast<char*>(&cv(c)[7]) <= block.data() + cv.total());
+    // a later reserve moves the carver to the buffer, as for any other carver
+    FakeBuf buf;
+    CHECK(cv.reserve(buf) == 0 && buf.asked == 768 && reinterpret_cast<char*>(cv(a)) == FakeBuf::block);
+}
+
 int main() {
     test_handles_count_up_from_one();
     test_tables_refuse_each_others_handles();
@@ -199,6 +216,7 @@ int main() {
     test_threads();
     test_carver_byte_sizes();
     test_carver_mixed_types();
+    test_carver_bound_to_a_block_of_its_total();
     if (g_failed) { std::printf("%d checks failed\n", g_failed); return 1; }
     std::printf("OK\n");
     return 0;

@@ -3,46 +3,17 @@
 // <out>/<players>.bin as little-endian uint32 words for tests/test_match_cs_ref_host.py to compare with the Python restatement:
 //   players size n num_vars pi_count blocks | wiring 5n | perm 5n | sel 9n (as value + 32768) | qb n | prk_row n | defs num_vars |
 //   pi_rows | pi_vars | block_rows
-#include <cstdio>
-#include <cstdlib>
-#include <string>
-
+#include "cs_layout_check.hpp"
 #include "../../uzkge_amd/csrc/matchcs_layout.cpp"
 
 using namespace uzk;
 
-#define CHECK(cond)                                                              \
-    do {                                                                         \
-        if (!(cond)) { std::printf("FAILED %s:%d %s\n", __FILE__, __LINE__, #cond); return 1; } \
-    } while (0)
-
 static int check(const MatchLayout& L) {
-    const size_t total = (size_t)kMcsWires * L.n;
-    CHECK(L.size == match_layout_size(L.players) && L.size <= L.n && (L.n & (L.n - 1)) == 0 && L.n < 2 * L.size);
-    CHECK(L.wiring.size() == total && L.perm.size() == total && L.sel.size() == (size_t)kMcsSelectors * L.n);
-    CHECK(L.qb.size() == L.n && L.prk_row.size() == L.n && L.defs.size() == L.num_vars);
-    CHECK(L.pi_rows.size() == 2 * (size_t)L.players + 2 && L.pi_vars.size() == L.pi_rows.size() && L.block_rows.size() == 1 + (size_t)L.stream_perms);
-    // the permutation: a bijection that never leaves a variable, and walks every position of a variable in one cycle
-    std::vector<uint8_t> hit(total, 0);
-    std::vector<uint32_t> uses(L.num_vars, 0);
-    for (size_t p = 0; p < total; ++p) {
-        CHECK(L.wiring[p] < L.num_vars && L.perm[p] < total && !hit[L.perm[p]]);
-        hit[L.perm[p]] = 1;
-        CHECK(L.wiring[L.perm[p]] == L.wiring[p]);
-        ++uses[L.wiring[p]];
-    }
-    for (size_t p = 0; p < total; ++p) {
-        if (L.perm[p] > p) continue;                               // the one step back of a cycle: from its last position to its first
-        uint32_t len = 1;
-        for (size_t at = L.perm[p]; at != p; at = L.perm[at]) { CHECK(L.perm[at] > at); ++len; }
-        CHECK(len == uses[L.wiring[p]]);
-    }
-    for (uint32_t v = 0; v < L.num_vars; ++v) CHECK(uses[v] > 0);  // no dangling variable
-    for (uint32_t row = L.size; row < L.n; ++row)
-        for (uint32_t i = 0; i < kMcsWires; ++i) CHECK(L.wiring[(size_t)i * L.n + row] == 0);
+    if (cs_check_common(L, match_layout_size(L.players))) return 1;
+    CHECK(L.prk_row.size() == L.n && L.pi_rows.size() == 2 * (size_t)L.players + 2 && L.block_rows.size() == 1 + (size_t)L.stream_perms);
     // every definition's operands stay inside what the witness kernel indexes with them
     for (uint32_t d : L.defs) {
-        const uint32_t kind = d >> 28, a = (d >> 16) & 0xfff, b = (d >> 8) & 0xff, c = d & 0xff;
+        const uint32_t kind = cs_def_kind(d), a = cs_def_a(d), b = cs_def_b(d), c = cs_def_c(d);
         CHECK(kind <= kMcsSelect && c == 0);
         switch (kind) {
         case kMcsConst: case kMcsInput: CHECK(a < L.players); break;
@@ -60,8 +31,6 @@ static int check(const MatchLayout& L) {
         for (uint32_t r = 0; r < kMcsRounds + 1; ++r) CHECK(L.prk_row[L.block_rows[k] + r] == (r < kMcsRounds ? 1 + r : 0));
     return 0;
 }
-
-static void put(std::FILE* f, uint32_t v) { std::fwrite(&v, 4, 1, f); }
 
 int main(int argc, char** argv) {
     if (argc < 3) { std::printf("usage: matchcs_host <out dir> <players>...\n"); return 2; }

@@ -987,24 +987,27 @@ class Circuit:
             self.handle = 0
 
 
-def shuffle_cs_info(cards: int) -> dict:
-    """uzk_shuffle_cs_info (host only): the shape of zshuffle's circuit for a deck of `cards`, and its public-input rows."""
+def _cs_info(fn, count: int) -> dict:
+    """uzk_*_cs_info (host only): the shape of a circuit for `count` cards or players, and its public-input rows."""
     v = [ctypes.c_uint32(0) for _ in range(4)]
-    check(lib.uzk_shuffle_cs_info(cards, *[ctypes.byref(x) for x in v], None))
+    check(fn(count, *[ctypes.byref(x) for x in v], None))
     rows = np.zeros(v[3].value, dtype=np.uint32)
-    check(lib.uzk_shuffle_cs_info(cards, None, None, None, None, rows.ctypes.data_as(ctypes.c_void_p)))
+    check(fn(count, None, None, None, None, rows.ctypes.data_as(ctypes.c_void_p)))
     return dict(size=v[0].value, n=v[1].value, num_vars=v[2].value, pi_count=v[3].value, pi_rows=rows)
 
 
-class ShuffleCircuit(Circuit):
-    """uzk_shuffle_circuit_create: zshuffle's circuit for a deck of `cards`, laid out and preprocessed on the device.  A Circuit in
-    every respect (the rounds, info, table, release take it); `commitments` are the 32 of the verifier key ([32, 12] Jacobian)."""
+def shuffle_cs_info(cards: int) -> dict:
+    """uzk_shuffle_cs_info (host only): the shape of zshuffle's circuit for a deck of `cards`, and its public-input rows."""
+    return _cs_info(lib.uzk_shuffle_cs_info, cards)
 
-    def __init__(self, cards: int, lagrange_bases: np.ndarray, blind_bases: np.ndarray, k: np.ndarray, precompute: bool = False, group_gen=None):
-        info = shuffle_cs_info(cards)
+
+class _CsCircuit(Circuit):
+    """What ShuffleCircuit and MatchCircuit share: a circuit the library lays out itself from a count (cards, players)."""
+
+    def _create(self, info: dict, d, create, n_commitments: int, lagrange_bases, blind_bases, k, precompute, group_gen) -> None:
+        """Fills the fields every uzk_*_circuit_desc has into `d` (the count is the caller's), creates the circuit, keeps its shape."""
         n = info["n"]
-        d = N.ShuffleCircuitDesc()
-        d.cards, d.precompute = cards, int(precompute)
+        d.precompute = int(precompute)
         lag = np.ascontiguousarray(lagrange_bases, dtype=np.uint64).reshape(-1, 8)
         bb = np.ascontiguousarray(blind_bases, dtype=np.uint64).reshape(-1, 8)
         assert lag.shape[0] == n and bb.shape[0] == 6, "n Lagrange bases and 6 blind bases"
@@ -1017,10 +1020,30 @@ class ShuffleCircuit(Circuit):
         for w in range(4):
             d.group_gen[w] = int(gg[w])
         h = ctypes.c_uint64(0)
-        self.commitments = np.zeros((N.SHUFFLE_CS_KEY_COMMITMENTS, 12), dtype=np.uint64)
-        check(lib.uzk_shuffle_circuit_create(ctypes.byref(d), ctypes.byref(h), _ptr(self.commitments)))
-        self.handle, self.n, self.shuffle, self.n_slots = h.value, n, True, N.CIRCUIT_SLOTS
-        self.cards, self.size, self.num_vars, self.pi_rows = cards, info["size"], info["num_vars"], info["pi_rows"]
+        self.commitments = np.zeros((n_commitments, 12), dtype=np.uint64)
+        check(create(ctypes.byref(d), ctypes.byref(h), _ptr(self.commitments)))
+        self.handle, self.n = h.value, n
+        self.size, self.num_vars, self.pi_rows = info["size"], info["num_vars"], info["pi_rows"]
+
+    def _test_tables(self, tables: int, call):
+        """(wiring [5, n], permutation [5, n], evaluation vectors [tables, n, 4]) through call(wiring, perm, evals)."""
+        wiring, perm = np.zeros((5, self.n), dtype=np.uint32), np.zeros((5, self.n), dtype=np.uint32)
+        evals = np.zeros((tables, self.n, 4), dtype=np.uint64)
+        vp = lambda arr: arr.ctypes.data_as(ctypes.c_void_p)
+        check(call(vp(wiring), vp(perm), _ptr(evals)))
+        return wiring, perm, evals
+
+
+class ShuffleCircuit(_CsCircuit):
+    """uzk_shuffle_circuit_create: zshuffle's circuit for a deck of `cards`, laid out and preprocessed on the device.  A Circuit in
+    every respect (the rounds, info, table, release take it); `commitments` are the 32 of the verifier key ([32, 12] Jacobian)."""
+
+    def __init__(self, cards: int, lagrange_bases: np.ndarray, blind_bases: np.ndarray, k: np.ndarray, precompute: bool = False, group_gen=None):
+        d = N.ShuffleCircuitDesc()
+        d.cards = cards
+        self._create(shuffle_cs_info(cards), d, lib.uzk_shuffle_circuit_create, N.SHUFFLE_CS_KEY_COMMITMENTS, lagrange_bases, blind_bases, k,
+                     precompute, group_gen)
+        self.shuffle, self.n_slots, self.cards = True, N.CIRCUIT_SLOTS, cards
 
     def set_key(self, key: "RemarkKey") -> np.ndarray:
         """uzk_shuffle_circuit_set_key: the game's public-key tables from the key's T_pk; returns their 12 commitments [12, 12]."""
@@ -1049,48 +1072,25 @@ class ShuffleCircuit(Circuit):
 
     def test_tables(self, key: "RemarkKey" = None):
         """uzk_test_shuffle_cs_tables (test hook): (wiring [5, n], permutation [5, n], evaluation vectors [44, n, 4])."""
-        wiring, perm = np.zeros((5, self.n), dtype=np.uint32), np.zeros((5, self.n), dtype=np.uint32)
-        evals = np.zeros((N.SHUFFLE_CS_TABLES, self.n, 4), dtype=np.uint64)
-        vp = lambda arr: arr.ctypes.data_as(ctypes.c_void_p)
-        check(lib.uzk_test_shuffle_cs_tables(self.handle, key.handle if key is not None else 0, vp(wiring), vp(perm), _ptr(evals)))
-        return wiring, perm, evals
+        return self._test_tables(N.SHUFFLE_CS_TABLES, lambda *out: lib.uzk_test_shuffle_cs_tables(self.handle, key.handle if key is not None else 0, *out))
 
 
 def match_cs_info(players: int) -> dict:
     """uzk_match_cs_info (host only): the shape of zmatchmaking's circuit for `players`, and its public-input rows."""
-    v = [ctypes.c_uint32(0) for _ in range(4)]
-    check(lib.uzk_match_cs_info(players, *[ctypes.byref(x) for x in v], None))
-    rows = np.zeros(v[3].value, dtype=np.uint32)
-    check(lib.uzk_match_cs_info(players, None, None, None, None, rows.ctypes.data_as(ctypes.c_void_p)))
-    return dict(size=v[0].value, n=v[1].value, num_vars=v[2].value, pi_count=v[3].value, pi_rows=rows)
+    return _cs_info(lib.uzk_match_cs_info, players)
 
 
-class MatchCircuit(Circuit):
+class MatchCircuit(_CsCircuit):
     """uzk_match_circuit_create: zmatchmaking's circuit for `players`, laid out and preprocessed on the device.  A Circuit without the
     shuffle feature in every respect (the rounds, info, table, release take it); `commitments` are the 19 of the verifier key
     ([19, 12] Jacobian: cm_q (9), cm_s (5), cm_qb, cm_prk (4))."""
 
     def __init__(self, players: int, lagrange_bases: np.ndarray, blind_bases: np.ndarray, k: np.ndarray, precompute: bool = False, group_gen=None):
-        info = match_cs_info(players)
-        n = info["n"]
         d = N.MatchCircuitDesc()
-        d.players, d.precompute = players, int(precompute)
-        lag = np.ascontiguousarray(lagrange_bases, dtype=np.uint64).reshape(-1, 8)
-        bb = np.ascontiguousarray(blind_bases, dtype=np.uint64).reshape(-1, 8)
-        assert lag.shape[0] == n and bb.shape[0] == 6, "n Lagrange bases and 6 blind bases"
-        d.lagrange_bases, d.blind_bases = lag.ctypes.data, bb.ctypes.data
-        kk = np.ascontiguousarray(k, dtype=np.uint64).reshape(5, 4)
-        gg = np.ascontiguousarray(domain_group_gen(n) if group_gen is None else group_gen, dtype=np.uint64).reshape(4)
-        for j in range(5):
-            for w in range(4):
-                d.k[j][w] = int(kk[j, w])
-        for w in range(4):
-            d.group_gen[w] = int(gg[w])
-        h = ctypes.c_uint64(0)
-        self.commitments = np.zeros((N.MATCH_CS_KEY_COMMITMENTS, 12), dtype=np.uint64)
-        check(lib.uzk_match_circuit_create(ctypes.byref(d), ctypes.byref(h), _ptr(self.commitments)))
-        self.handle, self.n, self.shuffle, self.n_slots = h.value, n, False, CS_QPK
-        self.players, self.size, self.num_vars, self.pi_rows = players, info["size"], info["num_vars"], info["pi_rows"]
+        d.players = players
+        self._create(match_cs_info(players), d, lib.uzk_match_circuit_create, N.MATCH_CS_KEY_COMMITMENTS, lagrange_bases, blind_bases, k,
+                     precompute, group_gen)
+        self.shuffle, self.n_slots, self.players = False, CS_QPK, players
 
     def witness_batch(self, inputs, seeds, randoms, d_witness: int):
         """uzk_match_witness_batch: inputs [batch, players, 4]; seeds, randoms [batch, 4]; d_witness: the device address of batch x 5n
@@ -1109,11 +1109,7 @@ class MatchCircuit(Circuit):
 
     def test_tables(self):
         """uzk_test_match_cs_tables (test hook): (wiring [5, n], permutation [5, n], evaluation vectors [19, n, 4])."""
-        wiring, perm = np.zeros((5, self.n), dtype=np.uint32), np.zeros((5, self.n), dtype=np.uint32)
-        evals = np.zeros((N.MATCH_CS_KEY_COMMITMENTS, self.n, 4), dtype=np.uint64)
-        vp = lambda arr: arr.ctypes.data_as(ctypes.c_void_p)
-        check(lib.uzk_test_match_cs_tables(self.handle, vp(wiring), vp(perm), _ptr(evals)))
-        return wiring, perm, evals
+        return self._test_tables(N.MATCH_CS_KEY_COMMITMENTS, lambda *out: lib.uzk_test_match_cs_tables(self.handle, *out))
 
 
 def match_divrem(values, m: int):

@@ -84,6 +84,8 @@ class WsCarver {
         if (rc == 0) base_ = static_cast<char*>(buf.p);
         return rc;
     }
+    // a block of the caller's own, of exactly total() bytes, in place of a buffer that grows
+    void bind(void* block) { base_ = static_cast<char*>(block); }
     template <class T>
     T* operator()(const WsArray<T>& a) const { return reinterpret_cast<T*>(base_ + a.offset); }
 

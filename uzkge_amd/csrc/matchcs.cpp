@@ -5,86 +5,36 @@
 #include <cstring>
 
 #include "host_math.hpp"
-#include "handles.hpp"
-#include "prover.hpp"
 #include "matchcs_dev.hpp"
 #include "matchcs_consts.inc"
 
 using namespace uzk;
-#define API_LOCK std::lock_guard<std::mutex> _lk(ctx_mutex())
 
 namespace {
 
-struct MatchCs {
+struct MatchCs : CsResident {
     MatchLayout host;
-    std::shared_ptr<DevBlock> blk;                                 // the device copies below, carved out of one block
-    const uint32_t *d_wiring = nullptr, *d_defs = nullptr, *d_pi_vars = nullptr;
-    const int16_t* d_sel = nullptr;
-    const uint8_t *d_qb = nullptr, *d_prk_row = nullptr;
-    const Fp* d_prk = nullptr;                                     // [14][4]
+    const uint8_t* d_prk_row = nullptr;
+    const Fp* d_prk = nullptr;                                     // [14][4]: the round keys after the linear layer
 };
 
-std::shared_ptr<MatchCs> match_of(const std::shared_ptr<Circuit>& cir) {
-    return cir && cir->ext_kind == kExtMatch ? std::static_pointer_cast<MatchCs>(cir->ext) : nullptr;          // the tag says whose ext is
-}
-
-struct Whole {                                                     // a block of exactly the carver's total, as the carver sees a buffer
-    void* p;
-    int reserve(size_t) { return UZK_OK; }
-};
-
-template <class T>
-int put(Ctx& c, T* dst, const std::vector<T>& src) {
-    UZK_HIP(hipMemcpyAsync(dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice, c.stream));
-    return UZK_OK;
-}
+std::shared_ptr<MatchCs> match_of(const std::shared_ptr<Circuit>& cir) { return cs_ext<MatchCs>(cir, kExtMatch); }
 
 int make_resident(Ctx& c, MatchCs& s) {
     const MatchLayout& L = s.host;
-    WsCarver cv;
-    const auto a_w = cv.array<uint32_t>(L.wiring.size()), a_d = cv.array<uint32_t>(L.defs.size()), a_p = cv.array<uint32_t>(L.pi_vars.size());
-    const auto a_s = cv.array<int16_t>(L.sel.size());
-    const auto a_q = cv.array<uint8_t>(L.qb.size()), a_r = cv.array<uint8_t>(L.prk_row.size());
-    const auto a_k = cv.array<Fp>(kMcsRounds * 4);
-    UZK_TRY(dev_block(cv.total(), &s.blk));
-    Whole whole{s.blk->p};
-    UZK_TRY(cv.reserve(whole));
-    UZK_TRY(put(c, cv(a_w), L.wiring)); UZK_TRY(put(c, cv(a_d), L.defs)); UZK_TRY(put(c, cv(a_p), L.pi_vars));
-    UZK_TRY(put(c, cv(a_s), L.sel)); UZK_TRY(put(c, cv(a_q), L.qb)); UZK_TRY(put(c, cv(a_r), L.prk_row));
-    static_assert(sizeof kMcsPrk == kMcsRounds * 4 * sizeof(Fp), "one Fp per round key");
-    UZK_HIP(hipMemcpyAsync(cv(a_k), kMcsPrk, sizeof kMcsPrk, hipMemcpyHostToDevice, c.stream));
-    UZK_HIP(hipStreamSynchronize(c.stream));
-    s.d_wiring = cv(a_w); s.d_defs = cv(a_d); s.d_pi_vars = cv(a_p); s.d_sel = cv(a_s); s.d_qb = cv(a_q); s.d_prk_row = cv(a_r); s.d_prk = cv(a_k);
-    return UZK_OK;
+    WsArray<uint8_t> a_r;
+    WsArray<Fp> a_k;
+    return cs_make_resident(c, L, &s, [&](WsCarver& cv) { a_r = cv.array<uint8_t>(L.prk_row.size()); a_k = cv.array<Fp>(kMcsRounds * 4); },
+                            [&](const WsCarver& cv) {
+        s.d_prk_row = cv(a_r); s.d_prk = cv(a_k);
+        UZK_TRY(cs_put(c, cv(a_r), L.prk_row));
+        static_assert(sizeof kMcsPrk == kMcsRounds * 4 * sizeof(Fp), "one Fp per round key");
+        UZK_HIP(hipMemcpyAsync(cv(a_k), kMcsPrk, sizeof kMcsPrk, hipMemcpyHostToDevice, c.stream));
+        return UZK_OK;
+    });
 }
 
-McsTableArgs table_args(const Circuit& cir, const MatchCs& s, Fp* d_out) {
-    McsTableArgs a = {};
-    a.n = cir.n; a.sel = s.d_sel; a.qb = s.d_qb; a.prk_row = s.d_prk_row; a.perm = cir.d_perm; a.group = cir.d_group; a.prk = s.d_prk; a.out = d_out;
-    for (uint32_t w = 0; w < kMcsWires; ++w) a.k[w] = cir.k[w];
-    return a;
-}
-
-int circuit_here(const Circuit& cir, const char* who) {
-    UZK_TRY(require_ready());
-    if (ctx().device != cir.device) { set_error("%s: the circuit lives on device %d, the calling context on device %d", who, cir.device, ctx().device); return UZK_ERR_PARAMETER; }
-    return UZK_OK;
-}
-
-// the tables of a fresh circuit: one pass of the table kernel, then two refreshes (slot 14, l1, and slot 20, coset_quotient, are the
-// circuit's own); cms: the 19 key commitments in the verifier key's order, or null
-int install_tables(Ctx& c, Circuit& cir, const MatchCs& s, Jac* cms) {
-    const uint32_t n = cir.n;
-    std::shared_ptr<DevBlock> evals;
-    UZK_TRY(dev_block((size_t)kMcsTables * n * sizeof(Fp), &evals));
-    Fp* d = static_cast<Fp*>(evals->p);
-    UZK_TRY(mcs_tables_run(c, table_args(cir, s, d)));
-    std::vector<Jac> cm(kMcsTables);
-    UZK_TRY(circuit_refresh_device(c, cir, UZK_CS_Q, 14, d, cm.data()));
-    UZK_TRY(circuit_refresh_device(c, cir, UZK_CS_QB, 5, d + (size_t)kMcsTabQb * n, cm.data() + kMcsTabQb));
-    if (cms) std::memcpy(cms, cm.data(), kMcsTables * sizeof(Jac));                                // cm_q, cm_s, cm_qb, cm_prk
-    return UZK_OK;
-}
+CsTableArgs table_args(const Circuit& cir, const MatchCs& s, Fp* d_out) { return cs_table_args(cir, s, s.d_prk_row, s.d_prk, d_out); }
 
 }  // namespace
 
@@ -95,11 +45,7 @@ namespace uzk {
 int mcs_info(uint32_t players, uint32_t* size_out, uint32_t* n_out, uint32_t* num_vars_out, uint32_t* pi_count_out, uint32_t* pi_rows_out) {
     MatchLayout L;
     if (!match_layout_build(players, &L)) { set_error("uzk_match_cs_info: %u players (%d .. %d)", players, UZK_MATCH_CS_MIN_PLAYERS, UZK_MATCH_CS_MAX_PLAYERS); return UZK_ERR_PARAMETER; }
-    if (size_out) *size_out = L.size;
-    if (n_out) *n_out = L.n;
-    if (num_vars_out) *num_vars_out = L.num_vars;
-    if (pi_count_out) *pi_count_out = (uint32_t)L.pi_rows.size();
-    if (pi_rows_out) std::memcpy(pi_rows_out, L.pi_rows.data(), L.pi_rows.size() * sizeof(uint32_t));
+    cs_info(L, size_out, n_out, num_vars_out, pi_count_out, pi_rows_out);
     return UZK_OK;
 }
 
@@ -107,34 +53,20 @@ int mcs_circuit_create(const uzk_match_circuit_desc* desc, uint64_t* circuit_out
     if (!desc || !circuit_out) { set_error("uzk_match_circuit_create: null pointer"); return UZK_ERR_PARAMETER; }
     auto s = std::make_shared<MatchCs>();
     if (!match_layout_build(desc->players, &s->host)) { set_error("uzk_match_circuit_create: %u players (%d .. %d)", desc->players, UZK_MATCH_CS_MIN_PLAYERS, UZK_MATCH_CS_MAX_PLAYERS); return UZK_ERR_PARAMETER; }
-    const uint32_t n = s->host.n;
-    // an ordinary circuit without the "shuffle" feature over the layout's permutation with empty tables; l1 = the iFFT of (n, 0, ..): n ones
-    uzk_circuit_desc cd = {};
-    cd.n = n; cd.shuffle = 0; cd.precompute = desc->precompute;
-    cd.lagrange_bases = desc->lagrange_bases; cd.blind_bases = desc->blind_bases;
-    cd.permutation = s->host.perm.data();
-    std::memcpy(cd.k, desc->k, sizeof cd.k);
-    std::memcpy(cd.group_gen, desc->group_gen, sizeof cd.group_gen);
-    const Fp one = Fr::one(), g = fr_from_u64(5), g_inv = fr_inv(g);   // AnemoiJive254: generator 5 and delta = 1 / 5; no edwards_a
-    std::memcpy(cd.anemoi_g, &g, sizeof g);
-    std::memcpy(cd.anemoi_g_inv, &g_inv, sizeof g_inv);
-    std::vector<Fp> l1(n, one);
-    cd.polys[UZK_CS_L1] = reinterpret_cast<const uint64_t*>(l1.data());
-    cd.poly_lens[UZK_CS_L1] = n;
-    uint64_t h = 0;
-    UZK_TRY(uzk_circuit_create(&cd, &h));
-    int rc;
-    {
-        API_LOCK;
-        auto cir = find_circuit(h);
-        Ctx& c = ctx();
-        rc = make_resident(c, *s);
-        if (rc == UZK_OK) rc = install_tables(c, *cir, *s, reinterpret_cast<Jac*>(commitments_out));
-        if (rc == UZK_OK) { cir->ext = s; cir->ext_kind = kExtMatch; }
-    }
-    if (rc != UZK_OK) { (void)uzk_circuit_release(h); return rc; }
-    *circuit_out = h;
-    return UZK_OK;
+    // without the "shuffle" feature; the tables: one pass of the table kernel and the two common refreshes; commitments_out: the 19
+    // key commitments in the verifier key's order (cm_q, cm_s, cm_qb, cm_prk), or null
+    return cs_circuit_create(cs_desc_of(*desc), s->host, [](uzk_circuit_desc& cd) {
+        const Fp g = fr_from_u64(5), g_inv = fr_inv(g);            // AnemoiJive254: generator 5 and delta = 1 / 5; no edwards_a
+        std::memcpy(cd.anemoi_g, &g, sizeof g);
+        std::memcpy(cd.anemoi_g_inv, &g_inv, sizeof g_inv);
+    }, kExtMatch, s, [&](Ctx& c, Circuit& cir) {
+        UZK_TRY(make_resident(c, *s));
+        std::shared_ptr<DevBlock> evals;
+        std::vector<Jac> cm(kMcsTables);
+        UZK_TRY(cs_install_common(c, cir, kMcsTables, [&](Fp* d) { return cs_tables_run(c, table_args(cir, *s, d)); }, &evals, cm.data()));
+        if (commitments_out) std::memcpy(commitments_out, cm.data(), kMcsTables * sizeof(Jac));
+        return UZK_OK;
+    }, circuit_out);
 }
 
 int mcs_witness_batch(uint64_t circuit, const uint64_t* inputs_mont, const uint64_t* seeds_mont, const uint64_t* randoms_mont, uint32_t players,
@@ -154,7 +86,7 @@ int mcs_witness_batch(uint64_t circuit, const uint64_t* inputs_mont, const uint6
         const size_t count = (size_t)batch * ck.per, bad = ed_first_noncanonical(reinterpret_cast<const Fp*>(ck.words), count);
         if (bad < count) { set_error("%s: %s %zu of match %zu is not below r", who, ck.name, bad % ck.per, bad / ck.per); return UZK_ERR_PARAMETER; }
     }
-    UZK_TRY(circuit_here(*cir, who));
+    UZK_TRY(cs_circuit_here(*cir, who));
     Ctx& c = ctx();
     // the cipher's input of a match: (seed, random number)
     std::vector<Fp> pairs(2 * (size_t)batch);
@@ -197,14 +129,13 @@ int mcs_test_tables(uint64_t circuit, uint32_t* wiring_out, uint32_t* perm_out, 
     auto cir = find_circuit(circuit);
     auto s = match_of(cir);
     if (!s) { set_error("uzk_test_match_cs_tables: %llu is no circuit of uzk_match_circuit_create", (unsigned long long)circuit); return UZK_ERR_PARAMETER; }
-    UZK_TRY(circuit_here(*cir, "uzk_test_match_cs_tables"));
+    UZK_TRY(cs_circuit_here(*cir, "uzk_test_match_cs_tables"));
     Ctx& c = ctx();
-    const size_t n = cir->n, words = kMcsWires * n * sizeof(uint32_t);
-    if (wiring_out) UZK_HIP(hipMemcpyAsync(wiring_out, s->d_wiring, words, hipMemcpyDeviceToHost, c.stream));
-    if (perm_out) UZK_HIP(hipMemcpyAsync(perm_out, cir->d_perm, words, hipMemcpyDeviceToHost, c.stream));
+    const size_t n = cir->n;
+    UZK_TRY(cs_test_tables_common(c, *cir, *s, wiring_out, perm_out));
     if (evals_out) {
         UZK_TRY(c.match_ws.reserve(kMcsTables * n * sizeof(Fp)));
-        UZK_TRY(mcs_tables_run(c, table_args(*cir, *s, c.match_ws.as<Fp>())));
+        UZK_TRY(cs_tables_run(c, table_args(*cir, *s, c.match_ws.as<Fp>())));
         UZK_HIP(hipMemcpyAsync(evals_out, c.match_ws.p, kMcsTables * n * sizeof(Fp), hipMemcpyDeviceToHost, c.stream));
     }
     UZK_HIP(hipStreamSynchronize(c.stream));

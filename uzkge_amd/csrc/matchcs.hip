@@ -1,6 +1,6 @@
 // zmatchmaking's circuit on the device (include/uzkge_gpu.h, "the matchmaking circuit"): the evaluation vectors of its tables and the
 // witnesses of `batch` matches, from the compact layout of matchcs.hpp and the two Anemoi traces anemoi_sponge_device leaves in HBM.
-//   mcs_tables   per row: 9 q (small signed integers into Fr), 5 s (one product k[w] omega^i each), qb, 4 q_prk    19 stores of 32 B
+//   cs_tables    per row: 9 q (small signed integers into Fr), 5 s (one product k[w] omega^i each), qb, 4 q_prk    19 stores of 32 B
 //   mcs_steps    one wave of 64 lanes per match.  Lane i (1 <= i < N) takes stream output i - 1 out of Montgomery form and divides its
 //                eight 32-bit words by i + 1 <= 64.  Then LANE j HOLDS POSITION j of the running output vector as an index into the
 //                inputs, in a register, and the N - 1 steps run one after the other: step i exchanges positions i and rem_i.  The only
@@ -9,26 +9,14 @@
 //   mcs_values   per (match, variable): the variable's definition in Fr -- a load, a small integer, or an input picked through a row
 //                of the step kernel's index table.  No sum is formed: a running sum of one-hot bits is rem < count, a running sum of
 //                the products is the picked input or zero
-//   mcs_gather   per (match, wire, row): extended[w][row] = value[wiring[w][row]]; the 2 N + 2 items behind them: the public inputs
+//   cs_gather    per (match, wire, row): extended[w][row] = value[wiring[w][row]]; the 2 N + 2 items behind them: the public inputs
 // Every launch but mcs_steps moves 32-byte elements and does next to no arithmetic; mcs_steps is N - 1 dependent steps of two
 // cross-lane reads and a 64-byte store.  A match's cost is its 18 (N = 50) serial Anemoi permutations, not these.
-#include "ctx.hpp"
 #include "matchcs_dev.hpp"
 
 namespace uzk {
 
-constexpr uint32_t kMcsBlock = 256;
-static uint32_t mcs_grid(size_t items) { return (uint32_t)((items + kMcsBlock - 1) / kMcsBlock); }
-
 #if defined(__HIP_DEVICE_COMPILE__)
-__device__ __forceinline__ Fp mcs_bit(bool on) { return on ? Fr::one() : Fr::zero(); }
-// an integer of magnitude below 2^15 as an element of Fr
-__device__ __forceinline__ Fp mcs_small(int v) {
-    Fp p = Fr::zero();
-    p.v[0] = (uint32_t)(v < 0 ? -v : v);
-    const Fp r = Fr::to_mont(p);
-    return v < 0 ? Fr::neg(r) : r;
-}
 // Long division of a plain 256-bit integer by m, 2 <= m <= 64, sixteen bits at a time from the top: the running remainder stays
 // below m, so every partial dividend is below 2^22 and every partial quotient below 2^16.  Returns the remainder.
 __device__ __forceinline__ uint32_t mcs_divrem(const Fp& plain, uint32_t m, Fp* quot) {
@@ -46,24 +34,6 @@ __device__ __forceinline__ uint32_t mcs_divrem(const Fp& plain, uint32_t m, Fp* 
     return rem;
 }
 #endif
-
-__global__ __launch_bounds__(kMcsBlock) void mcs_tables_kernel(McsTableArgs a) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    const uint32_t row = blockIdx.x * kMcsBlock + threadIdx.x, n = a.n;
-    if (row >= n) return;
-    for (uint32_t i = 0; i < kMcsSelectors; ++i) {
-        const int v = a.sel[(size_t)i * n + row];
-        a.out[(size_t)i * n + row] = v == 0 ? Fr::zero() : mcs_small(v);
-    }
-    for (uint32_t w = 0; w < kMcsWires; ++w) {                     // encode_perm_to_group: k[perm / n] group[perm mod n]
-        const uint32_t p = a.perm[(size_t)w * n + row];
-        a.out[(size_t)(kMcsTabS + w) * n + row] = Fr::mul(a.k[p / n], a.group[p % n]);
-    }
-    a.out[(size_t)kMcsTabQb * n + row] = mcs_bit(a.qb[row] != 0);
-    const uint32_t r = a.prk_row[row];                             // 0, or 1 + round <= 14
-    for (uint32_t i = 0; i < 4; ++i) a.out[(size_t)(kMcsTabPrk + i) * n + row] = r ? a.prk[(r - 1) * 4 + i] : Fr::zero();
-#endif
-}
 
 // one wave per match; every lane runs to the end (the shuffles read all 64)
 __global__ __launch_bounds__(kMcsLanes) void mcs_steps_kernel(McsWitnessArgs a) {
@@ -89,18 +59,18 @@ __global__ __launch_bounds__(kMcsLanes) void mcs_steps_kernel(McsWitnessArgs a) 
 #endif
 }
 
-__global__ __launch_bounds__(kMcsBlock) void mcs_values_kernel(McsWitnessArgs a) {
+__global__ __launch_bounds__(kCsBlock) void mcs_values_kernel(McsWitnessArgs a) {
 #if defined(__HIP_DEVICE_COMPILE__)
-    const uint32_t v = blockIdx.x * kMcsBlock + threadIdx.x, match = blockIdx.y, N = a.players;
+    const uint32_t v = blockIdx.x * kCsBlock + threadIdx.x, match = blockIdx.y, N = a.players;
     if (v >= a.num_vars) return;
-    const uint32_t d = a.defs[v], kind = d >> 28, x = (d >> 16) & 0xfff, y = (d >> 8) & 0xff;
+    const uint32_t d = a.defs[v], kind = cs_def_kind(d), x = cs_def_a(d), y = cs_def_b(d);
     const Fp* in = a.inputs + (size_t)match * N;
     const uint8_t* state = a.state + (size_t)match * (N + 1) * kMcsLanes;
     // steps are x = 1 .. N - 1 in every kind that reads them (matchcs_layout.cpp; tests/cpp/matchcs_host.cpp checks every operand)
     const uint32_t rem = kind >= kMcsRem ? a.rem[(size_t)match * kMcsLanes + x] : 0;
     Fp r = Fr::zero();
     switch (kind) {
-    case kMcsConst: r = mcs_small((int)x); break;
+    case kMcsConst: r = cs_small((int)x); break;
     case kMcsInput: r = in[x]; break;
     case kMcsSeed: r = a.seeds[match]; break;
     case kMcsRandom: r = a.randoms[match]; break;
@@ -109,9 +79,9 @@ __global__ __launch_bounds__(kMcsBlock) void mcs_values_kernel(McsWitnessArgs a)
     case kMcsStreamTrace: r = a.stream_trace[((size_t)match * a.stream_perms + x) * kMcsTraceElems + y]; break;
     case kMcsStreamOut: r = a.stream_out[(size_t)match * (N - 1) + x]; break;
     case kMcsQuot: r = a.quot[(size_t)match * kMcsLanes + x]; break;
-    case kMcsRem: r = mcs_small((int)rem); break;
-    case kMcsBit: r = mcs_bit(rem == y); break;
-    case kMcsBitSum: r = mcs_bit(rem < y); break;
+    case kMcsRem: r = cs_small((int)rem); break;
+    case kMcsBit: r = cs_bit(rem == y); break;
+    case kMcsBitSum: r = cs_bit(rem < y); break;
     case kMcsProduct: if (rem == y) r = in[state[(size_t)x * kMcsLanes + y]]; break;
     case kMcsProdSum: if (rem < y) r = in[state[(size_t)x * kMcsLanes + rem]]; break;
     default: r = in[state[(size_t)(x + 1) * kMcsLanes + y]]; break;
@@ -120,19 +90,10 @@ __global__ __launch_bounds__(kMcsBlock) void mcs_values_kernel(McsWitnessArgs a)
 #endif
 }
 
-__global__ __launch_bounds__(kMcsBlock) void mcs_gather_kernel(McsWitnessArgs a) {
+__global__ __launch_bounds__(kCsBlock) void mcs_divrem_kernel(const Fp* __restrict__ values, uint32_t m, uint32_t count, Fp* __restrict__ quot,
+                                                              uint32_t* __restrict__ rem) {
 #if defined(__HIP_DEVICE_COMPILE__)
-    const uint32_t p = blockIdx.x * kMcsBlock + threadIdx.x, match = blockIdx.y, total = kMcsWires * a.n;
-    const Fp* values = a.values + (size_t)match * a.num_vars;
-    if (p < total) a.witness[(size_t)match * total + p] = values[a.wiring[p]];
-    else if (p - total < a.pi_count) a.pi[(size_t)match * a.pi_count + (p - total)] = values[a.pi_vars[p - total]];
-#endif
-}
-
-__global__ __launch_bounds__(kMcsBlock) void mcs_divrem_kernel(const Fp* __restrict__ values, uint32_t m, uint32_t count, Fp* __restrict__ quot,
-                                                                uint32_t* __restrict__ rem) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    const uint32_t i = blockIdx.x * kMcsBlock + threadIdx.x;
+    const uint32_t i = blockIdx.x * kCsBlock + threadIdx.x;
     if (i >= count) return;
     Fp q;
     rem[i] = mcs_divrem(values[i], m, &q);
@@ -140,21 +101,16 @@ __global__ __launch_bounds__(kMcsBlock) void mcs_divrem_kernel(const Fp* __restr
 #endif
 }
 
-int mcs_tables_run(Ctx& c, const McsTableArgs& a) {
-    UZK_LAUNCH(c, "mcs_tables", mcs_tables_kernel, dim3(mcs_grid(a.n)), dim3(kMcsBlock), 0, c.stream, a);
-    return UZK_OK;
-}
-
 int mcs_witness_run(Ctx& c, const McsWitnessArgs& a, uint32_t batch) {
-    const dim3 block(kMcsBlock);
+    const dim3 block(kCsBlock);
     UZK_LAUNCH(c, "mcs_steps", mcs_steps_kernel, dim3(batch), dim3(kMcsLanes), 0, c.stream, a);
-    UZK_LAUNCH(c, "mcs_values", mcs_values_kernel, dim3(mcs_grid(a.num_vars), batch), block, 0, c.stream, a);
-    UZK_LAUNCH(c, "mcs_gather", mcs_gather_kernel, dim3(mcs_grid((size_t)kMcsWires * a.n + a.pi_count), batch), block, 0, c.stream, a);
+    UZK_LAUNCH(c, "mcs_values", mcs_values_kernel, dim3(cs_grid(a.num_vars), batch), block, 0, c.stream, a);
+    UZK_TRY(cs_gather_run(c, {a.n, a.num_vars, a.pi_count, a.wiring, a.pi_vars, a.values, a.witness, a.pi}, batch));
     return UZK_OK;
 }
 
 int mcs_divrem_run(Ctx& c, const Fp* d_values, uint32_t m, uint32_t count, Fp* d_quot, uint32_t* d_rem) {
-    UZK_LAUNCH(c, "mcs_divrem", mcs_divrem_kernel, dim3(mcs_grid(count)), dim3(kMcsBlock), 0, c.stream, d_values, m, count, d_quot, d_rem);
+    UZK_LAUNCH(c, "mcs_divrem", mcs_divrem_kernel, dim3(cs_grid(count)), dim3(kCsBlock), 0, c.stream, d_values, m, count, d_quot, d_rem);
     return UZK_OK;
 }
 

@@ -2,18 +2,16 @@
 // in a TurboCS once the values are taken out of it.  The layout half is plain C++17 with no HIP in it (matchcs_layout.cpp builds with
 // g++); the device half (matchcs.hip) turns a layout and the Anemoi traces of a batch of matches into evaluation vectors and witnesses.
 #pragma once
-#include <cstddef>
-#include <cstdint>
-#include <vector>
+#include "cs_layout.hpp"
 
 namespace uzk {
 
-constexpr uint32_t kMcsMinPlayers = 3, kMcsMaxPlayers = 64, kMcsWires = 5, kMcsSelectors = 9, kMcsRounds = 14, kMcsTraceElems = 64;
-// The evaluation vectors of a circuit in slot order, without l1 and coset_quotient: q (9), s (5), qb, q_prk (4)
-constexpr uint32_t kMcsTables = 19, kMcsTabS = 9, kMcsTabQb = 14, kMcsTabPrk = 15;
+constexpr uint32_t kMcsMinPlayers = 3, kMcsMaxPlayers = 64, kMcsRounds = 14, kMcsTraceElems = 64;
+constexpr uint32_t kMcsWires = kCsWires, kMcsSelectors = kCsSelectors;     // the circuit's own names for the common shape
+constexpr uint32_t kMcsTables = kCsCommonTables;                 // the evaluation vectors of a circuit: the common ones and no more
 
 // How a variable's value follows from a match (inputs, seed, random number), its two Anemoi traces and the remainders
-// rem_i = stream output i - 1 mod (i + 1): kind << 28 | a << 16 | b << 8 | c.  The running output vector before step i is the inputs
+// rem_i = stream output i - 1 mod (i + 1) (cs_def).  The running output vector before step i is the inputs
 // under an index vector idx_i (idx_1 = the identity; step i exchanges positions i and rem_i):
 //   kMcsConst        the integer a (0 .. players - 1)
 //   kMcsInput        input a
@@ -28,22 +26,17 @@ constexpr uint32_t kMcsTables = 19, kMcsTabS = 9, kMcsTabQb = 14, kMcsTabPrk = 1
 //   kMcsProdSum      the first b products of step a: rem_a < b ? input[idx_a[rem_a]] : 0
 //   kMcsSelect       step a, position b < a, after the step: input[idx_{a+1}[b]]
 enum McsKind : uint32_t {
-    kMcsConst = 0, kMcsInput, kMcsSeed, kMcsRandom, kMcsCommit, kMcsHashTrace, kMcsStreamTrace, kMcsStreamOut, kMcsQuot, kMcsRem, kMcsBit,
+    kMcsConst = kCsConst, kMcsInput, kMcsSeed, kMcsRandom, kMcsCommit, kMcsHashTrace, kMcsStreamTrace, kMcsStreamOut, kMcsQuot, kMcsRem, kMcsBit,
     kMcsBitSum, kMcsProduct, kMcsProdSum, kMcsSelect
 };
-constexpr uint32_t mcs_def(uint32_t kind, uint32_t a, uint32_t b = 0, uint32_t c = 0) { return kind << 28 | a << 16 | b << 8 | c; }
 
-struct MatchLayout {
-    uint32_t players = 0, size = 0, n = 0, num_vars = 0;           // size: gates before the pad; n: after it
+// CsLayout: the selector values are 0, +-1, 1 5 26 and their doubles, i + 1 <= 64, the constants; qb marks the running sums of the
+// bits; pi: 2 players + 2, inputs, outputs, random number, commitment; block_rows: the first row of every permutation block, the
+// hash's, then the cipher's
+struct MatchLayout : CsLayout {
+    uint32_t players = 0;
     uint32_t stream_perms = 0;                                     // permutations of the stream cipher: 1, or ceil((players - 1) / 3)
-    std::vector<uint32_t> wiring;                                  // [5][n] variable indices
-    std::vector<uint32_t> perm;                                    // [5][n]: compute_permutation over the wire-major flattening
-    std::vector<int16_t> sel;                                      // [9][n]: 0, +-1, 1 5 26 and their doubles, i + 1 <= 64, the constants
-    std::vector<uint8_t> qb;                                       // [n]: 1 on the boolean rows (the running sums of the bits)
     std::vector<uint8_t> prk_row;                                  // [n]: 0, or 1 + round on row a + round of a permutation block
-    std::vector<uint32_t> defs;                                    // [num_vars]
-    std::vector<uint32_t> pi_rows, pi_vars;                        // 2 players + 2: inputs, outputs, random number, commitment
-    std::vector<uint32_t> block_rows;                              // the first row of every permutation block: the hash's, then the cipher's
 };
 
 // gates before the pad: players + 15 + (14 P + players - 1 + [P > 1]) + sum_{i=1}^{players-1} (3 i + 4 + 2 ceil((i + 1) / 3)) + 2 players + 2

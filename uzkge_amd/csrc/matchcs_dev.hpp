@@ -1,6 +1,6 @@
 // What matchcs.cpp (the C ABI of the matchmaking circuit) and matchcs.hip (its kernels) share.
 #pragma once
-#include "ctx.hpp"
+#include "cs_common.hpp"
 #include "matchcs.hpp"
 
 namespace uzk {
@@ -8,17 +8,6 @@ namespace uzk {
 constexpr uint32_t kMcsLanes = 64;     // the lanes of the step kernel's one wave: lane j holds position j of the running output vector
 
 // every pointer a device address
-struct McsTableArgs {
-    uint32_t n;
-    const int16_t* sel;                // [9][n]
-    const uint8_t* qb;                 // [n]
-    const uint8_t* prk_row;            // [n]
-    const uint32_t* perm;              // [5][n]
-    const Fp* group;                   // [n]: omega^i
-    const Fp* prk;                     // [14][4]: the round keys after the linear layer
-    Fp k[kMcsWires];
-    Fp* out;                           // [kMcsTables][n]
-};
 struct McsWitnessArgs {
     uint32_t players, n, num_vars, pi_count, stream_perms;
     const uint32_t *defs, *wiring, *pi_vars;
@@ -31,9 +20,7 @@ struct McsWitnessArgs {
     Fp *values, *witness, *pi;         // [batch][num_vars], [batch][5][n], [batch][pi_count]
 };
 
-// all 19 evaluation vectors into a.out
-int mcs_tables_run(Ctx& c, const McsTableArgs& a);
-// steps (division, bits, the chain of exchanges), values, gather: three launches over traces that are already on the device
+// steps (division, bits, the chain of exchanges), values, gather (cs_gather): three launches over traces that are already on the device
 int mcs_witness_run(Ctx& c, const McsWitnessArgs& a, uint32_t batch);
 // the step kernel's own division on `count` plain integers (device arrays): quot plain, rem words
 int mcs_divrem_run(Ctx& c, const Fp* d_values, uint32_t m, uint32_t count, Fp* d_quot, uint32_t* d_rem);

@@ -5,86 +5,42 @@
 #include <cstring>
 
 #include "host_math.hpp"
-#include "handles.hpp"
-#include "prover.hpp"
 #include "shufflecs_dev.hpp"
 
 using namespace uzk;
-#define API_LOCK std::lock_guard<std::mutex> _lk(ctx_mutex())
 
 namespace {
 
-struct ShuffleCs {
+struct ShuffleCs : CsResident {
     ShuffleLayout host;
-    std::shared_ptr<DevBlock> blk;                                 // the device copies below, carved out of one block
-    const uint32_t *d_wiring = nullptr, *d_defs = nullptr, *d_pi_vars = nullptr;
-    const int8_t* d_sel = nullptr;
-    const uint8_t* d_qb = nullptr;
     const uint16_t* d_block = nullptr;
 };
 
-std::shared_ptr<ShuffleCs> shuffle_of(const std::shared_ptr<Circuit>& cir) {
-    return cir && cir->ext_kind == kExtShuffle ? std::static_pointer_cast<ShuffleCs>(cir->ext) : nullptr;      // the tag says whose ext is
-}
-
-struct Whole {                                                     // a block of exactly the carver's total, as the carver sees a buffer
-    void* p;
-    int reserve(size_t) { return UZK_OK; }
-};
-
-template <class T>
-int put(Ctx& c, T* dst, const std::vector<T>& src) {
-    UZK_HIP(hipMemcpyAsync(dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice, c.stream));
-    return UZK_OK;
-}
+std::shared_ptr<ShuffleCs> shuffle_of(const std::shared_ptr<Circuit>& cir) { return cs_ext<ShuffleCs>(cir, kExtShuffle); }
 
 int make_resident(Ctx& c, ShuffleCs& s) {
     const ShuffleLayout& L = s.host;
-    WsCarver cv;
-    const auto a_w = cv.array<uint32_t>(L.wiring.size()), a_d = cv.array<uint32_t>(L.defs.size()), a_p = cv.array<uint32_t>(L.pi_vars.size());
-    const auto a_s = cv.array<int8_t>(L.sel.size());
-    const auto a_q = cv.array<uint8_t>(L.qb.size());
-    const auto a_b = cv.array<uint16_t>(L.block.size());
-    UZK_TRY(dev_block(cv.total(), &s.blk));
-    Whole whole{s.blk->p};
-    UZK_TRY(cv.reserve(whole));
-    UZK_TRY(put(c, cv(a_w), L.wiring)); UZK_TRY(put(c, cv(a_d), L.defs)); UZK_TRY(put(c, cv(a_p), L.pi_vars));
-    UZK_TRY(put(c, cv(a_s), L.sel)); UZK_TRY(put(c, cv(a_q), L.qb)); UZK_TRY(put(c, cv(a_b), L.block));
-    UZK_HIP(hipStreamSynchronize(c.stream));
-    s.d_wiring = cv(a_w); s.d_defs = cv(a_d); s.d_pi_vars = cv(a_p); s.d_sel = cv(a_s); s.d_qb = cv(a_q); s.d_block = cv(a_b);
-    return UZK_OK;
+    WsArray<uint16_t> a_b;
+    return cs_make_resident(c, L, &s, [&](WsCarver& cv) { a_b = cv.array<uint16_t>(L.block.size()); },
+                            [&](const WsCarver& cv) { s.d_block = cv(a_b); return cs_put(c, cv(a_b), L.block); });
 }
 
-ShcsTableArgs table_args(const Circuit& cir, const ShuffleCs& s, Fp* d_out) {
-    ShcsTableArgs a = {};
-    a.n = cir.n; a.sel = s.d_sel; a.qb = s.d_qb; a.block = s.d_block; a.perm = cir.d_perm; a.group = cir.d_group; a.out = d_out;
-    for (uint32_t w = 0; w < kShcsWires; ++w) a.k[w] = cir.k[w];
-    return a;
-}
-
-int circuit_here(const Circuit& cir, const char* who) {
-    UZK_TRY(require_ready());
-    if (ctx().device != cir.device) { set_error("%s: the circuit lives on device %d, the calling context on device %d", who, cir.device, ctx().device); return UZK_ERR_PARAMETER; }
-    return UZK_OK;
-}
-
-// the tables of a fresh circuit: one pass of the table kernels, then four refreshes (slot 14, l1, and slot 20, coset_quotient, are
-// the circuit's own); cms: the 32 key commitments in the verifier key's order, or null
+// the tables of a fresh circuit: one pass of the table kernels, then four refreshes; cms: the 32 key commitments in the verifier
+// key's order, or null
 int install_tables(Ctx& c, Circuit& cir, const ShuffleCs& s, Jac* cms) {
     const uint32_t n = cir.n;
     const Fp* d_gen = nullptr;
     std::shared_ptr<DevBlock> evals;
-    UZK_TRY(dev_block((size_t)kShcsTables * n * sizeof(Fp), &evals));
-    Fp* d = static_cast<Fp*>(evals->p);
-    UZK_TRY(remark_device_tables(c, 0, nullptr, &d_gen));          // no key yet: the public-key columns start as the generator's
-    UZK_TRY(shcs_tables_run(c, table_args(cir, s, d), d_gen, d_gen));
     std::vector<Jac> cm(kShcsTables);
-    UZK_TRY(circuit_refresh_device(c, cir, UZK_CS_Q, 14, d, cm.data()));
-    UZK_TRY(circuit_refresh_device(c, cir, UZK_CS_QB, 5, d + (size_t)kShcsTabQb * n, cm.data() + kShcsTabQb));
+    UZK_TRY(cs_install_common(c, cir, kShcsTables, [&](Fp* d) {
+        UZK_TRY(remark_device_tables(c, 0, nullptr, &d_gen));      // no key yet: the public-key columns start as the generator's
+        return shcs_tables_run(c, cs_table_args(cir, s, nullptr, nullptr, d), s.d_block, d_gen, d_gen);
+    }, &evals, cm.data()));
+    const Fp* d = static_cast<const Fp*>(evals->p);
     UZK_TRY(circuit_refresh_device(c, cir, UZK_CS_QPK, 12, d + (size_t)kShcsTabPk * n, cm.data() + kShcsTabPk));
     UZK_TRY(circuit_refresh_device(c, cir, UZK_CS_QG, 13, d + (size_t)kShcsTabGen * n, cm.data() + kShcsTabGen));
     if (cms) {
-        std::memcpy(cms, cm.data(), 19 * sizeof(Jac));                                         // cm_q, cm_s, cm_qb, cm_prk
+        std::memcpy(cms, cm.data(), kCsCommonTables * sizeof(Jac));                            // cm_q, cm_s, cm_qb, cm_prk
         cms[19] = cm[kShcsTabEcc];
         std::memcpy(cms + 20, cm.data() + kShcsTabGen, 12 * sizeof(Jac));
     }
@@ -100,11 +56,7 @@ namespace uzk {
 int shcs_info(uint32_t cards, uint32_t* size_out, uint32_t* n_out, uint32_t* num_vars_out, uint32_t* pi_count_out, uint32_t* pi_rows_out) {
     ShuffleLayout L;
     if (!shuffle_layout_build(cards, &L)) { set_error("uzk_shuffle_cs_info: %u cards (1 .. %d)", cards, UZK_SHUFFLE_CS_MAX_CARDS); return UZK_ERR_PARAMETER; }
-    if (size_out) *size_out = L.size;
-    if (n_out) *n_out = L.n;
-    if (num_vars_out) *num_vars_out = L.num_vars;
-    if (pi_count_out) *pi_count_out = (uint32_t)L.pi_rows.size();
-    if (pi_rows_out) std::memcpy(pi_rows_out, L.pi_rows.data(), L.pi_rows.size() * sizeof(uint32_t));
+    cs_info(L, size_out, n_out, num_vars_out, pi_count_out, pi_rows_out);
     return UZK_OK;
 }
 
@@ -112,33 +64,14 @@ int shcs_circuit_create(const uzk_shuffle_circuit_desc* desc, uint64_t* circuit_
     if (!desc || !circuit_out) { set_error("uzk_shuffle_circuit_create: null pointer"); return UZK_ERR_PARAMETER; }
     auto s = std::make_shared<ShuffleCs>();
     if (!shuffle_layout_build(desc->cards, &s->host)) { set_error("uzk_shuffle_circuit_create: %u cards (1 .. %d)", desc->cards, UZK_SHUFFLE_CS_MAX_CARDS); return UZK_ERR_PARAMETER; }
-    const uint32_t n = s->host.n;
-    // an ordinary circuit over the layout's permutation with empty tables; l1 = the iFFT of (n, 0, ..): n ones
-    uzk_circuit_desc cd = {};
-    cd.n = n; cd.shuffle = 1; cd.precompute = desc->precompute;
-    cd.lagrange_bases = desc->lagrange_bases; cd.blind_bases = desc->blind_bases;
-    cd.permutation = s->host.perm.data();
-    std::memcpy(cd.k, desc->k, sizeof cd.k);
-    std::memcpy(cd.group_gen, desc->group_gen, sizeof cd.group_gen);
-    const Fp one = Fr::one();
-    std::memcpy(cd.edwards_a, &one, sizeof one);                   // Baby Jubjub: a = 1; no anemoi gates: generator and inverse zero
-    std::vector<Fp> l1(n, one);
-    cd.polys[UZK_CS_L1] = reinterpret_cast<const uint64_t*>(l1.data());
-    cd.poly_lens[UZK_CS_L1] = n;
-    uint64_t h = 0;
-    UZK_TRY(uzk_circuit_create(&cd, &h));
-    int rc;
-    {
-        API_LOCK;
-        auto cir = find_circuit(h);
-        Ctx& c = ctx();
-        rc = make_resident(c, *s);
-        if (rc == UZK_OK) rc = install_tables(c, *cir, *s, reinterpret_cast<Jac*>(commitments_out));
-        if (rc == UZK_OK) { cir->ext = s; cir->ext_kind = kExtShuffle; }
-    }
-    if (rc != UZK_OK) { (void)uzk_circuit_release(h); return rc; }
-    *circuit_out = h;
-    return UZK_OK;
+    return cs_circuit_create(cs_desc_of(*desc), s->host, [](uzk_circuit_desc& cd) {
+        const Fp one = Fr::one();
+        cd.shuffle = 1;
+        std::memcpy(cd.edwards_a, &one, sizeof one);               // Baby Jubjub: a = 1; no anemoi gates: generator and inverse zero
+    }, kExtShuffle, s, [&](Ctx& c, Circuit& cir) {
+        UZK_TRY(make_resident(c, *s));
+        return install_tables(c, cir, *s, reinterpret_cast<Jac*>(commitments_out));
+    }, circuit_out);
 }
 
 int shcs_circuit_set_key(uint64_t circuit, uint64_t remark_key, uzk_g1_jac* commitments_out) {
@@ -147,7 +80,7 @@ int shcs_circuit_set_key(uint64_t circuit, uint64_t remark_key, uzk_g1_jac* comm
     auto s = shuffle_of(cir);
     if (!s) { set_error("uzk_shuffle_circuit_set_key: %llu is no circuit of uzk_shuffle_circuit_create", (unsigned long long)circuit); return UZK_ERR_PARAMETER; }
     if (!remark_key_known(remark_key, nullptr)) { set_error("uzk_shuffle_circuit_set_key: unknown remask key %llu", (unsigned long long)remark_key); return UZK_ERR_PARAMETER; }
-    UZK_TRY(circuit_here(*cir, "uzk_shuffle_circuit_set_key"));
+    UZK_TRY(cs_circuit_here(*cir, "uzk_shuffle_circuit_set_key"));
     Ctx& c = ctx();
     const Fp* d_pk = nullptr;
     UZK_TRY(remark_device_tables(c, remark_key, &d_pk, nullptr));
@@ -186,7 +119,7 @@ int shcs_witness_batch(uint64_t circuit, uint64_t remark_key, const uint64_t* e1
             perm[(size_t)b * N + i] = p;
         }
     if (!remark_key_known(remark_key, nullptr)) { set_error("%s: unknown remask key %llu", who, (unsigned long long)remark_key); return UZK_ERR_PARAMETER; }
-    UZK_TRY(circuit_here(*cir, who));
+    UZK_TRY(cs_circuit_here(*cir, who));
     Ctx& c = ctx();
     const size_t pt_words = 2 * (size_t)total;
     WsCarver cv;
@@ -222,17 +155,16 @@ int shcs_test_tables(uint64_t circuit, uint64_t remark_key, uint32_t* wiring_out
     auto s = shuffle_of(cir);
     if (!s) { set_error("uzk_test_shuffle_cs_tables: %llu is no circuit of uzk_shuffle_circuit_create", (unsigned long long)circuit); return UZK_ERR_PARAMETER; }
     if (remark_key && !remark_key_known(remark_key, nullptr)) { set_error("uzk_test_shuffle_cs_tables: unknown remask key %llu", (unsigned long long)remark_key); return UZK_ERR_PARAMETER; }
-    UZK_TRY(circuit_here(*cir, "uzk_test_shuffle_cs_tables"));
+    UZK_TRY(cs_circuit_here(*cir, "uzk_test_shuffle_cs_tables"));
     Ctx& c = ctx();
-    const size_t n = cir->n, words = kShcsWires * n * sizeof(uint32_t);
-    if (wiring_out) UZK_HIP(hipMemcpyAsync(wiring_out, s->d_wiring, words, hipMemcpyDeviceToHost, c.stream));
-    if (perm_out) UZK_HIP(hipMemcpyAsync(perm_out, cir->d_perm, words, hipMemcpyDeviceToHost, c.stream));
+    const size_t n = cir->n;
+    UZK_TRY(cs_test_tables_common(c, *cir, *s, wiring_out, perm_out));
     if (evals_out) {
         const Fp *d_gen = nullptr, *d_pk = nullptr;
         UZK_TRY(remark_device_tables(c, 0, nullptr, &d_gen));
         if (remark_key) UZK_TRY(remark_device_tables(c, remark_key, &d_pk, nullptr));
         UZK_TRY(c.shuffle_ws.reserve(kShcsTables * n * sizeof(Fp)));
-        UZK_TRY(shcs_tables_run(c, table_args(*cir, *s, c.shuffle_ws.as<Fp>()), d_gen, remark_key ? d_pk : d_gen));
+        UZK_TRY(shcs_tables_run(c, cs_table_args(*cir, *s, nullptr, nullptr, c.shuffle_ws.as<Fp>()), s->d_block, d_gen, remark_key ? d_pk : d_gen));
         UZK_HIP(hipMemcpyAsync(evals_out, c.shuffle_ws.p, kShcsTables * n * sizeof(Fp), hipMemcpyDeviceToHost, c.stream));
     }
     UZK_HIP(hipStreamSynchronize(c.stream));

@@ -1,21 +1,11 @@
 // What shufflecs.cpp (the C ABI of the shuffle circuit) and shufflecs.hip (its kernels) share.
 #pragma once
-#include "ctx.hpp"
+#include "cs_common.hpp"
 #include "shufflecs.hpp"
 
 namespace uzk {
 
 // every pointer a device address
-struct ShcsTableArgs {
-    uint32_t n;
-    const int8_t* sel;                 // [9][n]
-    const uint8_t* qb;                 // [n]
-    const uint16_t* block;             // [n]
-    const uint32_t* perm;              // [5][n]
-    const Fp* group;                   // [n]: omega^i
-    Fp k[kShcsWires];
-    Fp* out;                           // [kShcsTables][n]
-};
 struct ShcsWitnessArgs {
     uint32_t cards, n, num_vars, pi_count;
     const uint32_t *defs, *wiring, *pi_vars;
@@ -27,10 +17,11 @@ struct ShcsWitnessArgs {
     Fp *values, *witness, *wsel, *pi;  // [batch][num_vars], [batch][5][n], [batch][3][n], [batch][pi_count]
 };
 
-// all 44 evaluation vectors into a.out: the fixed ones, T_pk's columns, T_G's columns
-int shcs_tables_run(Ctx& c, const ShcsTableArgs& a, const Fp* d_gen, const Fp* d_pk);
+// all 44 evaluation vectors into a.out: the common ones, T_pk's columns, T_G's columns, q_ecc
+int shcs_tables_run(Ctx& c, const CsTableArgs& a, const uint16_t* d_block, const Fp* d_gen, const Fp* d_pk);
 // the 12 columns of one table: d_out [12][n]
 int shcs_key_run(Ctx& c, const uint16_t* d_block, const Fp* d_table, Fp* d_out, uint32_t n);
+// values, gather (cs_gather), wire selectors: three launches over a remask that is already on the device
 int shcs_witness_run(Ctx& c, const ShcsWitnessArgs& a, uint32_t batch);
 
 // shufflecs.cpp: what api.cpp's uzk_shuffle_* and uzk_test_shuffle_cs_tables forward to, argument for argument
