@@ -977,6 +977,47 @@ int uzk_match_circuit_create(const uzk_match_circuit_desc* desc, uint64_t* circu
 int uzk_match_witness_batch(uint64_t circuit, const uint64_t* inputs_mont, const uint64_t* seeds_mont, const uint64_t* randoms_mont, uint32_t players,
                             uint32_t batch, void* d_witness, uint64_t* pi_values_out, uint64_t* outputs_out, uint64_t* commitments_out);
 
+/* ---- the reveal circuit: the R1CS of a Groth16 reveal proof and its witness, on the device ----------------------------------------------
+ * RevealCircuit (shuffle/src/reveal_with_snark.rs) over ark-r1cs-std 0.4's twisted Edwards gadget: g.scalar_mul_le(sk) == pk and
+ * h.scalar_mul_le(sk) == reveal for the constant generator g, the inputs h = masked.e1, reveal, pk and the 256 little-endian Boolean
+ * witnesses of sk -- the circuit behind reveal_card_with_snark (shuffle/src/sdk.rs:288-303) and RevealVerifier.sol.
+ *   variables    4869: the one; h.x h.y reveal.x reveal.y pk.x pk.y (l = 7, the statement of uzk_g16_verify_batch and
+ *                uzk_cp_reveal_verify_batch); x^2, y^2 of the three points; the 256 bits; 255 x 5 witnesses of the fixed-base chain
+ *                (v0 v1, tmp.x, tmp.y, res.x, res.y; its iteration 0 is linear); 10 + 255 x 13 of the variable-base chain (u, v0, v1, v0 v1,
+ *                tmp, res, then the doubling's xy, x^2, y^2, x3, y3)
+ *   constraints  4869 (9 curve checks, 256 bit rows, 255 x 5 + 2, 10 + 255 x 13 + 2); the domain has 8192 points
+ * tests/test_reveal_cs_ref_host.py holds the layout to the proving key the reference ships: a proof made over these matrices is
+ * accepted under that key's verifying key.
+ *   sk           ONE 256-bit integer for the call (four little-endian words, NOT Montgomery; the reference's secrets are below the
+ *                subgroup order): all 256 bits enter the circuit as they are
+ *   e1_mont      m points, x then y, canonical Montgomery words: any point of the curve (the subgroup is the caller's business, as in
+ *                the reference)
+ * UZK_ERR_PARAMETER before any launch: a handle not of uzk_reveal_circuit_create, m outside 1 .. UZK_REVEAL_CS_MAX_BATCH, a null pointer,
+ * a coordinate not below q, an e1 off the curve. */
+#define UZK_REVEAL_CS_VARS 4869
+#define UZK_REVEAL_CS_INPUTS 7
+#define UZK_REVEAL_CS_MAX_BATCH 1024
+/* Host only.  Every output optional (NULL); nnz_out: the non-zero counts of A, B, C. */
+int uzk_reveal_cs_info(uint32_t* n_vars_out, uint32_t* n_inputs_out, uint32_t* n_constraints_out, uint64_t* domain_out, uint64_t nnz_out[3]);
+/* Host only.  Fills the caller's CSR buffers (sizes from uzk_reveal_cs_info: row_ptr[k] n_constraints + 1 entries, col[k] and val[k]
+ * nnz[k]; val: 4 Montgomery words per entry; columns ascend within a row). */
+int uzk_reveal_cs_matrices(uint64_t* const row_ptr[3], uint32_t* const col[3], uint64_t* const val[3]);
+/* desc: a uzk_g16_key_desc whose row_ptr, col and val are NULL (n_constraints 0 or the circuit's).  A key whose n_vars, n_inputs,
+ * l_query_len or h_query_len are not the layout's is UZK_ERR_PARAMETER before the device is touched.  Creates the resident Groth16 key
+ * from the key's points and the circuit's own matrices, and uploads the 256 constant multiples 2^i G. */
+int uzk_reveal_circuit_create(const uzk_g16_key_desc* desc, uint64_t* circuit_out);
+/* Releases the circuit and the key it holds.  The caller makes sure no context still works with either. */
+int uzk_reveal_circuit_release(uint64_t circuit);
+/* The inner key handle, for uzk_g16_key_info, uzk_g16_h_device and uzk_g16_prove_batch[_device]; it lives as long as the circuit. */
+int uzk_reveal_circuit_key(uint64_t circuit, uint64_t* key_out);
+/* d_z (device): m full assignments of UZK_REVEAL_CS_VARS elements, the layout uzk_g16_prove_batch_device reads; statements_out (host):
+ * m x 6 elements e1.x e1.y reveal.x reveal.y pk.x pk.y.  Complete when the call returns. */
+int uzk_reveal_witness_batch(uint64_t circuit, const uint64_t* sk, const uint64_t* e1_mont, uint32_t m, void* d_z, uint64_t* statements_out);
+/* uzk_reveal_witness_batch into a buffer of the context's, then uzk_g16_prove_batch_device over it: nothing leaves the device in
+ * between.  r_mont, s_mont: m blinding scalars each; proofs_out: m proofs as uzk_g16_prove_batch writes them. */
+int uzk_reveal_prove_snark_batch(uint64_t circuit, const uint64_t* sk, const uint64_t* e1_mont, const uint64_t* r_mont, const uint64_t* s_mont, uint32_t m,
+                                 uint64_t* statements_out, uzk_g16_proof* proofs_out);
+
 /* ---- Anemoi-Jive over BN254's scalar field: hashes, the stream cipher, their traces (uzkge/src/anemoi) -------------------------------
  * AnemoiJive254: 2 columns, 14 rounds, alpha = 5, g = 5, delta = 1 / g, the round keys of the Anemoi paper's pi rule; a sponge of rate
  * 3 (eval_variable_length_hash, eval_stream_cipher).  Batches run one lane per item, every item of a call with the same lengths.

@@ -839,6 +839,93 @@ impl Drop for MatchCircuit {
     }
 }
 
+/// n_vars, n_inputs, n_constraints, the domain and the non-zero counts of A, B, C of the reveal circuit (`uzk_reveal_cs_info`; host only).
+pub fn reveal_cs_info() -> Result<(u32, u32, u32, u64, [u64; 3]), Error> {
+    let (mut m, mut l, mut nc, mut n, mut nnz) = (0u32, 0u32, 0u32, 0u64, [0u64; 3]);
+    check(unsafe { uzk_reveal_cs_info(&mut m, &mut l, &mut nc, &mut n, nnz.as_mut_ptr()) })?;
+    Ok((m, l, nc, n, nnz))
+}
+
+/// The reveal circuit's matrices A, B, C in CSR: (row_ptr, col, val) each (`uzk_reveal_cs_matrices`; host only).
+pub fn reveal_cs_matrices() -> Result<Vec<(Vec<u64>, Vec<u32>, Vec<Limbs>)>, Error> {
+    let (_, _, nc, _, nnz) = reveal_cs_info()?;
+    let mut mats: Vec<(Vec<u64>, Vec<u32>, Vec<Limbs>)> =
+        nnz.iter().map(|k| (vec![0u64; nc as usize + 1], vec![0u32; *k as usize], vec![[0u64; 4]; *k as usize])).collect();
+    let row_ptr: Vec<*mut u64> = mats.iter_mut().map(|m| m.0.as_mut_ptr()).collect();
+    let col: Vec<*mut u32> = mats.iter_mut().map(|m| m.1.as_mut_ptr()).collect();
+    let val: Vec<*mut u64> = mats.iter_mut().map(|m| m.2.as_mut_ptr() as *mut u64).collect();
+    check(unsafe { uzk_reveal_cs_matrices(row_ptr.as_ptr(), col.as_ptr(), val.as_ptr()) })?;
+    Ok(mats)
+}
+
+/// The six public inputs of a reveal proof behind the leading one: e1.x e1.y reveal.x reveal.y pk.x pk.y.
+pub type RevealSnarkStatement = [Limbs; 6];
+
+/// The assignments of a batch of cards, resident on the device until dropped: what `uzk_g16_prove_batch_device` reads.
+pub struct RevealWitness {
+    pub d_z: *mut std::os::raw::c_void,
+    pub statements: Vec<RevealSnarkStatement>,
+}
+impl Drop for RevealWitness {
+    fn drop(&mut self) {
+        unsafe { uzk_dev_free(self.d_z) };
+    }
+}
+
+/// The reveal circuit joined to the points of a Groth16 proving key (`uzk_reveal_circuit_create`): its own matrices, the resident key
+/// and the constants of the fixed-base chain.  Released on drop, the inner key with it.
+pub struct RevealCircuit {
+    handle: u64,
+    key: u64,
+}
+impl RevealCircuit {
+    /// `desc`: the key's points, the matrix pointers null; everything it points to is read before this returns.
+    pub fn create(desc: &uzk_g16_key_desc) -> Result<Self, Error> {
+        let mut handle = 0u64;
+        check(unsafe { uzk_reveal_circuit_create(desc, &mut handle) })?;
+        let mut key = 0u64;
+        if let Err(e) = check(unsafe { uzk_reveal_circuit_key(handle, &mut key) }) {
+            unsafe { uzk_reveal_circuit_release(handle) };
+            return Err(e);
+        }
+        Ok(Self { handle, key })
+    }
+    pub fn handle(&self) -> u64 { self.handle }
+    /// the inner Groth16 key, for the `uzk_g16_*` entry points; it lives as long as the circuit
+    pub fn key(&self) -> u64 { self.key }
+    /// The assignments of `e1.len()` cards under one secret, left on the device (`uzk_reveal_witness_batch`).  `sk`: a plain integer.
+    pub fn witness_batch(&self, sk: &Limbs, e1: &[EdPoint]) -> Result<RevealWitness, Error> {
+        let m = e1.len();
+        if m == 0 || m > UZK_REVEAL_CS_MAX_BATCH as usize {
+            return Err(Error::Parameter);
+        }
+        let mut w = RevealWitness { d_z: std::ptr::null_mut(), statements: vec![[[0u64; 4]; 6]; m] };
+        check(unsafe { uzk_dev_alloc(32 * UZK_REVEAL_CS_VARS as usize * m, &mut w.d_z) })?;
+        check(unsafe { uzk_reveal_witness_batch(self.handle, sk.as_ptr(), e1.as_ptr() as *const u64, m as u32, w.d_z, w.statements.as_mut_ptr() as *mut u64) })?;
+        Ok(w)
+    }
+    /// Witness and proof of every card in one call (`uzk_reveal_prove_snark_batch`): `r`, `s` one pair of blinds per card
+    /// (Montgomery limbs), drawn by the caller.
+    pub fn prove_snark_batch(&self, sk: &Limbs, e1: &[EdPoint], r: &[Limbs], s: &[Limbs]) -> Result<(Vec<RevealSnarkStatement>, Vec<uzk_g16_proof>), Error> {
+        let m = e1.len();
+        if m == 0 || m > UZK_REVEAL_CS_MAX_BATCH as usize || r.len() != m || s.len() != m {
+            return Err(Error::Parameter);
+        }
+        let mut statements = vec![[[0u64; 4]; 6]; m];
+        let mut proofs = vec![uzk_g16_proof::default(); m];
+        check(unsafe {
+            uzk_reveal_prove_snark_batch(self.handle, sk.as_ptr(), e1.as_ptr() as *const u64, r.as_ptr() as *const u64, s.as_ptr() as *const u64, m as u32,
+                                         statements.as_mut_ptr() as *mut u64, proofs.as_mut_ptr())
+        })?;
+        Ok((statements, proofs))
+    }
+}
+impl Drop for RevealCircuit {
+    fn drop(&mut self) {
+        unsafe { uzk_reveal_circuit_release(self.handle) };
+    }
+}
+
 /// m cards masked under the joint key (`uzk_cp_mask_prove_batch`): (e1, e2, m proof blobs of UZK_CP_PROOF_BYTES).  `rs` and `omegas`
 /// are plain integers below the subgroup order, drawn by the caller.
 pub fn cp_mask_prove_batch(pk: &EdPoint, cards: &[EdPoint], rs: &[Limbs], omegas: &[Limbs]) -> Result<(Vec<EdPoint>, Vec<EdPoint>, Vec<u8>), Error> {

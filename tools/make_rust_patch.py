@@ -40,7 +40,11 @@ EDITS = {
          '#[cfg(feature = "gpu")]\npub use gpu_verifier::{\n    fold_reveals as gpu_fold_reveals, release_verifier_keys, reveal_proof_bytes, verify_batch as gpu_verify_batch, verify_reveals as gpu_verify_reveals,\n    RevealVerifyingKey,\n};\n'),
     ],
     "shuffle/Cargo.toml": [
-        ('no_vk = []\n', 'no_vk = []\n# MI355X backend (uzkge/gpu): device-resident prover and the public-key refresh as one device call\ngpu = ["uzkge/gpu"]\n'),
+        ('uzkge = { workspace = true, features = ["shuffle"] }\n',
+         'uzkge = { workspace = true, features = ["shuffle"] }\nuzkge-gpu-sys = { path = "../uzkge-gpu-sys", optional = true }\n'),
+        ('no_vk = []\n', 'no_vk = []\n# MI355X backend (uzkge/gpu): device-resident prover and the public-key refresh as one device call\ngpu = ["uzkge/gpu"]\n'
+         '# the snark reveal of a deck on the device: src/gpu_reveal_snark.rs (uzkge-glue/gpu_reveal_snark.rs), declared in src/lib.rs as\n'
+         '# `#[cfg(feature = "gpu-reveal-snark")] pub mod gpu_reveal_snark;`\ngpu-reveal-snark = ["gpu", "uzkge-gpu-sys"]\n'),
     ],
     "shuffle/src/gen_params/params.rs": [
         ('    let q_shuffle_public_key_evals = params.cs.compute_shuffle_public_key_selectors();\n',

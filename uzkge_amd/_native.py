@@ -151,6 +151,13 @@ PROTOTYPES = {
     "uzk_match_cs_info": (_I, [ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32), _P]),
     "uzk_match_circuit_create": (_I, [_P, ctypes.POINTER(_U64), _P]),
     "uzk_match_witness_batch": (_I, [_U64, _P, _P, _P, ctypes.c_uint32, ctypes.c_uint32, _P, _P, _P, _P]),
+    "uzk_reveal_cs_info": (_I, [ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(_U64), _P]),
+    "uzk_reveal_cs_matrices": (_I, [_P, _P, _P]),
+    "uzk_reveal_circuit_create": (_I, [_P, ctypes.POINTER(_U64)]),
+    "uzk_reveal_circuit_release": (_I, [_U64]),
+    "uzk_reveal_circuit_key": (_I, [_U64, ctypes.POINTER(_U64)]),
+    "uzk_reveal_witness_batch": (_I, [_U64, _P, _P, ctypes.c_uint32, _P, _P]),
+    "uzk_reveal_prove_snark_batch": (_I, [_U64, _P, _P, _P, _P, ctypes.c_uint32, _P, _P]),
     "uzk_cp_mask_prove_batch": (_I, [_P, _P, _P, _P, ctypes.c_uint32, _P, _P, _P]),
     "uzk_cp_mask_verify_batch": (_I, [_P, _P, _P, _P, _P, ctypes.c_uint32, _P, _P]),
     "uzk_anemoi_permute_batch": (_I, [_P, _SZ, _P]),
@@ -290,6 +297,9 @@ class ShuffleCircuitDesc(ctypes.Structure):
 MATCH_CS_MIN_PLAYERS = 3
 MATCH_CS_MAX_PLAYERS = 64
 MATCH_CS_MAX_BATCH = 1024
+REVEAL_CS_VARS = 4869
+REVEAL_CS_INPUTS = 7
+REVEAL_CS_MAX_BATCH = 1024
 MATCH_CS_KEY_COMMITMENTS = 19     # also uzk_test_match_cs_tables' evaluation vectors: q (9), s (5), qb, q_prk (4)
 
 

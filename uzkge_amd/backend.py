@@ -1120,6 +1120,76 @@ def match_divrem(values, m: int):
     return q, r
 
 
+def reveal_cs_info() -> dict:
+    """uzk_reveal_cs_info (host only): n_vars, n_inputs, n_constraints, domain and the non-zero counts of A, B, C"""
+    m, l, nc, n = ctypes.c_uint32(0), ctypes.c_uint32(0), ctypes.c_uint32(0), ctypes.c_uint64(0)
+    nnz = np.zeros(3, dtype=np.uint64)
+    check(lib.uzk_reveal_cs_info(ctypes.byref(m), ctypes.byref(l), ctypes.byref(nc), ctypes.byref(n), _ptr(nnz)))
+    return dict(n_vars=m.value, n_inputs=l.value, n_constraints=nc.value, domain=n.value, nnz=[int(v) for v in nnz])
+
+
+def reveal_cs_matrices():
+    """uzk_reveal_cs_matrices (host only): three (row_ptr uint64, col uint32, val [nnz, 4]) triples in CSR for A, B, C"""
+    info = reveal_cs_info()
+    mats = [(np.zeros(info["n_constraints"] + 1, dtype=np.uint64), np.zeros(k, dtype=np.uint32), np.zeros((k, 4), dtype=np.uint64)) for k in info["nnz"]]
+    arrs = [(ctypes.c_void_p * 3)(*[m[j].ctypes.data for m in mats]) for j in range(3)]
+    check(lib.uzk_reveal_cs_matrices(*arrs))
+    return mats
+
+
+class RevealCircuit:
+    """uzk_reveal_circuit_create: the reveal circuit's R1CS joined to the points of a Groth16 proving key (the arguments of
+    Groth16Key.describe without the matrices), resident on the device.  `key` is the inner Groth16Key: it lives as long as the circuit.
+    Use as a context manager, or release() it."""
+
+    def __init__(self, alpha_g1, beta_g1, delta_g1, beta_g2, delta_g2, a_query, b_g1_query, l_query, h_query, b_g2_query, n_vars: int = None,
+                 n_inputs: int = None):
+        a = np.ascontiguousarray(a_query, dtype=np.uint64).reshape(-1, 8)
+        d, keep = Groth16Key.describe(a.shape[0] if n_vars is None else n_vars, N.REVEAL_CS_INPUTS if n_inputs is None else n_inputs, 0, alpha_g1, beta_g1,
+                                      delta_g1, beta_g2, delta_g2, a, b_g1_query, l_query, h_query, b_g2_query, [])
+        h = ctypes.c_uint64(0)
+        check(lib.uzk_reveal_circuit_create(ctypes.byref(d), ctypes.byref(h)))
+        del keep
+        self.handle = h.value
+        k = ctypes.c_uint64(0)
+        check(lib.uzk_reveal_circuit_key(self.handle, ctypes.byref(k)))
+        self.key = Groth16Key(k.value)
+        self.n_vars = self.key.n_vars
+
+    def witness_batch(self, sk, e1, d_z: int) -> np.ndarray:
+        """uzk_reveal_witness_batch: sk [4] plain words, e1 [m, 8] wire points, d_z the device address of m x n_vars elements.
+        Returns the statements [m, 6, 4]."""
+        sk = np.ascontiguousarray(sk, dtype=np.uint64).reshape(4)
+        e1 = np.ascontiguousarray(e1, dtype=np.uint64).reshape(-1, 8)
+        st = np.zeros((max(e1.shape[0], 1), 6, 4), dtype=np.uint64)
+        check(lib.uzk_reveal_witness_batch(self.handle, _ptr(sk), _ptr(e1) if e1.size else None, e1.shape[0], ctypes.c_void_p(d_z), _ptr(st)))
+        return st[:e1.shape[0]]
+
+    def prove_snark_batch(self, sk, e1, r, s):
+        """uzk_reveal_prove_snark_batch: r, s [m, 4].  Returns (statements [m, 6, 4], proofs [m, 32]: A (8 words), B (16), C (8))."""
+        sk = np.ascontiguousarray(sk, dtype=np.uint64).reshape(4)
+        e1 = np.ascontiguousarray(e1, dtype=np.uint64).reshape(-1, 8)
+        r = np.ascontiguousarray(r, dtype=np.uint64).reshape(-1, 4)
+        s = np.ascontiguousarray(s, dtype=np.uint64).reshape(-1, 4)
+        m = e1.shape[0]
+        assert r.shape[0] == m and s.shape[0] == m, "one pair of blinds per card"
+        st, out = np.zeros((max(m, 1), 6, 4), dtype=np.uint64), np.zeros((max(m, 1), 32), dtype=np.uint64)
+        check(lib.uzk_reveal_prove_snark_batch(self.handle, _ptr(sk), _ptr(e1) if m else None, _ptr(r) if m else None, _ptr(s) if m else None, m, _ptr(st),
+                                               _ptr(out)))
+        return st[:m], out[:m]
+
+    def release(self) -> None:
+        if self.handle:
+            check(lib.uzk_reveal_circuit_release(self.handle))
+            self.handle, self.key.handle = 0, 0
+
+    def __enter__(self) -> "RevealCircuit":
+        return self
+
+    def __exit__(self, *exc) -> None:
+        self.release()
+
+
 class VerifierKey:
     """A verifier key resident on the device (uzk_vk_create).  Points are wire rows of 8 words ((0,0) = infinity), scalars rows of 4;
     `prefix`: the caller's transcript bytes in front of transcript_init_plonk."""

@@ -236,6 +236,8 @@ static void ctx_release(Ctx& c) {
     c.ed_ws.release();
     c.shuffle_ws.release();
     c.match_ws.release();
+    c.reveal_ws.release();
+    c.reveal_z.release();
     c.ed_gen.release();
     c.ed_gen_ready = false;
     c.pairing_ws.release();
@@ -328,6 +330,7 @@ int uzk_shutdown(void) try {
     prover_release_all();                  // circuits and provers own device memory (takes Shared::mu itself)
     vf_release_all();                      // verifier keys
     g2_release_all();                      // G2 bases
+    rcs_release_all();                     // reveal circuits, with the Groth16 keys they hold
     g16_release_all();                     // Groth16 proving keys
     g16v_release_all();                    // Groth16 verifying keys
     remark_release_all();                  // remask keys
@@ -1656,6 +1659,36 @@ int uzk_test_match_cs_tables(uint64_t circuit, uint32_t* wiring_out, uint32_t* p
 int uzk_test_match_divrem(const uint64_t* values, uint32_t m, uint32_t count, uint64_t* quot_out, uint32_t* rem_out) try {
     return mcs_test_divrem(values, m, count, quot_out, rem_out);
 } catch (...) { return uzk::on_exception("uzk_test_match_divrem"); }
+
+/* ---- the reveal circuit (revealcs.hip takes the context lock itself) ------------------------------- */
+int uzk_reveal_cs_info(uint32_t* n_vars_out, uint32_t* n_inputs_out, uint32_t* n_constraints_out, uint64_t* domain_out, uint64_t nnz_out[3]) try {
+    return rcs_info(n_vars_out, n_inputs_out, n_constraints_out, domain_out, nnz_out);
+} catch (...) { return uzk::on_exception("uzk_reveal_cs_info"); }
+
+int uzk_reveal_cs_matrices(uint64_t* const row_ptr[3], uint32_t* const col[3], uint64_t* const val[3]) try {
+    return rcs_matrices(row_ptr, col, val);
+} catch (...) { return uzk::on_exception("uzk_reveal_cs_matrices"); }
+
+int uzk_reveal_circuit_create(const uzk_g16_key_desc* desc, uint64_t* circuit_out) try {
+    return rcs_circuit_create(desc, circuit_out);
+} catch (...) { return uzk::on_exception("uzk_reveal_circuit_create"); }
+
+int uzk_reveal_circuit_release(uint64_t circuit) try {
+    return rcs_circuit_release(circuit);
+} catch (...) { return uzk::on_exception("uzk_reveal_circuit_release"); }
+
+int uzk_reveal_circuit_key(uint64_t circuit, uint64_t* key_out) try {
+    return rcs_circuit_key(circuit, key_out);
+} catch (...) { return uzk::on_exception("uzk_reveal_circuit_key"); }
+
+int uzk_reveal_witness_batch(uint64_t circuit, const uint64_t* sk, const uint64_t* e1_mont, uint32_t m, void* d_z, uint64_t* statements_out) try {
+    return rcs_witness_batch(circuit, sk, e1_mont, m, d_z, statements_out);
+} catch (...) { return uzk::on_exception("uzk_reveal_witness_batch"); }
+
+int uzk_reveal_prove_snark_batch(uint64_t circuit, const uint64_t* sk, const uint64_t* e1_mont, const uint64_t* r_mont, const uint64_t* s_mont, uint32_t m,
+                                 uint64_t* statements_out, uzk_g16_proof* proofs_out) try {
+    return rcs_prove_snark_batch(circuit, sk, e1_mont, r_mont, s_mont, m, statements_out, proofs_out);
+} catch (...) { return uzk::on_exception("uzk_reveal_prove_snark_batch"); }
 
 int uzk_cp_mask_prove_batch(const uint64_t* pk_mont, const uint64_t* cards_mont, const uint64_t* rs, const uint64_t* omegas, uint32_t m, uint64_t* e1_out,
                             uint64_t* e2_out, uint8_t* proofs_out) try {

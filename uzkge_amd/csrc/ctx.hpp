@@ -160,6 +160,10 @@ struct Ctx {
     DevBuf shuffle_ws;
     // matchcs.hip: one block carved into the arrays of a matchmaking witness (matches, the two Anemoi traces, steps, variable values)
     DevBuf match_ws;
+    // revealcs.hip: one block carved into the arrays of a reveal witness (cards, the chains' workspace, affine points), and the
+    // assignments of uzk_reveal_prove_snark_batch
+    DevBuf reveal_ws;
+    DevBuf reveal_z;
     int tune_verify_transcript = 0;   // which transcript kernel a fold runs: 1 one proof per lane; 0 / 2 a proof's state spread over a half wave (the default)
     // an entry of the process-wide SRS registry
     struct Srs {
@@ -362,6 +366,16 @@ int remark_key_create(Ctx& c, const EdAffine* pk, uint64_t* out);
 bool remark_key_known(uint64_t h, int* device);
 int remark_key_release(uint64_t h);
 void remark_release_all();
+// revealcs.hip: the reveal circuit (they take the context lock themselves)
+int rcs_info(uint32_t* n_vars, uint32_t* n_inputs, uint32_t* n_constraints, uint64_t* domain, uint64_t nnz_out[3]);
+int rcs_matrices(uint64_t* const row_ptr[3], uint32_t* const col[3], uint64_t* const val[3]);
+int rcs_circuit_create(const uzk_g16_key_desc* desc, uint64_t* circuit_out);
+int rcs_circuit_release(uint64_t circuit);
+void rcs_release_all();
+int rcs_circuit_key(uint64_t circuit, uint64_t* key_out);
+int rcs_witness_batch(uint64_t circuit, const uint64_t* sk, const uint64_t* e1_mont, uint32_t m, void* d_z, uint64_t* statements_out);
+int rcs_prove_snark_batch(uint64_t circuit, const uint64_t* sk, const uint64_t* e1_mont, const uint64_t* r_mont, const uint64_t* s_mont, uint32_t m,
+                          uint64_t* statements_out, uzk_g16_proof* proofs_out);
 int remark_tables_run(Ctx& c, uint64_t h, Fp* pk_tables_out, Fp* gen_tables_out);
 int remark_run(Ctx& c, uint64_t h, const EdAffine* e1, const EdAffine* e2, const uint8_t* digits, const uint32_t* slot, uint32_t n, EdAffine* e1_out,
                EdAffine* e2_out, Fp* trace_out);

@@ -109,6 +109,17 @@ def verify_reveal0(pks: Sequence[Point], masked_cards: Sequence[Tuple[Point, Poi
     return [int(v) for v in b.cp_reveal_verify_batch(st, b"".join(proofs), anemoi=True)]
 
 
+def reveal_with_snark(sk: int, masked_cards: Sequence[Tuple[Point, Point]], circuit, r: Sequence[int], s: Sequence[int]):
+    """One player's reveals with a Groth16 proof each (sdk.rs reveal_card_with_snark; RevealVerifier.sol): (reveal cards, proofs, pk).
+    circuit: a reveal_cs.RevealCircuit; r, s: one pair of fresh uniform integers below the scalar field's order per card, drawn by the
+    caller.  A proof is the 256-byte blob Groth16VerifierKey.verify_batch takes, with the public inputs e1.x e1.y reveal.x reveal.y
+    pk.x pk.y of its card."""
+    if len(r) != len(masked_cards) or len(s) != len(masked_cards):
+        raise ValueError("one pair of blinds per card")
+    statements, proofs = circuit.prove(sk, [c[0] for c in masked_cards], r, s)
+    return [(st[2], st[3]) for st in statements], proofs, (statements[0][4], statements[0][5])
+
+
 def unmask(masked_cards: Sequence[Tuple[Point, Point]], reveal_cards: Sequence[Sequence[Point]]) -> List[Point]:
     """card_j = e2_j minus every player's reveal of card j; reveal_cards[k][j] is player k's reveal of card j"""
     n = len(masked_cards)
