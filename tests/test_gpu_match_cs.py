@@ -39,13 +39,27 @@ def literal(gpu):
     cir.release()
 
 
-@pytest.mark.parametrize("players", [3, 5, 8, 50])
+@pytest.fixture(scope="module")
+def bound(gpu):
+    """the circuit of UZK_MATCH_CS_MAX_PLAYERS players: the only one of 16384 rows, with 22 permutation blocks"""
+    from uzkge_amd import _native as N
+    assert N.MATCH_CS_MAX_PLAYERS == mr.MAX_PLAYERS == 64
+    cir = make_circuit(N.MATCH_CS_MAX_PLAYERS)
+    yield cir
+    cir.release()
+
+
+ROWS = {50: 8192, 63: 8192, 64: 16384}               # 63 players are the most that fit 8192 rows (8054 gates; 64 have 8295)
+
+
+@pytest.mark.parametrize("players", [3, 5, 8, 50, 63, 64])
 def test_wiring_permutation_and_every_evaluation_vector(gpu, players):
     k = [1, 7, 13, 17, 23]
     cir = make_circuit(players, k)
     try:
         cs = built(players, zero=True)
         n = cs.size
+        assert n == ROWS.get(players, n)
         info = gpu.match_cs_info(players)
         assert (info["size"], info["n"], info["num_vars"], info["pi_count"]) == (cs.gates, n, cs.num_vars, 2 * players + 2)
         assert cir.info()[:3] == (n, 15, 19)                 # a circuit without the shuffle feature
@@ -100,7 +114,21 @@ def edge_match(players, kind):
     return [v] * players, v, v
 
 
-@pytest.mark.parametrize("players,batch", [(3, 65), (5, 7), (8, 7), (50, 3)])
+def check_witness(gpu, cir, ms, alone=0):
+    """every lane of one call against the restatement; the rows behind the pad; lane `alone` in a call of its own"""
+    got = run_witness(gpu, cir, ms)
+    for lane, m in enumerate(ms):
+        for name, g, w in zip(("witness", "pi", "outputs", "commitment"), got, expect(m)):
+            assert np.array_equal(g[lane], w), (lane, name)
+    ext = got[0].reshape(len(ms), 5, cir.n, 4)
+    assert not ext[:, :, cir.size:].any()                    # the rows behind the pad hold variable 0's value: zero
+    # alone, a match gives what it gives inside a batch
+    single = run_witness(gpu, cir, ms[alone:alone + 1])
+    assert all(np.array_equal(a[0], b[alone]) for a, b in zip(single, got))
+    return got
+
+
+@pytest.mark.parametrize("players,batch", [(3, 65), (5, 7), (8, 7), (50, 3), (63, 3)])
 def test_witness_inputs_outputs_and_commitments_are_the_restated_ones(gpu, literal, players, batch):
     ms = [match(players, 40 + i) for i in range(batch)]
     ms[1] = edge_match(players, "zero")
@@ -109,20 +137,41 @@ def test_witness_inputs_outputs_and_commitments_are_the_restated_ones(gpu, liter
         ms[3] = (list(range(players)), ms[3][1], ms[3][2])   # distinct small inputs: the outputs are a visible permutation
     cir = literal["cir"] if players == 50 else make_circuit(players)
     try:
-        got = run_witness(gpu, cir, ms)
-        for lane, m in enumerate(ms):
-            for name, g, w in zip(("witness", "pi", "outputs", "commitment"), got, expect(m)):
-                assert np.array_equal(g[lane], w), (lane, name)
-        ext = got[0].reshape(batch, 5, cir.n, 4)
-        assert not ext[:, :, cir.size:].any()                # the rows behind the pad hold variable 0's value: zero
+        got = check_witness(gpu, cir, ms)
         if batch > 3:
             assert sorted(oc.fr_to_ints(got[2][3])) == list(range(players))
-        # alone, a match gives what it gives inside a batch
-        alone = run_witness(gpu, cir, ms[:1])
-        assert all(np.array_equal(a[0], b[0]) for a, b in zip(alone, got))
     finally:
         if players != 50:
             cir.release()
+
+
+def test_witness_at_the_player_bound(gpu, bound):
+    """64 players: the whole wave divides and walks (divisors 2 .. 64, 63 steps, the last reads lane 63), the state table has 65
+    rows, the cipher runs 21 permutations and the circuit 16384 rows.  One call holds the all-zero match, the all-(r - 1) match, the
+    match of the inputs 0 .. 63 and a random one."""
+    players = mr.MAX_PLAYERS
+    assert (bound.players, bound.n, bound.size) == (players, 16384, 8295)
+    ms = [match(players, 60 + i) for i in range(4)]
+    ms[0], ms[1] = edge_match(players, "zero"), edge_match(players, "max")
+    ms[2] = (list(range(players)), ms[2][1], ms[2][2])
+    got = check_witness(gpu, bound, ms, alone=3)
+    outs = oc.fr_to_ints(got[2][2])
+    assert sorted(outs) == list(range(players)) and outs != list(range(players))
+    # what came out is the Fisher-Yates walk of all 63 steps on plain integers
+    stream, want = an.eval_stream_cipher([ms[2][1], ms[2][2]], players - 1), list(range(players))
+    for i in range(1, players):
+        r = stream[i - 1] % (i + 1)
+        want[i], want[r] = want[r], want[i]
+    assert outs == want
+
+
+def test_every_case_of_the_first_middle_and_last_steps_at_the_player_bound(gpu, bound):
+    """The matches of tests/test_match_cs_bounds.py, which that module shows to take the self-exchange rem_i == i, the exchange with
+    position 0 and an exchange in between at each of the steps 1, 31, 32, 62 and 63 of the walk at 64 players."""
+    from test_match_cs_bounds import directed_matches, wanted
+    ms, seen, _ = directed_matches()
+    assert seen == wanted()
+    check_witness(gpu, bound, ms, alone=len(ms) - 1)
 
 
 def plain_words(values):

@@ -67,7 +67,18 @@ def _verify(dk, blobs, publics, seed=0):
     return accepted, [int(s) for s in status]
 
 
-def check_batch(gpu, circuit, sk, pts):
+_mul = {}
+
+
+def ref_mul(sk, p):
+    """the integer multiple [sk] p on the whole curve: no reduction of sk, p of any order"""
+    if (sk, p) not in _mul:
+        _mul[(sk, p)] = ed.mul(sk, p)
+    return _mul[(sk, p)]
+
+
+def check_batch(gpu, circuit, sk, pts, cross=True):
+    """cross: the statements against uzk_cp_reveal_prove_batch too, whose contract is a secret below L"""
     from uzkge_amd import reveal as rv
     w = circuit.witness(sk, pts)
     try:
@@ -77,11 +88,14 @@ def check_batch(gpu, circuit, sk, pts):
             if not np.array_equal(z[i], want):
                 bad = [j for j in range(rc.N_VARS) if not np.array_equal(z[i, j], want[j])]
                 raise AssertionError("card %d: %d variables differ, the first %d (%s)" % (i, len(bad), bad[0], rc.roles().get(bad[0])))
-        reveal, pk, _ = gpu.cp_reveal_prove_batch(rv.scalars_to_wire([sk])[0], rv.points_to_wire(pts), rv.scalars_to_wire([7 + i for i in range(len(pts))]))
+        if cross:
+            reveal, pk, _ = gpu.cp_reveal_prove_batch(rv.scalars_to_wire([sk])[0], rv.points_to_wire(pts), rv.scalars_to_wire([7 + i for i in range(len(pts))]))
         for i in range(len(pts)):
             assert np.array_equal(w.statements_wire[i, 0:2].reshape(8), rv.points_to_wire(pts[i:i + 1])[0])
-            assert np.array_equal(w.statements_wire[i, 2:4].reshape(8), reveal[i]) and np.array_equal(w.statements_wire[i, 4:6].reshape(8), pk)
+            if cross:
+                assert np.array_equal(w.statements_wire[i, 2:4].reshape(8), reveal[i]) and np.array_equal(w.statements_wire[i, 4:6].reshape(8), pk)
             assert w.statements[i] == rc.witness_statement([int(v) for v in oc.fr_to_ints(ref_witness(sk, pts[i])[:7])])
+            assert w.statements[i] == tuple(pts[i]) + tuple(ref_mul(sk, pts[i])) + tuple(ref_mul(sk, ed.G))
     finally:
         w.release()
 
@@ -110,6 +124,26 @@ def test_witness_parity(gpu, circuit, m):
 def test_witness_parity_at_the_edge_scalars(gpu, circuit, name):
     """sk = 0, 1, l - 1 and a scalar whose low 128 bits are all set, each over the edge points and past a wave boundary"""
     check_batch(gpu, circuit, EDGE_SKS[name], batch_points(66))
+
+
+_high = random.Random("gpu-reveal-cs-high")
+ONES = (1 << 256) - 1
+HIGH_SKS = {"2^256-1": ONES, "2^255": 1 << 255, "2^251": 1 << 251, "l": ed.L, "l+1": ed.L + 1, "2^32": 1 << 32, "2^224|2^31": 1 << 224 | 1 << 31,
+            "random-with-bit-255": 1 << 255 | _high.getrandbits(255)}
+
+
+@pytest.mark.parametrize("name", list(HIGH_SKS))
+def test_witness_parity_under_secrets_up_to_256_bits(gpu, circuit, name):
+    """sk is 256 plain bits and the circuit constrains only the bits, so every integer below 2^256 is a secret: all bits set; bit 255
+    alone (255 neutral iterations, then one point); bit 251, the first above every secret below L; L and L + 1 (a multiple of every
+    subgroup point's order, and one more); bit 32 alone and bit 224 with bit 31, where a word boundary decides the highest set bit
+    below an iteration; a random secret with bit 255 set.  Each over the edge points and past a wave boundary; the reveal and the
+    key are the integer multiples on the whole curve (a point with a component of order 8 among them).
+    uzk_cp_reveal_prove_batch does not refuse a secret of L or more, but its contract is one below L (its response is computed mod L),
+    so it is held against the statements only for the two secrets below L."""
+    sk = HIGH_SKS[name]
+    assert 0 <= sk < 1 << 256 and (sk < ed.L) == (name in ("2^32", "2^224|2^31"))
+    check_batch(gpu, circuit, sk, batch_points(66), cross=sk < ed.L)
 
 
 def test_the_witness_does_not_depend_on_the_batch(gpu, circuit):
@@ -145,6 +179,24 @@ def test_proofs_verify_under_the_reference_key(gpu, circuit, vk, m):
     bent = [list(st) for st in statements]
     bent[m - 1][2] = (bent[m - 1][2] + 1) % Q
     assert _verify(vk, blobs, bent, m) == (False, [0] * m)
+
+
+def test_a_proof_under_the_secret_of_all_ones_verifies(gpu, circuit, vk):
+    """sk = 2^256 - 1, far above L: the R1CS constrains the 256 bits and nothing else, so the proof is one of the statement
+    ([sk] e1, [sk] G) and is accepted under the reference's verifying key, on the device and by the Python-integer verifier; with one
+    statement word altered it is rejected.  The two cards are the generator and a point with a component of order 8."""
+    pts = batch_points(2)
+    assert pts == [ed.G, ORDER8]
+    r, s = _blinds(2, "ones")
+    statements, blobs = circuit.prove(ONES, pts, r, s)
+    assert [tuple(st) for st in statements] == [tuple(p) + tuple(ref_mul(ONES, p)) + tuple(ref_mul(ONES, ed.G)) for p in pts]
+    assert [list(st) for st in statements] == [[int(v) for v in oc.fr_to_ints(ref_witness(ONES, p)[1:7])] for p in pts]
+    assert _verify(vk, blobs, statements, "ones") == (True, [0, 0])
+    assert gr.verify(vr.real_vk(), [1] + list(statements[1]), _blob_proof(blobs[1]))
+    for word in (2, 5):                                      # reveal.x of the second card; then pk.y
+        bent = [list(st) for st in statements]
+        bent[1][word] = (bent[1][word] + 1) % Q
+        assert _verify(vk, blobs, bent, "ones") == (False, [0, 0])
 
 
 def test_the_device_path_equals_the_host_path_over_the_exported_matrices(gpu, circuit):

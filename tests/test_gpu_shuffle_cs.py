@@ -180,6 +180,79 @@ def test_witness_selectors_inputs_and_decks_are_the_restated_ones(gpu, cards):
         cir.release()
 
 
+def check_lanes(gpu, cir, key, t_pk, lanes):
+    """one call over the lanes [(deck, digits, perm)]: witness, wire selectors, public inputs and both output decks of every lane
+    against the restatement"""
+    got = run_witness(gpu, cir, key, [l[0] for l in lanes], [l[1] for l in lanes], [l[2] for l in lanes])
+    assert all(g.shape[0] == len(lanes) for g in got)
+    for lane, (deck, dg, pm) in enumerate(lanes):
+        for name, g, w in zip(("witness", "wsel", "pi", "e1", "e2"), got, expect_witness(deck, dg, pm, t_pk)):
+            assert np.array_equal(g[lane], w), (lane, name)
+    return got
+
+
+@pytest.mark.parametrize("cards", [64, 63])
+def test_witness_at_the_card_bound(gpu, cards):
+    """UZK_SHUFFLE_CS_MAX_CARDS and one below: only here the value kernel sums 64 (63) matrix entries of a row and of a column and
+    32 products, the last of them ragged at 63 cards (card 62 has no neighbour).  Three lanes in one call: the identity over all-zero
+    digits, the reversal of another deck over all-seven digits, a random permutation over random digits; then the second alone."""
+    from uzkge_amd import _native as N
+    assert N.SHUFFLE_CS_MAX_CARDS == 64
+    pk, deck, _, rnd = game(cards, 500 + cards)
+    _, deck2, _, _ = game(cards, 700 + cards)
+    t_pk = pk_tables(pk)
+    rng = random.Random(cards)
+    draw = [[rng.randrange(8) for _ in range(sr.ITERATIONS)] for _ in range(cards)]
+    const = lambda d: [[d] * sr.ITERATIONS for _ in range(cards)]
+    ident, rev = list(range(cards)), list(range(cards))[::-1]
+    assert rnd not in (ident, rev) and sorted(rnd) == ident
+    cir = make_circuit(cards)
+    try:
+        cs = cr.layout(cards)
+        assert (cir.n, cs.num_vars) == (32768, {64: 39682}.get(cards, cs.num_vars))
+        with gpu.RemarkKey(e.points_wire([pk])[0]) as key:
+            lanes = [(deck, const(0), ident), (deck2, const(7), rev), (deck, draw, rnd)]
+            got = check_lanes(gpu, cir, key, t_pk, lanes)
+            alone = run_witness(gpu, cir, key, [deck2], [const(7)], [rev])
+            assert all(np.array_equal(a[0], g[1]) for a, g in zip(alone, got))
+    finally:
+        cir.release()
+
+
+def test_the_largest_batch_and_the_refusal_of_one_more(gpu):
+    """UZK_SHUFFLE_CS_MAX_BATCH decks of 3 cards in one call, every lane its own deck and digits; three cards have six permutations,
+    so the lanes go through all of them in turn.  One deck more is refused before anything is written."""
+    import itertools
+    from uzkge_amd import UzkgeError
+    from uzkge_amd import _native as N
+    cards, batch = 3, N.SHUFFLE_CS_MAX_BATCH
+    assert batch == 64
+    pk = game(cards, 41)[0]
+    t_pk = pk_tables(pk)
+    perms = [list(p) for p in itertools.permutations(range(cards))]
+    lanes = [game(cards, 3000 + lane)[1:3] + (perms[lane % len(perms)],) for lane in range(batch)]
+    assert len({str(l[0]) for l in lanes}) == len({str(l[1]) for l in lanes}) == batch
+    cir = make_circuit(cards)
+    n, more = cir.n, batch + 1
+    d_w, d_s = gpu.dev_alloc(32 * 5 * n * more), gpu.dev_alloc(32 * 3 * n * more)
+    try:
+        with gpu.RemarkKey(e.points_wire([pk])[0]) as key:
+            check_lanes(gpu, cir, key, t_pk, lanes)
+            poison_w, poison_s = np.full((more * 5 * n, 4), 0xA5A5A5A5A5A5A5A5, dtype=np.uint64), np.full((more * 3 * n, 4), 0x5A5A5A5A5A5A5A5A, dtype=np.uint64)
+            gpu.dev_upload(d_w, poison_w)
+            gpu.dev_upload(d_s, poison_s)
+            over = lanes + lanes[:1]
+            e1, e2 = decks_wire([l[0] for l in over])
+            with pytest.raises(UzkgeError) as err:
+                cir.witness_batch(key, e1, e2, np.array([l[1] for l in over], dtype=np.uint8), np.array([l[2] for l in over], dtype=np.uint32), d_w, d_s)
+            assert err.value.code == N.UZK_ERR_PARAMETER and "%d decks" % more in str(err.value)
+            assert np.array_equal(gpu.dev_download(d_w, poison_w.shape), poison_w) and np.array_equal(gpu.dev_download(d_s, poison_s.shape), poison_s)
+    finally:
+        gpu.dev_free(d_w)
+        gpu.dev_free(d_s)
+        cir.release()
+
+
 def test_refusals_leave_the_outputs_alone(gpu):
     from uzkge_amd import UzkgeError
     from uzkge_amd import _native as N

@@ -17,7 +17,7 @@ from test_shuffle_cs_ref_host import game, pk_tables
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "cpp", "shufflecs_host.cpp")
-SIZES = [1, 2, 3, 4, 5, 6, 7, 20, 52, 64]
+SIZES = [1, 2, 3, 4, 5, 6, 7, 20, 52, 63, 64]      # 63: the most cards with a ragged last product; 64: UZK_SHUFFLE_CS_MAX_CARDS
 R = cr.R
 
 
@@ -94,7 +94,7 @@ def eval_defs(defs, deck, traces, perm):
     return out
 
 
-@pytest.mark.parametrize("cards", [1, 2, 3, 4, 5, 6, 7, 20])
+@pytest.mark.parametrize("cards", [1, 2, 3, 4, 5, 6, 7, 20, 63, 64])
 def test_every_variable_definition_gives_the_restated_value(dumps, cards):
     pk, deck, digits, perm = game(cards, 300 + cards)
     t_pk = pk_tables(pk)
