@@ -1054,6 +1054,73 @@ int uzk_cp_reveal_prove0_batch(const uint64_t* sk, const uint64_t* e1_mont, cons
                                uint8_t* proofs_out);
 int uzk_cp_reveal_verify0_batch(const uint64_t* statements_mont, const uint8_t* proofs, uint32_t m, uint8_t* verdict_out, uint64_t* challenges_out);
 
+/* ---- the point codec: ark-serialize's compressed G1, G2 and Baby Jubjub points, and keys made of them -----------------------------
+ * Everything the reference persists or sends as a point is in this form: groth16_pk.bin (load_groth16_pk), the SDK's key strings
+ * (hex_to_point), the card points (index_to_point: a y coordinate alone).  Decoding is a square root per point, one lane each
+ * (csrc/sqrt29.hpp); batches take host pointers like uzk_ed_*.
+ *   G1    32 bytes: x little-endian; in byte 31 bit 6 = infinity, bit 7 = "y is the larger of y and p - y, as integers"
+ *   G2    64 bytes: x.c0 then x.c1, little-endian; the flags in byte 63; "larger" orders Fq2 by c1 first, then c0
+ *   Ed    32 bytes: y little-endian; bit 7 of byte 31 = "x is the larger of x and q - x"; no infinity flag, the identity is (0, 1);
+ *         x^2 = (1 - y^2) / (1 - d y^2)  (get_point_from_y_unchecked(y, true) is this rule with the bit set)
+ * The library is strict: an encoding that ark never writes is status 1.
+ *   - G1, G2: infinity is bit 6 set, bit 7 clear and every other bit of the encoding zero; anything else with bit 6 set is status 1
+ *   - a masked coordinate (for G2 either component of x) at or above the modulus is status 1
+ *   - a sign bit on a coordinate that is its own negation (y = 0; x = 0 on the Edwards curve) is status 1
+ * status_out: n bytes in the numbering of uzk_ed_check_points, the first that applies: 1 not a canonical encoding; 2 no point (the
+ * right-hand side is not a square); 3 on the curve but [r] P != O (G2) or [L] P != identity (Ed), reported only with check_subgroup
+ * != 0 and never for G1 (cofactor 1); 0 accepted.  Outputs are wire form (uzk_g1_affine, uzk_g2_affine, Edwards x then y; canonical
+ * Montgomery words); an accepted infinity, and every point whose status is not 0, comes back as all-zero words.  A call returns
+ * UZK_OK when it ran, whatever the statuses say.  n == 0, n > UZK_CODEC_MAX_BATCH (larger inputs are the caller's loop) or a null
+ * pointer: UZK_ERR_PARAMETER before the device is touched.
+ * Encoding checks only that the coordinates are below the modulus (status 1: 32 or 64 zero bytes come back); it does not check the
+ * curve.  All-zero G1 / G2 words are infinity. */
+#define UZK_CODEC_MAX_BATCH 1048576
+int uzk_g1_decompress_batch(const uint8_t* enc, size_t n, uzk_g1_affine* out, uint8_t* status_out);
+int uzk_g2_decompress_batch(const uint8_t* enc, size_t n, int check_subgroup, uzk_g2_affine* out, uint8_t* status_out);
+int uzk_ed_decompress_batch(const uint8_t* enc, size_t n, int check_subgroup, uint64_t* points_mont_out, uint8_t* status_out);
+int uzk_g1_compress_batch(const uzk_g1_affine* points, size_t n, uint8_t* out, uint8_t* status_out);
+int uzk_g2_compress_batch(const uzk_g2_affine* points, size_t n, uint8_t* out, uint8_t* status_out);
+int uzk_ed_compress_batch(const uint64_t* points_mont, size_t n, uint8_t* out, uint8_t* status_out);
+/* n compressed points decoded straight into device memory the new handle owns (an SRS handle as of uzk_srs_register, a G2 handle as of
+ * uzk_g2_register; any n >= 1, decoded UZK_CODEC_MAX_BATCH at a time).  Any non-zero status refuses the call with UZK_ERR_PARAMETER,
+ * uzk_last_error names the first bad index, and no handle is made. */
+int uzk_srs_register_compressed(const uint8_t* enc, size_t n, uint64_t* handle_out);
+int uzk_g2_register_compressed(const uint8_t* enc, size_t n, int check_subgroup, uint64_t* handle_out);
+/* The sections of a compressed Groth16 ProvingKey<Bn254> (groth16_pk.bin): vk = alpha_g1 | beta_g2 | gamma_g2 | delta_g2 | Vec
+ * gamma_abc_g1, then beta_g1 | delta_g1 | Vec a_query | Vec b_g1_query | Vec b_g2_query | Vec h_query | Vec l_query (a Vec: u64
+ * little-endian length, then the elements).  Arrays are indexed by UZK_PK_* (the struct cannot share the function's name in C: uzk_g16_pk_sections). */
+#define UZK_G16_PK_SECTIONS 12
+#define UZK_PK_ALPHA_G1 0
+#define UZK_PK_BETA_G2 1
+#define UZK_PK_GAMMA_G2 2
+#define UZK_PK_DELTA_G2 3
+#define UZK_PK_GAMMA_ABC_G1 4
+#define UZK_PK_BETA_G1 5
+#define UZK_PK_DELTA_G1 6
+#define UZK_PK_A_QUERY 7
+#define UZK_PK_B_G1_QUERY 8
+#define UZK_PK_B_G2_QUERY 9
+#define UZK_PK_H_QUERY 10
+#define UZK_PK_L_QUERY 11
+typedef struct {
+    uint64_t offset[UZK_G16_PK_SECTIONS];       /* of the section's first encoding, in bytes */
+    uint64_t count[UZK_G16_PK_SECTIONS];        /* encodings in the section */
+    uint64_t infinities[UZK_G16_PK_SECTIONS];   /* of them, how many have the infinity bit set */
+    uint64_t bytes;                             /* the length of the key */
+} uzk_g16_pk_sections;
+/* Host only, no device.  A key that ends inside a section, a length that does not fit the bytes left, or bytes behind the key:
+ * UZK_ERR_PARAMETER, and uzk_last_error names the section. */
+int uzk_g16_pk_layout(const uint8_t* pk, size_t len, uzk_g16_pk_sections* out);
+/* A key from its bytes: ALL G1 encodings are decoded in one launch and all G2 encodings in one (with validate != 0 also the G2
+ * subgroup check, one more launch), then the points go to uzk_g16_vk_create / uzk_reveal_circuit_create through host memory.  Any
+ * non-zero status refuses the key with UZK_ERR_PARAMETER; uzk_last_error names the section and the index in it.  Without validate the
+ * points are still decoded strictly and are on their curves (a decoded point always is); only the subgroup of the G2 points is taken on
+ * trust, as the reference does (deserialize_compressed_unchecked).
+ * uzk_g16_vk_create_compressed reads the first 232 + 32 l bytes of key (a verifying key, or a proving key's head) and ignores what lies
+ * behind them; uzk_reveal_circuit_create_compressed takes the whole proving key. */
+int uzk_g16_vk_create_compressed(const uint8_t* key, size_t len, int validate, uint64_t* vk_out);
+int uzk_reveal_circuit_create_compressed(const uint8_t* pk, size_t len, int validate, uint64_t* circuit_out);
+
 /* ---- synthetic workloads (bench / tests; generated on device, nothing uploaded) -------- */
 /* d_points[i] = (i + 1) * Q with Q = seed_scalar * G: n distinct valid G1 points whose discrete
  * logs relative to Q are known, so MSM(points, s) == (sum_i s_i (i+1)) * Q for any size. */

@@ -143,6 +143,11 @@ int uzk_test_match_cs_tables(uint64_t circuit, uint32_t* wiring_out, uint32_t* p
  * quot_out: count x 4 words, plain; rem_out: count words. */
 int uzk_test_match_divrem(const uint64_t* values, uint32_t m, uint32_t count, uint64_t* quot_out, uint32_t* rem_out);
 
+/* The square roots of csrc/sqrt29.hpp, one lane per element.  field: 0 = Fq, 1 = Fq2 (8 words per element, c0 then c1), 2 = Fr.  a_mont:
+ * n canonical Montgomery elements; root_out: n elements, a root where there is one (unspecified otherwise); is_square_out: n bytes,
+ * 1 iff root^2 = a held on the device.  n outside 1 .. UZK_CODEC_MAX_BATCH or a word not below the modulus: UZK_ERR_PARAMETER. */
+int uzk_test_sqrt_kat(int field, const uint64_t* a_mont, size_t n, uint64_t* root_out, uint8_t* is_square_out);
+
 #ifdef __cplusplus
 }
 #endif

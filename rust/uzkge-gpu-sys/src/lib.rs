@@ -409,6 +409,18 @@ impl Groth16Vk {
         }
         Ok(Groth16Vk { handle, n_inputs: l as usize })
     }
+    /// The key from its compressed bytes (`uzk_g16_vk_create_compressed`): a verifying key, or a proving key whose head is one.
+    /// The points are decoded on the device; `validate` adds the subgroup check of beta, gamma and delta.
+    pub fn from_compressed(key: &[u8], validate: bool) -> Result<Self, Error> {
+        let mut handle = 0u64;
+        check(unsafe { uzk_g16_vk_create_compressed(key.as_ptr(), key.len(), validate as c_int, &mut handle) })?;
+        let (mut l, mut dev) = (0u32, 0 as c_int);
+        if let Err(e) = check(unsafe { uzk_g16_vk_info(handle, &mut l, &mut dev) }) {
+            unsafe { uzk_g16_vk_release(handle) };
+            return Err(e);
+        }
+        Ok(Groth16Vk { handle, n_inputs: l as usize })
+    }
     /// l, the constant one included.
     pub fn n_inputs(&self) -> usize { self.n_inputs }
     /// `proofs`: m blobs of `UZK_G16_PROOF_BYTES`, back to back; `public`: m x (l - 1) inputs; `weights`: one element per proof,
@@ -890,6 +902,19 @@ impl RevealCircuit {
         }
         Ok(Self { handle, key })
     }
+    /// The circuit over a compressed `ProvingKey<Bn254>` (groth16_pk.bin as it lies on disk): every point of the key is decoded on
+    /// the device, all G1 encodings in one launch and all G2 encodings in one (`uzk_reveal_circuit_create_compressed`).  `validate`
+    /// adds the subgroup check of the G2 points; a point that fails any check refuses the key (`last_error` names it).
+    pub fn from_compressed(pk: &[u8], validate: bool) -> Result<Self, Error> {
+        let mut handle = 0u64;
+        check(unsafe { uzk_reveal_circuit_create_compressed(pk.as_ptr(), pk.len(), validate as c_int, &mut handle) })?;
+        let mut key = 0u64;
+        if let Err(e) = check(unsafe { uzk_reveal_circuit_key(handle, &mut key) }) {
+            unsafe { uzk_reveal_circuit_release(handle) };
+            return Err(e);
+        }
+        Ok(Self { handle, key })
+    }
     pub fn handle(&self) -> u64 { self.handle }
     /// the inner Groth16 key, for the `uzk_g16_*` entry points; it lives as long as the circuit
     pub fn key(&self) -> u64 { self.key }
@@ -1052,5 +1077,62 @@ impl Prover {
 impl Drop for Prover {
     fn drop(&mut self) {
         unsafe { uzk_prover_destroy(self.handle) };
+    }
+}
+
+// ---- the point codec: ark-serialize's compressed points, decoded and encoded on the device ------------------------------------------
+/// `uzk_*_decompress_batch` / `uzk_*_compress_batch`: encodings back to back (G1 32 bytes, G2 64, Baby Jubjub 32), points in the wire
+/// forms, one status byte per point -- 0 accepted, 1 not a canonical encoding, 2 no point, 3 outside the prime-order subgroup (only
+/// when asked).  A point whose status is not 0, and an accepted infinity, is all zeros.
+pub mod codec {
+    use super::*;
+
+    fn count(bytes: usize, width: usize) -> Result<usize, Error> {
+        if bytes == 0 || bytes % width != 0 || bytes / width > UZK_CODEC_MAX_BATCH as usize {
+            return Err(Error::Parameter);
+        }
+        Ok(bytes / width)
+    }
+    pub fn g1_decompress(enc: &[u8]) -> Result<(Vec<uzk_g1_affine>, Vec<u8>), Error> {
+        let n = count(enc.len(), 32)?;
+        let (mut out, mut status) = (vec![uzk_g1_affine::default(); n], vec![0u8; n]);
+        check(unsafe { uzk_g1_decompress_batch(enc.as_ptr(), n, out.as_mut_ptr(), status.as_mut_ptr()) })?;
+        Ok((out, status))
+    }
+    pub fn g2_decompress(enc: &[u8], check_subgroup: bool) -> Result<(Vec<uzk_g2_affine>, Vec<u8>), Error> {
+        let n = count(enc.len(), 64)?;
+        let (mut out, mut status) = (vec![uzk_g2_affine::default(); n], vec![0u8; n]);
+        check(unsafe { uzk_g2_decompress_batch(enc.as_ptr(), n, check_subgroup as c_int, out.as_mut_ptr(), status.as_mut_ptr()) })?;
+        Ok((out, status))
+    }
+    pub fn ed_decompress(enc: &[u8], check_subgroup: bool) -> Result<(Vec<EdPoint>, Vec<u8>), Error> {
+        let n = count(enc.len(), 32)?;
+        let (mut out, mut status) = (vec![[[0u64; 4]; 2]; n], vec![0u8; n]);
+        check(unsafe { uzk_ed_decompress_batch(enc.as_ptr(), n, check_subgroup as c_int, out.as_mut_ptr() as *mut u64, status.as_mut_ptr()) })?;
+        Ok((out, status))
+    }
+    pub fn g1_compress(points: &[uzk_g1_affine]) -> Result<(Vec<u8>, Vec<u8>), Error> {
+        let n = count(points.len() * 32, 32)?;
+        let (mut out, mut status) = (vec![0u8; 32 * n], vec![0u8; n]);
+        check(unsafe { uzk_g1_compress_batch(points.as_ptr(), n, out.as_mut_ptr(), status.as_mut_ptr()) })?;
+        Ok((out, status))
+    }
+    pub fn g2_compress(points: &[uzk_g2_affine]) -> Result<(Vec<u8>, Vec<u8>), Error> {
+        let n = count(points.len() * 64, 64)?;
+        let (mut out, mut status) = (vec![0u8; 64 * n], vec![0u8; n]);
+        check(unsafe { uzk_g2_compress_batch(points.as_ptr(), n, out.as_mut_ptr(), status.as_mut_ptr()) })?;
+        Ok((out, status))
+    }
+    pub fn ed_compress(points: &[EdPoint]) -> Result<(Vec<u8>, Vec<u8>), Error> {
+        let n = count(points.len() * 32, 32)?;
+        let (mut out, mut status) = (vec![0u8; 32 * n], vec![0u8; n]);
+        check(unsafe { uzk_ed_compress_batch(points.as_ptr() as *const u64, n, out.as_mut_ptr(), status.as_mut_ptr()) })?;
+        Ok((out, status))
+    }
+    /// Host only: where the sections of a compressed Groth16 proving key lie (`uzk_g16_pk_layout`).
+    pub fn g16_pk_layout(pk: &[u8]) -> Result<uzk_g16_pk_sections, Error> {
+        let mut out = uzk_g16_pk_sections::default();
+        check(unsafe { uzk_g16_pk_layout(pk.as_ptr(), pk.len(), &mut out) })?;
+        Ok(out)
     }
 }

@@ -166,6 +166,17 @@ PROTOTYPES = {
     "uzk_anemoi_permutations": (ctypes.c_uint32, [ctypes.c_uint32, ctypes.c_uint32]),
     "uzk_cp_reveal_prove0_batch": (_I, [_P, _P, _P, ctypes.c_uint32, _P, _P, _P]),
     "uzk_cp_reveal_verify0_batch": (_I, [_P, _P, ctypes.c_uint32, _P, _P]),
+    "uzk_g1_decompress_batch": (_I, [_P, _SZ, _P, _P]),
+    "uzk_g2_decompress_batch": (_I, [_P, _SZ, _I, _P, _P]),
+    "uzk_ed_decompress_batch": (_I, [_P, _SZ, _I, _P, _P]),
+    "uzk_g1_compress_batch": (_I, [_P, _SZ, _P, _P]),
+    "uzk_g2_compress_batch": (_I, [_P, _SZ, _P, _P]),
+    "uzk_ed_compress_batch": (_I, [_P, _SZ, _P, _P]),
+    "uzk_srs_register_compressed": (_I, [_P, _SZ, ctypes.POINTER(_U64)]),
+    "uzk_g2_register_compressed": (_I, [_P, _SZ, _I, ctypes.POINTER(_U64)]),
+    "uzk_g16_pk_layout": (_I, [_P, _SZ, _P]),
+    "uzk_g16_vk_create_compressed": (_I, [_P, _SZ, _I, ctypes.POINTER(_U64)]),
+    "uzk_reveal_circuit_create_compressed": (_I, [_P, _SZ, _I, ctypes.POINTER(_U64)]),
     "uzk_synth_points_arith": (_I, [_P, _SZ, _P]),
     "uzk_synth_points_random": (_I, [_P, _SZ, _U64]),
     "uzk_synth_scalars": (_I, [_P, _SZ, _U64]),
@@ -206,6 +217,7 @@ TEST_PROTOTYPES = {
     "uzk_test_srs_weights_device": (_I, [_P, _U64, _P]),
     "uzk_test_lanes": (_I, [_I, _P, _P, ctypes.c_uint32, _P, _P, _P, ctypes.c_uint32, _U64, _P, ctypes.POINTER(ctypes.c_int)]),
     "uzk_test_ntt_in_len": (_I, [_P, _U64, _P, _U64, _U64, ctypes.c_uint32, _P, _U64]),
+    "uzk_test_sqrt_kat": (_I, [_I, _P, _SZ, _P, _P]),
 }
 
 
@@ -373,3 +385,15 @@ class SrsCurveReport(ctypes.Structure):
     """uzk_srs_curve_report (include/uzkge_gpu.h)."""
     _fields_ = [("checked", ctypes.c_uint64), ("infinity", ctypes.c_uint64), ("non_canonical", ctypes.c_uint64), ("off_curve", ctypes.c_uint64),
                 ("first_bad", ctypes.c_uint64)]
+
+
+CODEC_MAX_BATCH = 1 << 20
+G16_PK_SECTIONS = 12
+PK_SECTION_NAMES = ("alpha_g1", "beta_g2", "gamma_g2", "delta_g2", "gamma_abc_g1", "beta_g1", "delta_g1", "a_query", "b_g1_query", "b_g2_query",
+                    "h_query", "l_query")
+
+
+class G16PkSections(ctypes.Structure):
+    """uzk_g16_pk_sections (include/uzkge_gpu.h): arrays indexed by UZK_PK_*, in the order of PK_SECTION_NAMES."""
+    _fields_ = [("offset", ctypes.c_uint64 * G16_PK_SECTIONS), ("count", ctypes.c_uint64 * G16_PK_SECTIONS),
+                ("infinities", ctypes.c_uint64 * G16_PK_SECTIONS), ("bytes", ctypes.c_uint64)]

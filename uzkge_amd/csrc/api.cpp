@@ -9,10 +9,13 @@
 #include <cstring>
 #include <exception>
 #include <new>
+#include <vector>
 
 #include "anemoi29.hpp"
 #include "ctx.hpp"
+#include "curvecheck.hpp"
 #include "fq12_29.hpp"
+#include "g16_pk_layout.hpp"
 #include "g2_29.hpp"
 #include "host_ec64.hpp"
 #include "host_math.hpp"
@@ -234,6 +237,7 @@ static void ctx_release(Ctx& c) {
     c.verify_ws.release();
     c.g16v_ws.release();
     c.ed_ws.release();
+    c.codec_ws.release();
     c.shuffle_ws.release();
     c.match_ws.release();
     c.reveal_ws.release();
@@ -1689,6 +1693,213 @@ int uzk_reveal_prove_snark_batch(uint64_t circuit, const uint64_t* sk, const uin
                                  uint64_t* statements_out, uzk_g16_proof* proofs_out) try {
     return rcs_prove_snark_batch(circuit, sk, e1_mont, r_mont, s_mont, m, statements_out, proofs_out);
 } catch (...) { return uzk::on_exception("uzk_reveal_prove_snark_batch"); }
+
+/* ---- the point codec ------------------------------------------------------------------------------ */
+static int codec_batch_args(const char* who, const void* in, size_t n, const void* out, const void* status) {
+    if (n == 0 || n > UZK_CODEC_MAX_BATCH) { set_error("%s: %zu points (1 .. %d per call)", who, n, UZK_CODEC_MAX_BATCH); return UZK_ERR_PARAMETER; }
+    if (!in || !out || !status) { set_error("%s: null pointer", who); return UZK_ERR_PARAMETER; }
+    return UZK_OK;
+}
+static int codec_decompress_entry(const char* who, int group, const uint8_t* in, size_t n, int check_subgroup, void* out, uint8_t* status_out) {
+    API_LOCK;
+    UZK_TRY(codec_batch_args(who, in, n, out, status_out));
+    UZK_TRY(require_ready());
+    return codec_decompress_run(ctx(), group, in, n, check_subgroup != 0, out, nullptr, status_out);
+}
+static int codec_compress_entry(const char* who, int group, const void* points, size_t n, uint8_t* out, uint8_t* status_out) {
+    API_LOCK;
+    UZK_TRY(codec_batch_args(who, points, n, out, status_out));
+    UZK_TRY(require_ready());
+    return codec_compress_run(ctx(), group, points, n, out, status_out);
+}
+
+int uzk_g1_decompress_batch(const uint8_t* enc, size_t n, uzk_g1_affine* out, uint8_t* status_out) try {
+    return codec_decompress_entry("uzk_g1_decompress_batch", 0, enc, n, 0, out, status_out);
+} catch (...) { return uzk::on_exception("uzk_g1_decompress_batch"); }
+
+int uzk_g2_decompress_batch(const uint8_t* enc, size_t n, int check_subgroup, uzk_g2_affine* out, uint8_t* status_out) try {
+    return codec_decompress_entry("uzk_g2_decompress_batch", 1, enc, n, check_subgroup, out, status_out);
+} catch (...) { return uzk::on_exception("uzk_g2_decompress_batch"); }
+
+int uzk_ed_decompress_batch(const uint8_t* enc, size_t n, int check_subgroup, uint64_t* points_mont_out, uint8_t* status_out) try {
+    return codec_decompress_entry("uzk_ed_decompress_batch", 2, enc, n, check_subgroup, points_mont_out, status_out);
+} catch (...) { return uzk::on_exception("uzk_ed_decompress_batch"); }
+
+int uzk_g1_compress_batch(const uzk_g1_affine* points, size_t n, uint8_t* out, uint8_t* status_out) try {
+    return codec_compress_entry("uzk_g1_compress_batch", 0, points, n, out, status_out);
+} catch (...) { return uzk::on_exception("uzk_g1_compress_batch"); }
+
+int uzk_g2_compress_batch(const uzk_g2_affine* points, size_t n, uint8_t* out, uint8_t* status_out) try {
+    return codec_compress_entry("uzk_g2_compress_batch", 1, points, n, out, status_out);
+} catch (...) { return uzk::on_exception("uzk_g2_compress_batch"); }
+
+int uzk_ed_compress_batch(const uint64_t* points_mont, size_t n, uint8_t* out, uint8_t* status_out) try {
+    return codec_compress_entry("uzk_ed_compress_batch", 2, points_mont, n, out, status_out);
+} catch (...) { return uzk::on_exception("uzk_ed_compress_batch"); }
+
+// n encodings of `group` decoded into a fresh device array, UZK_CODEC_MAX_BATCH at a time; a non-zero status frees it and is the error
+static int codec_register_decode(const char* who, int group, const uint8_t* in, size_t n, bool check_subgroup, void** d_out) {
+    Ctx& c = ctx();
+    const size_t enc = group == 1 ? 64 : 32, pt = group == 1 ? sizeof(G2Affine) : sizeof(Affine);
+    char* d = nullptr;
+    UZK_HIP(hipMalloc(reinterpret_cast<void**>(&d), n * pt));
+    std::vector<uint8_t> st;
+    int rc = UZK_OK;
+    for (size_t at = 0; at < n && rc == UZK_OK; at += UZK_CODEC_MAX_BATCH) {
+        const size_t m = std::min<size_t>(UZK_CODEC_MAX_BATCH, n - at);
+        st.assign(m, 0);
+        rc = codec_decompress_run(c, group, in + at * enc, m, check_subgroup, nullptr, d + at * pt, st.data());
+        for (size_t i = 0; i < m && rc == UZK_OK; ++i)
+            if (st[i]) { set_error("%s: point %zu: status %u", who, at + i, (unsigned)st[i]); rc = UZK_ERR_PARAMETER; }
+    }
+    if (rc != UZK_OK) { (void)hipFree(d); return rc; }
+    *d_out = d;
+    return UZK_OK;
+}
+
+int uzk_srs_register_compressed(const uint8_t* enc, size_t n, uint64_t* handle_out) try {
+    API_LOCK;
+    if (!enc || !handle_out) { set_error("uzk_srs_register_compressed: null pointer"); return UZK_ERR_PARAMETER; }
+    if (n == 0 || n > (SIZE_MAX >> 8)) { set_error("uzk_srs_register_compressed: %zu points", n); return UZK_ERR_PARAMETER; }
+    UZK_TRY(require_ready());
+    void* d = nullptr;
+    UZK_TRY(codec_register_decode("uzk_srs_register_compressed", 0, enc, n, false, &d));
+    Ctx::Srs s;
+    s.d_points = static_cast<Affine*>(d);
+    s.n = n;
+    s.owned = true;
+    s.device = ctx().device;
+    *handle_out = srs_insert(s);
+    return UZK_OK;
+} catch (...) { return uzk::on_exception("uzk_srs_register_compressed"); }
+
+int uzk_g2_register_compressed(const uint8_t* enc, size_t n, int check_subgroup, uint64_t* handle_out) try {
+    API_LOCK;
+    if (!enc || !handle_out) { set_error("uzk_g2_register_compressed: null pointer"); return UZK_ERR_PARAMETER; }
+    if (n == 0 || n > (SIZE_MAX >> 8)) { set_error("uzk_g2_register_compressed: %zu points", n); return UZK_ERR_PARAMETER; }
+    UZK_TRY(require_ready());
+    void* d = nullptr;
+    UZK_TRY(codec_register_decode("uzk_g2_register_compressed", 1, enc, n, check_subgroup != 0, &d));
+    return g2_register_owned(static_cast<G2Affine*>(d), n, ctx().device, handle_out);
+} catch (...) { return uzk::on_exception("uzk_g2_register_compressed"); }
+
+static int pk_layout_checked(const char* who, const uint8_t* pk, size_t len, bool whole_key, uzk_g16_pk_sections* out) {
+    int bad = 0;
+    switch (g16_pk_layout_parse(pk, len, whole_key, out, &bad)) {
+        case PK_PARSE_OK: return UZK_OK;
+        case PK_PARSE_TRUNCATED: set_error("%s: %zu bytes end inside %s", who, len, g16_pk_section_name(bad)); break;
+        case PK_PARSE_LENGTH: set_error("%s: the length of %s does not fit the %zu bytes of the key", who, g16_pk_section_name(bad), len); break;
+        case PK_PARSE_TRAILING: set_error("%s: bytes behind %s, the last section", who, g16_pk_section_name(bad)); break;
+    }
+    return UZK_ERR_PARAMETER;
+}
+
+int uzk_g16_pk_layout(const uint8_t* pk, size_t len, uzk_g16_pk_sections* out) try {
+    if (!pk || !out) { set_error("uzk_g16_pk_layout: null pointer"); return UZK_ERR_PARAMETER; }
+    return pk_layout_checked("uzk_g16_pk_layout", pk, len, true, out);
+} catch (...) { return uzk::on_exception("uzk_g16_pk_layout"); }
+
+// The points of sections [0, sections) of a key: every G1 encoding in one launch, every G2 encoding in one (two with validate).
+// first[s]: where section s begins in g1 or g2.  Takes the context lock for the decoding only.
+static int key_decode(const char* who, const uint8_t* key, const uzk_g16_pk_sections& lay, int sections, bool validate, std::vector<Affine>& g1,
+                      std::vector<G2Affine>& g2, size_t (&first)[UZK_G16_PK_SECTIONS]) {
+    std::vector<uint8_t> e1, e2;
+    for (int s = 0; s < sections; ++s) {
+        std::vector<uint8_t>& e = g16_pk_section_is_g2(s) ? e2 : e1;
+        const size_t width = g16_pk_section_width(s);
+        first[s] = e.size() / width;
+        e.insert(e.end(), key + lay.offset[s], key + lay.offset[s] + (size_t)lay.count[s] * width);
+    }
+    const size_t n1 = e1.size() / 32, n2 = e2.size() / 64;
+    if (n1 > UZK_CODEC_MAX_BATCH || n2 > UZK_CODEC_MAX_BATCH) { set_error("%s: %zu G1 and %zu G2 points (at most %d each)", who, n1, n2, UZK_CODEC_MAX_BATCH); return UZK_ERR_PARAMETER; }
+    g1.resize(n1);
+    g2.resize(n2);
+    std::vector<uint8_t> s1(n1), s2(n2);
+    {
+        API_LOCK;
+        UZK_TRY(require_ready());
+        if (n1) UZK_TRY(codec_decompress_run(ctx(), 0, e1.data(), n1, false, g1.data(), nullptr, s1.data()));
+        if (n2) UZK_TRY(codec_decompress_run(ctx(), 1, e2.data(), n2, validate, g2.data(), nullptr, s2.data()));
+    }
+    for (int s = 0; s < sections; ++s) {
+        const std::vector<uint8_t>& st = g16_pk_section_is_g2(s) ? s2 : s1;
+        for (size_t i = 0; i < lay.count[s]; ++i)
+            if (st[first[s] + i]) {
+                set_error("%s: %s[%zu]: status %u (1 not canonical, 2 no point, 3 outside the subgroup)", who, g16_pk_section_name(s), i, (unsigned)st[first[s] + i]);
+                return UZK_ERR_PARAMETER;
+            }
+    }
+    return UZK_OK;
+}
+static uzk_g1_affine as_c_g1(const Affine& p) { uzk_g1_affine r; memcpy(&r, &p, sizeof r); return r; }
+static uzk_g2_affine as_c_g2(const G2Affine& p) { uzk_g2_affine r; memcpy(&r, &p, sizeof r); return r; }
+
+int uzk_g16_vk_create_compressed(const uint8_t* key, size_t len, int validate, uint64_t* vk_out) try {
+    if (!key || !vk_out) { set_error("uzk_g16_vk_create_compressed: null pointer"); return UZK_ERR_PARAMETER; }
+    uzk_g16_pk_sections lay;
+    UZK_TRY(pk_layout_checked("uzk_g16_vk_create_compressed", key, len, false, &lay));
+    const uint64_t l = lay.count[UZK_PK_GAMMA_ABC_G1];
+    if (l < 1 || l > UZK_G16_VERIFY_MAX_INPUTS) { set_error("uzk_g16_vk_create_compressed: gamma_abc_g1 of %llu points (1 .. %d)", (unsigned long long)l, UZK_G16_VERIFY_MAX_INPUTS); return UZK_ERR_PARAMETER; }
+    std::vector<Affine> g1;
+    std::vector<G2Affine> g2;
+    size_t first[UZK_G16_PK_SECTIONS] = {};
+    UZK_TRY(key_decode("uzk_g16_vk_create_compressed", key, lay, 5, validate != 0, g1, g2, first));
+    uzk_g16_vk_desc d = {};
+    d.n_inputs = (uint32_t)l;
+    d.alpha_g1 = as_c_g1(g1[first[UZK_PK_ALPHA_G1]]);
+    d.beta_g2 = as_c_g2(g2[first[UZK_PK_BETA_G2]]);
+    d.gamma_g2 = as_c_g2(g2[first[UZK_PK_GAMMA_G2]]);
+    d.delta_g2 = as_c_g2(g2[first[UZK_PK_DELTA_G2]]);
+    d.gamma_abc_g1 = reinterpret_cast<const uzk_g1_affine*>(g1.data() + first[UZK_PK_GAMMA_ABC_G1]);
+    return uzk_g16_vk_create(&d, vk_out);
+} catch (...) { return uzk::on_exception("uzk_g16_vk_create_compressed"); }
+
+int uzk_reveal_circuit_create_compressed(const uint8_t* pk, size_t len, int validate, uint64_t* circuit_out) try {
+    if (!pk || !circuit_out) { set_error("uzk_reveal_circuit_create_compressed: null pointer"); return UZK_ERR_PARAMETER; }
+    uzk_g16_pk_sections lay;
+    UZK_TRY(pk_layout_checked("uzk_reveal_circuit_create_compressed", pk, len, true, &lay));
+    const uint64_t n_vars = lay.count[UZK_PK_A_QUERY];
+    if (n_vars > UINT32_MAX || lay.count[UZK_PK_GAMMA_ABC_G1] > UINT32_MAX || lay.count[UZK_PK_B_G1_QUERY] != n_vars || lay.count[UZK_PK_B_G2_QUERY] != n_vars) {
+        set_error("uzk_reveal_circuit_create_compressed: a_query, b_g1_query and b_g2_query of %llu, %llu and %llu points", (unsigned long long)n_vars,
+                  (unsigned long long)lay.count[UZK_PK_B_G1_QUERY], (unsigned long long)lay.count[UZK_PK_B_G2_QUERY]);
+        return UZK_ERR_PARAMETER;
+    }
+    std::vector<Affine> g1;
+    std::vector<G2Affine> g2;
+    size_t first[UZK_G16_PK_SECTIONS] = {};
+    UZK_TRY(key_decode("uzk_reveal_circuit_create_compressed", pk, lay, UZK_G16_PK_SECTIONS, validate != 0, g1, g2, first));
+    const auto g1s = [&](int s) { return reinterpret_cast<const uzk_g1_affine*>(g1.data() + first[s]); };
+    uzk_g16_key_desc d = {};
+    d.n_vars = (uint32_t)n_vars;
+    d.n_inputs = (uint32_t)lay.count[UZK_PK_GAMMA_ABC_G1];
+    d.l_query_len = lay.count[UZK_PK_L_QUERY];
+    d.h_query_len = lay.count[UZK_PK_H_QUERY];
+    d.alpha_g1 = *g1s(UZK_PK_ALPHA_G1);
+    d.beta_g1 = *g1s(UZK_PK_BETA_G1);
+    d.delta_g1 = *g1s(UZK_PK_DELTA_G1);
+    d.beta_g2 = as_c_g2(g2[first[UZK_PK_BETA_G2]]);
+    d.delta_g2 = as_c_g2(g2[first[UZK_PK_DELTA_G2]]);
+    d.a_query = g1s(UZK_PK_A_QUERY);
+    d.b_g1_query = g1s(UZK_PK_B_G1_QUERY);
+    d.l_query = g1s(UZK_PK_L_QUERY);
+    d.h_query = g1s(UZK_PK_H_QUERY);
+    d.b_g2_query = reinterpret_cast<const uzk_g2_affine*>(g2.data() + first[UZK_PK_B_G2_QUERY]);
+    return rcs_circuit_create(&d, circuit_out);
+} catch (...) { return uzk::on_exception("uzk_reveal_circuit_create_compressed"); }
+
+int uzk_test_sqrt_kat(int field, const uint64_t* a_mont, size_t n, uint64_t* root_out, uint8_t* is_square_out) try {
+    API_LOCK;
+    if (field < 0 || field > 2) { set_error("uzk_test_sqrt_kat: field %d (0 Fq, 1 Fq2, 2 Fr)", field); return UZK_ERR_PARAMETER; }
+    UZK_TRY(codec_batch_args("uzk_test_sqrt_kat", a_mont, n, root_out, is_square_out));
+    const size_t words = field == 1 ? 2 * n : n;
+    for (size_t i = 0; i < words; ++i)
+        if (!(field == 2 ? gv_below_modulus<FrCfg>(as_fp(a_mont)[i]) : gv_below_modulus<FqCfg>(as_fp(a_mont)[i]))) {
+            set_error("uzk_test_sqrt_kat: element %zu is not below the modulus", i);
+            return UZK_ERR_PARAMETER;
+        }
+    UZK_TRY(require_ready());
+    return codec_sqrt_kat_run(ctx(), field, as_fp(a_mont), n, reinterpret_cast<Fp*>(root_out), is_square_out);
+} catch (...) { return uzk::on_exception("uzk_test_sqrt_kat"); }
 
 int uzk_cp_mask_prove_batch(const uint64_t* pk_mont, const uint64_t* cards_mont, const uint64_t* rs, const uint64_t* omegas, uint32_t m, uint64_t* e1_out,
                             uint64_t* e2_out, uint8_t* proofs_out) try {

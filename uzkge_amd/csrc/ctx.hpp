@@ -164,6 +164,8 @@ struct Ctx {
     // assignments of uzk_reveal_prove_snark_batch
     DevBuf reveal_ws;
     DevBuf reveal_z;
+    // codec.hip: one block carved into the arrays of a decoding or encoding call (bytes, points, statuses)
+    DevBuf codec_ws;
     int tune_verify_transcript = 0;   // which transcript kernel a fold runs: 1 one proof per lane; 0 / 2 a proof's state spread over a half wave (the default)
     // an entry of the process-wide SRS registry
     struct Srs {
@@ -357,6 +359,12 @@ int anemoi_sponge_run(Ctx& c, const Fp* inputs, uint32_t len, size_t n, uint32_t
 // copied and nothing waited for.  d_trace: null or n x P x 64 elements
 int anemoi_sponge_device(Ctx& c, const Fp* d_inputs, uint32_t len, uint32_t n, uint32_t out_len, Fp* d_out, Fp* d_trace);
 int ed_raw_op_device(Ctx& c, int op, const uint32_t* in, uint32_t* out, size_t n);
+// codec.hip: compressed points.  group: 0 G1, 1 G2, 2 Baby Jubjub; in / out on the host unless named d_*.  d_out: null (the points
+// come back to `out`) or the device array the points are decoded into and stay in.
+int codec_decompress_run(Ctx& c, int group, const uint8_t* in, size_t n, bool check_subgroup, void* out, void* d_out, uint8_t* status_out);
+int codec_compress_run(Ctx& c, int group, const void* points, size_t n, uint8_t* out, uint8_t* status_out);
+int codec_sqrt_kat_run(Ctx& c, int field, const Fp* a, size_t n, Fp* root_out, uint8_t* is_square_out);
+int g2_register_owned(G2Affine* d_points, size_t n, int device, uint64_t* handle_out);     // g2msm.hip: the handle takes the array over
 // edwards.hip: the Chaum-Pedersen proofs of a mask; remask keys (process-wide handles: T_pk on the device), the tables and the remask
 int cp_mask_prove_run(Ctx& c, const EdAffine* pk, const EdAffine* cards, const Fp* rs, const Fp* omegas, uint32_t m, EdAffine* e1_out, EdAffine* e2_out,
                       uint8_t* proofs_out);

@@ -318,6 +318,14 @@ int g2_register(Ctx& c, const G2Affine* points, size_t n, uint64_t* handle_out) 
     *handle_out = g_reg.insert(e);
     return UZK_OK;
 }
+int g2_register_owned(G2Affine* d_points, size_t n, int device, uint64_t* handle_out) {
+    G2Entry e;
+    e.d_points = d_points;
+    e.n = n;
+    e.device = device;
+    *handle_out = g_reg.insert(e);
+    return UZK_OK;
+}
 bool g2_lookup(uint64_t handle, const G2Affine** d_points, size_t* n, int* device) {
     G2Entry e;
     if (!g_reg.get(handle, &e)) return false;

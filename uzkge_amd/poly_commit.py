@@ -608,6 +608,26 @@ class Groth16VerifierKey:
     def from_key_bytes(cls, head: bytes) -> "Groth16VerifierKey":
         return cls(*cls.parse_key_bytes(head))
 
+    @classmethod
+    def from_compressed(cls, data: bytes, validate: bool = False) -> "Groth16VerifierKey":
+        """`from_key_bytes` with the points decoded on the device (uzk_g16_vk_create_compressed): data is a compressed verifying key,
+        or a proving key whose first 232 + 32 l bytes are one.  validate: also the subgroup check of beta, gamma and delta.  The
+        integer attributes of the other constructors (alpha_g1 ...) are not filled in."""
+        import ctypes
+
+        from . import codec
+        raw = np.frombuffer(bytes(data), dtype=np.uint8)
+        h = ctypes.c_uint64(0)
+        codec.check(codec.lib.uzk_g16_vk_create_compressed(raw.ctypes.data_as(ctypes.c_void_p) if raw.size else None, raw.size, int(bool(validate)), ctypes.byref(h)))
+        self = cls.__new__(cls)
+        key = B.Groth16VerifierKey.__new__(B.Groth16VerifierKey)
+        key.handle = h.value
+        g2, _ = codec.g2_decompress(bytes(data[32:224]))             # accepted above: every status is 0
+        key.beta_g2, key.gamma_g2, key.delta_g2 = (g2[k].copy() for k in range(3))
+        key.n_inputs, key.device = key.info()
+        self.key, self.n_inputs = key, key.n_inputs
+        return self
+
     def _inputs(self, what, proofs, publics, weights):
         m = len(proofs)
         if m != len(publics) or (weights is not None and len(weights) != m) or any(len(p) != N.G16_PROOF_BYTES for p in proofs):

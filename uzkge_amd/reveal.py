@@ -61,6 +61,45 @@ def statements_to_wire(pks: Sequence[Point], e1s: Sequence[Point], reveal_cards:
     return points_to_wire(rows).reshape(len(e1s), 6, 4)
 
 
+def _decoded(who: str, raw: bytes, check_subgroup: bool) -> List[Point]:
+    from . import codec
+    wire, status = codec.ed_decompress(raw, check_subgroup)
+    bad = np.flatnonzero(status)
+    if bad.size:
+        raise ValueError("%s: point %d: status %d (1 not a canonical encoding, 2 not on the curve, 3 outside the prime-order subgroup)"
+                         % (who, int(bad[0]), int(status[bad[0]])))
+    return points_from_wire(wire)
+
+
+def points_from_hex(strings: Sequence[str], check_subgroup: bool = True) -> List[Point]:
+    """The SDK's point strings (shuffle/src/utils.rs hex_to_point: the hex of ark-serialize's 32 compressed bytes, with or without
+    "0x") decoded on the device in one call (uzk_ed_decompress_batch).  check_subgroup: what Validate::Yes adds to the curve check."""
+    raw = b"".join(bytes.fromhex(s[2:] if s.startswith("0x") else s) for s in strings)
+    if len(raw) != 32 * len(strings):
+        raise ValueError("a point string is 32 bytes")
+    return _decoded("points_from_hex", raw, check_subgroup) if strings else []
+
+
+def points_to_hex(points: Sequence[Point], with_start: bool = True) -> List[str]:
+    """point_to_hex of every point (uzk_ed_compress_batch)"""
+    from . import codec
+    if not len(points):
+        return []
+    enc, _ = codec.ed_compress(points_to_wire(points))              # points_to_wire refuses what status 1 would report
+    return [("0x" if with_start else "") + bytes(row).hex() for row in enc]
+
+
+def points_from_y(ys: Sequence[int], greatest: bool = True) -> List[Point]:
+    """index_to_point over a table of the caller's: the point with y = ys[i] and the larger (greatest) or smaller of its two x
+    (get_point_from_y_unchecked(y, greatest)), all in one call.  Neither the curve's cofactor nor the table is checked beyond the
+    curve equation: a y with no point is refused."""
+    if any(not 0 <= y < Q for y in ys):
+        raise ValueError("a y coordinate is not below q")
+    # y = +-1 has x = 0 alone: no sign to choose, and the strict decoder takes no sign bit on it
+    raw = b"".join((y | (int(bool(greatest) and y not in (1, Q - 1)) << 255)).to_bytes(32, "little") for y in ys)
+    return _decoded("points_from_y", raw, False) if len(ys) else []
+
+
 def keypair_public(sks: Sequence[int]) -> List[Point]:
     """pk = sk G for every secret"""
     return points_from_wire(b.ed_mul_batch(points_to_wire([GENERATOR])[0], scalars_to_wire(sks)))

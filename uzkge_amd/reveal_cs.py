@@ -94,6 +94,24 @@ class RevealCircuit(b.RevealCircuit):
         self.vk_points = (k["alpha_g1"], k["beta_g2"], k["gamma_g2"], k["delta_g2"], k["gamma_abc_g1"])
         return self
 
+    @classmethod
+    def from_compressed(cls, data: bytes, validate: bool = False) -> "RevealCircuit":
+        """`from_key_bytes` with every point of the key decoded on the device (uzk_reveal_circuit_create_compressed): one launch for the
+        22 801 G1 encodings of the reference's key, one for its 4 872 G2 encodings.  validate: also the subgroup check of the G2
+        points; a point that fails any check is refused with its section and index.  vk_points is not filled in: make the verifying
+        key with Groth16VerifierKey.from_compressed(data)."""
+        import ctypes
+        raw = np.frombuffer(bytes(data), dtype=np.uint8)
+        h = ctypes.c_uint64(0)
+        b.check(b.lib.uzk_reveal_circuit_create_compressed(raw.ctypes.data_as(ctypes.c_void_p) if raw.size else None, raw.size, int(bool(validate)), ctypes.byref(h)))
+        self = cls.__new__(cls)
+        self.handle = h.value
+        k = ctypes.c_uint64(0)
+        b.check(b.lib.uzk_reveal_circuit_key(self.handle, ctypes.byref(k)))
+        self.key = b.Groth16Key(k.value)
+        self.n_vars = self.key.n_vars
+        return self
+
     def witness(self, sk: int, cards) -> RevealWitness:
         e1 = rv.points_to_wire(_e1s(cards))
         m = e1.shape[0]
