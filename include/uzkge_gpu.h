@@ -199,6 +199,11 @@ int uzk_msm_g2(uint64_t handle, size_t offset, const uint64_t* scalars_mont, siz
 /* `batch` scalar vectors (scalars[b*n + i]) against the same bases in one launch sequence: the reveal proofs of one deck. */
 int uzk_msm_g2_batch(uint64_t handle, size_t offset, const uint64_t* scalars_mont, size_t n, uint32_t batch, uzk_g2_jac* out);
 int uzk_msm_g2_batch_device(uint64_t handle, size_t offset, const void* d_scalars_mont, size_t n, uint32_t batch, uzk_g2_jac* out);
+/* The same sums finished on the device: handle, offset, n, batch, UZK_ERR_DEGREE and infinities as uzk_msm_g2_batch_device, but the
+ * window sums never come back -- their chunk sums (n > 2^15), the Horner chain over the 32 windows and the affine map are kernels.
+ * The results are canonical affine points (fully reduced Montgomery words; infinity all zeros), written to out (host, batch points),
+ * to d_out (device, batch points), or to both; both NULL is UZK_ERR_PARAMETER.  Complete when the call returns. */
+int uzk_msm_g2_batch_finish(uint64_t handle, size_t offset, const void* d_scalars_mont, size_t n, uint32_t batch, uzk_g2_affine* out, void* d_out);
 /* Host-side fold of partial sums and Jacobian -> affine (canonical words), as for G1. */
 int uzk_g2_fold(const uzk_g2_jac* partials, size_t count, uzk_g2_jac* out);
 int uzk_g2_to_affine(const uzk_g2_jac* p, uzk_g2_affine* out);
@@ -266,6 +271,16 @@ int uzk_g16_prove_batch(uint64_t key, const uint64_t* z_mont, const uint64_t* r_
 /* The same with the assignments already in device memory (a witness produced there); z[0] is not read back. */
 int uzk_g16_prove_batch_device(uint64_t key, const void* d_z_mont, const uint64_t* r_mont, const uint64_t* s_mont, uint32_t batch,
                                uzk_g16_proof* out);
+/* The same proofs finished on the device: B comes from uzk_msm_g2_batch_finish's kernels, the three G1 sums are uploaded again
+ * (288 bytes per proof) and s A, r B1, their sum with K, the affine maps of A and C and the encoding are kernels -- no curve arithmetic
+ * on the host.  z_mont is a host array (z_on_device == 0; z[0] must be 1) or a device array (z_on_device != 0), r and s as above.
+ *   proofs_out   host, batch proofs in the struct layout: bit for bit what uzk_g16_prove_batch writes
+ *   blobs_out    host, batch x UZK_G16_PROOF_BYTES: what uzk_g16_verify_batch reads -- the words a.x, a.y, b.x.c1, b.x.c0, b.y.c1, b.y.c0,
+ *                c.x, c.y, each the canonical integer in 32 big-endian bytes; infinity is all-zero coordinates
+ *   d_blobs_out  device, the same bytes, left there
+ * Any of the three may be NULL, not all of them (UZK_ERR_PARAMETER).  Complete when the call returns. */
+int uzk_g16_prove_batch_finish(uint64_t key, const void* z_mont, int z_on_device, const uint64_t* r_mont, const uint64_t* s_mont, uint32_t batch,
+                               uzk_g16_proof* proofs_out, uint8_t* blobs_out, void* d_blobs_out);
 
 /* ---- NTT: replaces EvaluationDomain::{fft, ifft} (field_polynomial.rs:585,595) --------- */
 /* The largest transforms this library runs: n = 2^k with k <= UZK_NTT_MAX_LOG2, n = 3 * 2^k with k <= UZK_NTT_MAX_LOG2_MIXED.
@@ -1017,6 +1032,10 @@ int uzk_reveal_witness_batch(uint64_t circuit, const uint64_t* sk, const uint64_
  * between.  r_mont, s_mont: m blinding scalars each; proofs_out: m proofs as uzk_g16_prove_batch writes them. */
 int uzk_reveal_prove_snark_batch(uint64_t circuit, const uint64_t* sk, const uint64_t* e1_mont, const uint64_t* r_mont, const uint64_t* s_mont, uint32_t m,
                                  uint64_t* statements_out, uzk_g16_proof* proofs_out);
+/* uzk_reveal_witness_batch into the same buffer, then uzk_g16_prove_batch_finish over it: the proofs leave the call as the blobs
+ * uzk_g16_verify_batch reads.  proofs_out, blobs_out (host) and d_blobs_out (device) as there: any may be NULL, not all. */
+int uzk_reveal_prove_snark_batch_finish(uint64_t circuit, const uint64_t* sk, const uint64_t* e1_mont, const uint64_t* r_mont, const uint64_t* s_mont,
+                                        uint32_t m, uint64_t* statements_out, uzk_g16_proof* proofs_out, uint8_t* blobs_out, void* d_blobs_out);
 
 /* ---- Anemoi-Jive over BN254's scalar field: hashes, the stream cipher, their traces (uzkge/src/anemoi) -------------------------------
  * AnemoiJive254: 2 columns, 14 rounds, alpha = 5, g = 5, delta = 1 / g, the round keys of the Anemoi paper's pi rule; a sponge of rate

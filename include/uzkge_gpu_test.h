@@ -44,6 +44,12 @@ int uzk_test_g1_kat(int op, const uzk_g1_affine* a, const uzk_g1_affine* b, uzk_
  * zeros; out: n Jacobian points of 24 words): 10 a + b by the accumulator's mixed addition (complete: doubling, cancellation,
  * infinity on either side), 11 a + b by the full XYZZ addition, 12 2a, 13 a - b (mixed, negated operand), 14 2(a + b). */
 int uzk_test_g2_kat(int op, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n);
+/* The finish kernels of uzk_g16_prove_batch_finish (csrc/groth16.hip g16_chains, g16_combine) on the caller's points: record i is three
+ * Jacobian points A, B1, K (any Z; infinity <=> z = 0) and the blinds r, s (Montgomery words); a_out[i] = the affine A, c_out[i] = the
+ * affine s A + r B1 + K, canonical words, infinity all zeros.  A real key cannot be steered into the degenerate branches (equal or
+ * opposite terms, an infinite operand or sum); this can.  n <= 4096. */
+int uzk_test_g16_finish(const uzk_g1_jac* a_jac, const uzk_g1_jac* b1_jac, const uzk_g1_jac* k_jac, const uint64_t* r_mont, const uint64_t* s_mont, size_t n,
+                        uzk_g1_affine* a_out, uzk_g1_affine* c_out);
 
 /* ---- raw 9 x 29-bit limbs: the primitives of the hot loops (fp29.hpp) and the typed lazy operations (lz29.hpp) at their bounds ----
  * in: n records of four operands a, b, c, d, 9 limbs (uint32) each, taken EXACTLY as given; out: n x 9 words, the raw result (no

@@ -120,3 +120,46 @@ pub fn gpu_reveal_cards_with_snark<R: CryptoRng + RngCore>(
     }
     Some(out)
 }
+
+/// `gpu_reveal_cards_with_snark` with every proof as the contract takes it: the eight words a.x, a.y, b.x.c1, b.x.c0, b.y.c1, b.y.c0,
+/// c.x, c.y of `RevealedCardWithSnarkProof` (sdk.rs) as 0x-prefixed hex, cut from the blob the device encodes
+/// (`uzk_reveal_prove_snark_batch_finish`): no point is decoded or re-encoded here.
+pub fn gpu_reveal_cards_with_snark_hex<R: CryptoRng + RngCore>(
+    prng: &mut R,
+    circuit: &sys::RevealCircuit,
+    keypair: &Keypair,
+    masked_cards: &[MaskedCard],
+) -> Option<Vec<(RevealCard, [String; 8])>> {
+    if masked_cards.is_empty() {
+        return Some(Vec::new());
+    }
+    if masked_cards.len() > sys::UZK_REVEAL_CS_MAX_BATCH as usize {
+        return None;
+    }
+    let e1: Vec<sys::EdPoint> = masked_cards.iter().map(|c| point_to_wire(&c.e1)).collect();
+    let mut r = Vec::with_capacity(e1.len());
+    let mut s = Vec::with_capacity(e1.len());
+    for _ in 0..e1.len() {
+        r.push((ScalarFr::rand(prng).0).0);
+        s.push((ScalarFr::rand(prng).0).0);
+    }
+    let sk: Fr = keypair.secret;
+    let (statements, _, blobs) = circuit.prove_snark_finish(&sk.into_bigint().0, &e1, &r, &s).ok()?;
+    let per = sys::UZK_G16_PROOF_BYTES as usize;
+    let mut out = Vec::with_capacity(e1.len());
+    for (st, blob) in statements.iter().zip(blobs.chunks_exact(per)) {
+        if point_from_wire(&st[4], &st[5]) != keypair.public {
+            return None;                           // the keypair is not (sk, sk G): the caller's loop decides
+        }
+        let words: [String; 8] = std::array::from_fn(|k| {
+            let mut h = String::with_capacity(66);
+            h.push_str("0x");
+            for b in &blob[32 * k..32 * k + 32] {
+                h.push_str(&format!("{:02x}", b));
+            }
+            h
+        });
+        out.push((point_from_wire(&st[2], &st[3]), words));
+    }
+    Some(out)
+}

@@ -944,6 +944,58 @@ impl RevealCircuit {
         })?;
         Ok((statements, proofs))
     }
+    /// The same proofs finished and encoded on the device (`uzk_reveal_prove_snark_batch_finish`): per card the statement, the proof in
+    /// the struct layout and the `UZK_G16_PROOF_BYTES` blob `uzk_g16_verify_batch` reads (eight 32-byte big-endian words in the EVM
+    /// order), with no curve arithmetic on the host.
+    pub fn prove_snark_finish(&self, sk: &Limbs, e1: &[EdPoint], r: &[Limbs], s: &[Limbs]) -> Result<(Vec<RevealSnarkStatement>, Vec<uzk_g16_proof>, Vec<u8>), Error> {
+        let m = e1.len();
+        if m == 0 || m > UZK_REVEAL_CS_MAX_BATCH as usize || r.len() != m || s.len() != m {
+            return Err(Error::Parameter);
+        }
+        let mut statements = vec![[[0u64; 4]; 6]; m];
+        let mut proofs = vec![uzk_g16_proof::default(); m];
+        let mut blobs = vec![0u8; m * UZK_G16_PROOF_BYTES as usize];
+        check(unsafe {
+            uzk_reveal_prove_snark_batch_finish(self.handle, sk.as_ptr(), e1.as_ptr() as *const u64, r.as_ptr() as *const u64, s.as_ptr() as *const u64, m as u32,
+                                                statements.as_mut_ptr() as *mut u64, proofs.as_mut_ptr(), blobs.as_mut_ptr(), std::ptr::null_mut())
+        })?;
+        Ok((statements, proofs, blobs))
+    }
+    /// the inner key as a borrowed `Groth16Key`: it lives as long as the circuit
+    pub fn groth16_key(&self) -> Groth16Key<'_> {
+        Groth16Key { handle: self.key, _owner: std::marker::PhantomData }
+    }
+}
+
+/// A Groth16 proving key resident on the device, borrowed from the object that owns it (`RevealCircuit::groth16_key`).
+pub struct Groth16Key<'a> {
+    handle: u64,
+    _owner: std::marker::PhantomData<&'a RevealCircuit>,
+}
+impl<'a> Groth16Key<'a> {
+    pub fn handle(&self) -> u64 { self.handle }
+    /// (n_vars, n_inputs, n_constraints, domain) of the key (`uzk_g16_key_info`)
+    pub fn info(&self) -> Result<(u32, u32, u32, u64), Error> {
+        let (mut m, mut l, mut nc, mut n) = (0u32, 0u32, 0u32, 0u64);
+        check(unsafe { uzk_g16_key_info(self.handle, &mut m, &mut l, &mut nc, &mut n, std::ptr::null_mut()) })?;
+        Ok((m, l, nc, n))
+    }
+    /// `r.len()` proofs over host assignments `z` (`r.len()` x n_vars Montgomery elements, z[0] = 1 each), finished and encoded on the
+    /// device (`uzk_g16_prove_batch_finish`): the proofs in the struct layout and their `UZK_G16_PROOF_BYTES` blobs.
+    pub fn prove_finish(&self, z: &[Limbs], r: &[Limbs], s: &[Limbs]) -> Result<(Vec<uzk_g16_proof>, Vec<u8>), Error> {
+        let batch = r.len();
+        let (m, _, _, _) = self.info()?;
+        if batch == 0 || s.len() != batch || z.len() != batch * m as usize {
+            return Err(Error::Parameter);
+        }
+        let mut proofs = vec![uzk_g16_proof::default(); batch];
+        let mut blobs = vec![0u8; batch * UZK_G16_PROOF_BYTES as usize];
+        check(unsafe {
+            uzk_g16_prove_batch_finish(self.handle, z.as_ptr() as *const std::os::raw::c_void, 0, r.as_ptr() as *const u64, s.as_ptr() as *const u64, batch as u32,
+                                       proofs.as_mut_ptr(), blobs.as_mut_ptr(), std::ptr::null_mut())
+        })?;
+        Ok((proofs, blobs))
+    }
 }
 impl Drop for RevealCircuit {
     fn drop(&mut self) {

@@ -14,7 +14,12 @@ and 52 (the reveals of one deck):
               the scalar rows, and the finish (2 scalar multiplications and 2 additions per proof), which a host prover does with its own
               curve library.  This sequence is the yardstick.
 
-Both alternate in ONE process, warm-up first, the median of `--reps` repetitions.
+  finish      uzk_g16_prove_batch_finish on the same host assignments: the one call with B's Horner chain, C = s A + r B1 + K, the affine
+              maps and the blob encoding as kernels (finish="device").  Its column stands beside the one call's, with the spread
+              (min .. max) of both over the repetitions; its profiled call gives finish_device (the wall time of the upload of the
+              three G1 sums, g16_chains, g16_combine, g16_encode and the copies back) and the new kernels' device times.
+
+All three alternate in ONE process, warm-up first, the median of `--reps` repetitions.
 usage: python tools/g16_shape.py [--reps 7] [--out profiles/g16_shape.txt]"""
 import argparse, ctypes, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -95,17 +100,23 @@ def sequence(batch):
 STAGES = ("host_g16_h", "host_g16_msm_a", "host_g16_msm_b1", "host_g16_msm_k", "host_g16_msm_g2", "host_g16_finish")
 say(f"Groth16 prover at the real shape (l = {l}, m = {m}, {nc} constraints, n = {n}), host assignments, median of {a.reps} alternating "
     f"repetitions; {b.lib.uzk_version().decode()}")
-say(f"{'batch':>5} | {'one call ms':>11} {'sequence ms':>11} {'seq/one':>7} | one profiled call: stages (wall ms), then kernels inside (device ms)")
+say(f"{'batch':>5} | {'one call ms':>11} {'sequence ms':>11} {'seq/one':>7} | {'finish ms':>9} {'one/finish':>10} {'one min..max':>15} {'finish min..max':>15} | one profiled call: "
+    f"stages (wall ms), then kernels inside (device ms) ||| one profiled finish call: stages, then the finish kernels (device ms)")
+FIN_STAGES = STAGES[:-1] + ("host_g16_finish_device",)
+FIN_KERNELS = ("g2_horner", "g2_affine", "g16_chains", "g16_combine", "g16_encode")
 for batch in BATCHES:
     one_call = lambda: dk.prove(z_w[:batch], r_w[:batch], s_w[:batch])
+    fin_call = lambda: dk.prove(z_w[:batch], r_w[:batch], s_w[:batch], finish="device")
     proofs = one_call()
+    assert np.array_equal(fin_call()[0], proofs)                  # the two finishes give the same proofs
     ja, _, _, jb2, h_seq = sequence(batch)
     # the two paths compute the same A, B and h
     assert np.array_equal(b.g1_to_affine(ja[0]), proofs[0, 0:8]) and np.array_equal(b.g2_to_affine(jb2[0]), proofs[0, 8:24])
     assert np.array_equal(dk.h(z_w[:1])[0], h_seq[0])
-    t1, t2 = [], []
+    t1, t2, t3 = [], [], []
     for _ in range(a.reps):
         b.sync(); t = time.perf_counter(); one_call(); t1.append((time.perf_counter() - t) * 1e3)
+        b.sync(); t = time.perf_counter(); fin_call(); t3.append((time.perf_counter() - t) * 1e3)
         b.sync(); t = time.perf_counter(); sequence(batch); t2.append((time.perf_counter() - t) * 1e3)
     b.profile_reset(); b.profile_enable(True)
     one_call(); b.sync()
@@ -122,8 +133,15 @@ for batch in BATCHES:
         elif k == "host_g2_horner": grp["g2_host_horner"] += ms
         elif k.startswith("msm_"): grp["g1_msm_kernels"] += ms
         elif k == "host_msm_horner": grp["g1_host_horner"] += ms
-    m1, m2 = float(np.median(t1)), float(np.median(t2))
-    say(f"{batch:>5} | {m1:11.3f} {m2:11.3f} {m2 / m1:7.2f} | {stages} || " + " ".join(f"{k}={v:.3f}" for k, v in grp.items()))
+    b.profile_reset(); b.profile_enable(True)
+    fin_call(); b.sync()
+    b.profile_enable(False)
+    ftab = b.profile_table()
+    fstages = " ".join(f"{k.replace('host_g16_', '')}={ftab[k][1]:.3f}" for k in FIN_STAGES if k in ftab)
+    fkern = " ".join(f"{k}={ftab[k][1]:.3f}" for k in FIN_KERNELS if k in ftab)
+    m1, m2, m3 = float(np.median(t1)), float(np.median(t2)), float(np.median(t3))
+    say(f"{batch:>5} | {m1:11.3f} {m2:11.3f} {m2 / m1:7.2f} | {m3:9.3f} {m1 / m3:10.2f} {f'{min(t1):.2f}..{max(t1):.2f}':>15} {f'{min(t3):.2f}..{max(t3):.2f}':>15} | {stages} || "
+        + " ".join(f"{k}={v:.3f}" for k, v in grp.items()) + f" ||| {fstages} || {fkern}")
 dk.release(); srs_a.release(); srs_b.release(); srs_k.release(); g2_b.release()
 os.makedirs(os.path.dirname(a.out), exist_ok=True)
 open(a.out, "w").write("\n".join(lines) + "\n")

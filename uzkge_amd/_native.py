@@ -63,6 +63,7 @@ PROTOTYPES = {
     "uzk_msm_g2": (_I, [_U64, _SZ, _P, _SZ, _P]),
     "uzk_msm_g2_batch": (_I, [_U64, _SZ, _P, _SZ, ctypes.c_uint32, _P]),
     "uzk_msm_g2_batch_device": (_I, [_U64, _SZ, _P, _SZ, ctypes.c_uint32, _P]),
+    "uzk_msm_g2_batch_finish": (_I, [_U64, _SZ, _P, _SZ, ctypes.c_uint32, _P, _P]),
     "uzk_g2_fold": (_I, [_P, _SZ, _P]),
     "uzk_g2_to_affine": (_I, [_P, _P]),
     "uzk_g16_key_create": (_I, [_P, ctypes.POINTER(_U64)]),
@@ -72,6 +73,7 @@ PROTOTYPES = {
     "uzk_g16_h_device": (_I, [_U64, _P, ctypes.c_uint32, _P]),
     "uzk_g16_prove_batch": (_I, [_U64, _P, _P, _P, ctypes.c_uint32, _P]),
     "uzk_g16_prove_batch_device": (_I, [_U64, _P, _P, _P, ctypes.c_uint32, _P]),
+    "uzk_g16_prove_batch_finish": (_I, [_U64, _P, _I, _P, _P, ctypes.c_uint32, _P, _P, _P]),
     "uzk_domain_supported": (_I, [_U64]),
     "uzk_domain_group_gen": (_I, [_U64, _P]),
     "uzk_ntt_fr": (_I, [_P, _U64, _I, _P]),
@@ -158,6 +160,7 @@ PROTOTYPES = {
     "uzk_reveal_circuit_key": (_I, [_U64, ctypes.POINTER(_U64)]),
     "uzk_reveal_witness_batch": (_I, [_U64, _P, _P, ctypes.c_uint32, _P, _P]),
     "uzk_reveal_prove_snark_batch": (_I, [_U64, _P, _P, _P, _P, ctypes.c_uint32, _P, _P]),
+    "uzk_reveal_prove_snark_batch_finish": (_I, [_U64, _P, _P, _P, _P, ctypes.c_uint32, _P, _P, _P, _P]),
     "uzk_cp_mask_prove_batch": (_I, [_P, _P, _P, _P, ctypes.c_uint32, _P, _P, _P]),
     "uzk_cp_mask_verify_batch": (_I, [_P, _P, _P, _P, _P, ctypes.c_uint32, _P, _P]),
     "uzk_anemoi_permute_batch": (_I, [_P, _SZ, _P]),
@@ -201,6 +204,7 @@ TEST_PROTOTYPES = {
     "uzk_test_const_operands": (_I, [_I, _I, _I, _I, _I, _P, _P, _P, _SZ]),
     "uzk_test_g1_kat": (_I, [_I, _P, _P, _P, _SZ]),
     "uzk_test_g2_kat": (_I, [_I, _P, _P, _P, _SZ]),
+    "uzk_test_g16_finish": (_I, [_P, _P, _P, _P, _P, _SZ, _P, _P]),
     "uzk_test_circuit_truncate_t": (_I, [_U64, _I]),
     "uzk_test_shuffle_cs_tables": (_I, [_U64, _U64, _P, _P, _P]),
     "uzk_test_match_cs_tables": (_I, [_U64, _P, _P, _P]),

@@ -303,6 +303,16 @@ def msm_g2_batch_device(bases: G2Bases, d_scalars: int, n: int, batch: int, offs
     return out
 
 
+def g2_msm_finish(bases: G2Bases, d_scalars: int, n: int, batch: int, offset: int = 0, d_out: int = 0, host: bool = True):
+    """uzk_msm_g2_batch_finish: the sums of msm_g2_batch_device as canonical affine points [batch, 16] (infinity = zeros), combined
+    and mapped to affine on the device.  d_out: a device address that also receives them (batch x 128 bytes); host=False: d_out alone,
+    returns None."""
+    out = np.zeros((max(batch, 1), 16), dtype=np.uint64) if host else None
+    check(lib.uzk_msm_g2_batch_finish(bases.handle, offset, ctypes.c_void_p(d_scalars), n, batch, _ptr(out) if host else None,
+                                      ctypes.c_void_p(d_out) if d_out else None))
+    return out[:batch] if host else None
+
+
 def g2_fold(partials: np.ndarray) -> np.ndarray:
     p = np.ascontiguousarray(partials, dtype=np.uint64).reshape(-1, 24)
     out = np.zeros(24, dtype=np.uint64)
@@ -385,21 +395,41 @@ class Groth16Key:
             dev_free(d_z)
             dev_free(d_h)
 
-    def prove(self, z: np.ndarray, r: np.ndarray, s: np.ndarray) -> np.ndarray:
-        """z [batch, n_vars, 4], r and s [batch, 4] -> proofs [batch, 32]: A (8 words), B (16), C (8), affine, infinity = zeros"""
+    def _prove_finish(self, z, on_device: bool, r: np.ndarray, s: np.ndarray, d_blobs: int):
+        """uzk_g16_prove_batch_finish -> (proofs [batch, 32], blobs [batch, 256] bytes)"""
+        batch = r.shape[0]
+        proofs = np.zeros((max(batch, 1), 32), dtype=np.uint64)
+        blobs = np.zeros((max(batch, 1), N.G16_PROOF_BYTES), dtype=np.uint8)
+        check(lib.uzk_g16_prove_batch_finish(self.handle, z, int(on_device), _ptr(r) if r.size else None, _ptr(s) if s.size else None, batch, _ptr(proofs),
+                                             blobs.ctypes.data_as(ctypes.c_void_p), ctypes.c_void_p(d_blobs) if d_blobs else None))
+        return proofs[:batch], blobs[:batch]
+
+    def prove(self, z: np.ndarray, r: np.ndarray, s: np.ndarray, finish: str = "host", d_blobs: int = 0):
+        """z [batch, n_vars, 4], r and s [batch, 4] -> proofs [batch, 32]: A (8 words), B (16), C (8), affine, infinity = zeros.
+        finish="device": C, the affine maps and the encoding run on the device (uzk_g16_prove_batch_finish); returns (proofs, blobs) with
+        blobs [batch, 256] bytes as Groth16VerifierKey.verify_batch reads them, also left at the device address d_blobs when given."""
+        if finish not in ("host", "device"):
+            raise ValueError("finish is 'host' or 'device'")
         z = np.ascontiguousarray(z, dtype=np.uint64).reshape(-1, self.n_vars, 4)
         r = np.ascontiguousarray(r, dtype=np.uint64).reshape(-1, 4)
         s = np.ascontiguousarray(s, dtype=np.uint64).reshape(-1, 4)
         assert r.shape[0] == z.shape[0] and s.shape[0] == z.shape[0]
+        if finish == "device":
+            return self._prove_finish(_ptr(z) if z.size else None, False, r, s, d_blobs)
         out = np.zeros((z.shape[0], 32), dtype=np.uint64)
         check(lib.uzk_g16_prove_batch(self.handle, _ptr(z) if z.size else None, _ptr(r) if r.size else None, _ptr(s) if s.size else None,
                                       z.shape[0], _ptr(out)))
         return out
 
-    def prove_device(self, d_z: int, r: np.ndarray, s: np.ndarray) -> np.ndarray:
+    def prove_device(self, d_z: int, r: np.ndarray, s: np.ndarray, finish: str = "host", d_blobs: int = 0):
+        """`prove` over assignments at the device address d_z"""
+        if finish not in ("host", "device"):
+            raise ValueError("finish is 'host' or 'device'")
         r = np.ascontiguousarray(r, dtype=np.uint64).reshape(-1, 4)
         s = np.ascontiguousarray(s, dtype=np.uint64).reshape(-1, 4)
         assert r.shape[0] == s.shape[0]
+        if finish == "device":
+            return self._prove_finish(ctypes.c_void_p(d_z), True, r, s, d_blobs)
         out = np.zeros((r.shape[0], 32), dtype=np.uint64)
         check(lib.uzk_g16_prove_batch_device(self.handle, ctypes.c_void_p(d_z), _ptr(r) if r.size else None, _ptr(s) if s.size else None,
                                              r.shape[0], _ptr(out)))
@@ -1177,6 +1207,21 @@ class RevealCircuit:
         check(lib.uzk_reveal_prove_snark_batch(self.handle, _ptr(sk), _ptr(e1) if m else None, _ptr(r) if m else None, _ptr(s) if m else None, m, _ptr(st),
                                                _ptr(out)))
         return st[:m], out[:m]
+
+    def prove_snark_batch_finish(self, sk, e1, r, s, d_blobs: int = 0):
+        """uzk_reveal_prove_snark_batch_finish: as prove_snark_batch with the proofs finished and encoded on the device.  Returns
+        (statements [m, 6, 4], proofs [m, 32], blobs [m, 256] bytes); the blobs are also left at the device address d_blobs when given."""
+        sk = np.ascontiguousarray(sk, dtype=np.uint64).reshape(4)
+        e1 = np.ascontiguousarray(e1, dtype=np.uint64).reshape(-1, 8)
+        r = np.ascontiguousarray(r, dtype=np.uint64).reshape(-1, 4)
+        s = np.ascontiguousarray(s, dtype=np.uint64).reshape(-1, 4)
+        m = e1.shape[0]
+        assert r.shape[0] == m and s.shape[0] == m, "one pair of blinds per card"
+        st, out = np.zeros((max(m, 1), 6, 4), dtype=np.uint64), np.zeros((max(m, 1), 32), dtype=np.uint64)
+        blobs = np.zeros((max(m, 1), N.G16_PROOF_BYTES), dtype=np.uint8)
+        check(lib.uzk_reveal_prove_snark_batch_finish(self.handle, _ptr(sk), _ptr(e1) if m else None, _ptr(r) if m else None, _ptr(s) if m else None, m,
+                                                      _ptr(st), _ptr(out), blobs.ctypes.data_as(ctypes.c_void_p), ctypes.c_void_p(d_blobs) if d_blobs else None))
+        return st[:m], out[:m], blobs[:m]
 
     def release(self) -> None:
         if self.handle:

@@ -952,6 +952,20 @@ int uzk_msm_g2_batch_device(uint64_t handle, size_t offset, const void* d_scalar
     return g2_msm_run(ctx(), pts + offset, static_cast<const Fp*>(d_scalars_mont), n, batch, reinterpret_cast<G2Jac*>(out));
 } catch (...) { return uzk::on_exception("uzk_msm_g2_batch_device"); }
 
+int uzk_msm_g2_batch_finish(uint64_t handle, size_t offset, const void* d_scalars_mont, size_t n, uint32_t batch, uzk_g2_affine* out, void* d_out) try {
+    API_LOCK;
+    if (!out && !d_out) { set_error("uzk_msm_g2_batch_finish: no output asked for"); return UZK_ERR_PARAMETER; }
+    if (batch > 0 && n > 0 && !d_scalars_mont) { set_error("uzk_msm_g2_batch_finish: null pointer"); return UZK_ERR_PARAMETER; }
+    if (!g2_lookup(handle, nullptr, nullptr, nullptr)) { set_error("uzk_msm_g2_batch_finish: unknown G2 handle %llu", (unsigned long long)handle); return UZK_ERR_PARAMETER; }
+    UZK_TRY(require_ready());
+    const G2Affine* pts = nullptr;
+    UZK_TRY(g2_checked("uzk_msm_g2_batch_finish", handle, offset, n, &pts));
+    Ctx& c = ctx();
+    UZK_TRY(g2_msm_finish_run(c, pts + offset, static_cast<const Fp*>(d_scalars_mont), n, batch, reinterpret_cast<G2Affine*>(out), static_cast<G2Affine*>(d_out)));
+    UZK_HIP(hipStreamSynchronize(c.stream));          // d_out is complete when the call returns
+    return UZK_OK;
+} catch (...) { return uzk::on_exception("uzk_msm_g2_batch_finish"); }
+
 int uzk_msm_g2_batch(uint64_t handle, size_t offset, const uint64_t* scalars_mont, size_t n, uint32_t batch, uzk_g2_jac* out) try {
     API_LOCK;
     if (batch > 0 && (!out || (n > 0 && !scalars_mont))) { set_error("uzk_msm_g2_batch: null pointer"); return UZK_ERR_PARAMETER; }
@@ -1025,9 +1039,10 @@ int uzk_g16_h_device(uint64_t key, const void* d_z, uint32_t batch, void* d_h) t
     return g16_h_run(ctx(), key, static_cast<const Fp*>(d_z), batch, static_cast<Fp*>(d_h));
 } catch (...) { return uzk::on_exception("uzk_g16_h_device"); }
 
-static int g16_prove_common(const char* who, uint64_t key, const void* z, bool on_device, const uint64_t* r, const uint64_t* s, uint32_t batch, uzk_g16_proof* out) {
+// the checks of every prover entry; the outputs are the caller's to check
+static int g16_prove_checked(const char* who, uint64_t key, const void* z, bool on_device, const uint64_t* r, const uint64_t* s, uint32_t batch) {
     if (batch == 0) { set_error("%s: batch is 0", who); return UZK_ERR_PARAMETER; }
-    if (!z || !r || !s || !out) { set_error("%s: null pointer", who); return UZK_ERR_PARAMETER; }
+    if (!z || !r || !s) { set_error("%s: null pointer", who); return UZK_ERR_PARAMETER; }
     uint32_t m = 0;
     if (!g16_key_known(key, &m, nullptr, nullptr, nullptr, nullptr)) { set_error("%s: unknown key handle %llu", who, (unsigned long long)key); return UZK_ERR_PARAMETER; }
     if (!on_device) {
@@ -1035,7 +1050,11 @@ static int g16_prove_common(const char* who, uint64_t key, const void* z, bool o
         for (uint32_t b = 0; b < batch; ++b)
             if (std::memcmp(static_cast<const Fp*>(z) + (size_t)b * m, &one, sizeof one) != 0) { set_error("%s: assignment %u does not start with the constant one", who, b); return UZK_ERR_PARAMETER; }
     }
-    UZK_TRY(g16_checked(who, key));
+    return g16_checked(who, key);
+}
+static int g16_prove_common(const char* who, uint64_t key, const void* z, bool on_device, const uint64_t* r, const uint64_t* s, uint32_t batch, uzk_g16_proof* out) {
+    if (batch > 0 && !out) { set_error("%s: null pointer", who); return UZK_ERR_PARAMETER; }
+    UZK_TRY(g16_prove_checked(who, key, z, on_device, r, s, batch));
     return g16_prove_run(ctx(), key, static_cast<const Fp*>(z), on_device, as_fp(r), as_fp(s), batch, out);
 }
 int uzk_g16_prove_batch(uint64_t key, const uint64_t* z_mont, const uint64_t* r_mont, const uint64_t* s_mont, uint32_t batch, uzk_g16_proof* out) try {
@@ -1046,6 +1065,15 @@ int uzk_g16_prove_batch_device(uint64_t key, const void* d_z_mont, const uint64_
     API_LOCK;
     return g16_prove_common("uzk_g16_prove_batch_device", key, d_z_mont, true, r_mont, s_mont, batch, out);
 } catch (...) { return uzk::on_exception("uzk_g16_prove_batch_device"); }
+int uzk_g16_prove_batch_finish(uint64_t key, const void* z_mont, int z_on_device, const uint64_t* r_mont, const uint64_t* s_mont, uint32_t batch,
+                               uzk_g16_proof* proofs_out, uint8_t* blobs_out, void* d_blobs_out) try {
+    static const char* who = "uzk_g16_prove_batch_finish";
+    API_LOCK;
+    if (!proofs_out && !blobs_out && !d_blobs_out) { set_error("%s: no output asked for", who); return UZK_ERR_PARAMETER; }
+    UZK_TRY(g16_prove_checked(who, key, z_mont, z_on_device != 0, r_mont, s_mont, batch));
+    return g16_prove_finish_run(ctx(), key, static_cast<const Fp*>(z_mont), z_on_device != 0, as_fp(r_mont), as_fp(s_mont), batch, proofs_out, blobs_out,
+                                static_cast<uint8_t*>(d_blobs_out));
+} catch (...) { return uzk::on_exception("uzk_g16_prove_batch_finish"); }
 
 /* ---- NTT ---------------------------------------------------------------------------------- */
 int uzk_domain_supported(uint64_t n) try { return domain_supported(n) ? 1 : 0; } catch (...) { return uzk::on_exception("uzk_domain_supported"); }
@@ -1694,6 +1722,11 @@ int uzk_reveal_prove_snark_batch(uint64_t circuit, const uint64_t* sk, const uin
     return rcs_prove_snark_batch(circuit, sk, e1_mont, r_mont, s_mont, m, statements_out, proofs_out);
 } catch (...) { return uzk::on_exception("uzk_reveal_prove_snark_batch"); }
 
+int uzk_reveal_prove_snark_batch_finish(uint64_t circuit, const uint64_t* sk, const uint64_t* e1_mont, const uint64_t* r_mont, const uint64_t* s_mont, uint32_t m,
+                                        uint64_t* statements_out, uzk_g16_proof* proofs_out, uint8_t* blobs_out, void* d_blobs_out) try {
+    return rcs_prove_snark_batch_finish(circuit, sk, e1_mont, r_mont, s_mont, m, statements_out, proofs_out, blobs_out, d_blobs_out);
+} catch (...) { return uzk::on_exception("uzk_reveal_prove_snark_batch_finish"); }
+
 /* ---- the point codec ------------------------------------------------------------------------------ */
 static int codec_batch_args(const char* who, const void* in, size_t n, const void* out, const void* status) {
     if (n == 0 || n > UZK_CODEC_MAX_BATCH) { set_error("%s: %zu points (1 .. %d per call)", who, n, UZK_CODEC_MAX_BATCH); return UZK_ERR_PARAMETER; }
@@ -2165,6 +2198,17 @@ int uzk_test_g1_kat(int op, const uzk_g1_affine* a, const uzk_g1_affine* b, uzk_
     return g1_op_device(ctx(), op, reinterpret_cast<const Affine*>(a), reinterpret_cast<const Affine*>(b),
                         reinterpret_cast<Jac*>(out), n);
 } catch (...) { return uzk::on_exception("uzk_test_g1_kat"); }
+
+int uzk_test_g16_finish(const uzk_g1_jac* a_jac, const uzk_g1_jac* b1_jac, const uzk_g1_jac* k_jac, const uint64_t* r_mont, const uint64_t* s_mont, size_t n,
+                        uzk_g1_affine* a_out, uzk_g1_affine* c_out) try {
+    API_LOCK;
+    if (n == 0) return UZK_OK;
+    if (!a_jac || !b1_jac || !k_jac || !r_mont || !s_mont || !a_out || !c_out) { set_error("uzk_test_g16_finish: null pointer"); return UZK_ERR_PARAMETER; }
+    if (n > 4096) { set_error("uzk_test_g16_finish: more than 4096 records"); return UZK_ERR_PARAMETER; }
+    UZK_TRY(require_ready());
+    return g16_finish_test_run(ctx(), reinterpret_cast<const Jac*>(a_jac), reinterpret_cast<const Jac*>(b1_jac), reinterpret_cast<const Jac*>(k_jac), as_fp(r_mont),
+                               as_fp(s_mont), (uint32_t)n, reinterpret_cast<Affine*>(a_out), reinterpret_cast<Affine*>(c_out));
+} catch (...) { return uzk::on_exception("uzk_test_g16_finish"); }
 
 int uzk_test_g2_kat(int op, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n) try {
     API_LOCK;

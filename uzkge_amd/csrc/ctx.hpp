@@ -311,6 +311,8 @@ bool g2_release(uint64_t handle);
 void g2_release_all();
 void g2_free(Ctx& c);
 int g2_msm_run(Ctx& c, const G2Affine* d_points, const Fp* d_scalars, size_t n, uint32_t batch, G2Jac* out_host);
+// the same sums finished on the device: canonical affine points (infinity all zeros) to out_host, to d_out, or to both
+int g2_msm_finish_run(Ctx& c, const G2Affine* d_points, const Fp* d_scalars, size_t n, uint32_t batch, G2Affine* out_host, G2Affine* d_out);
 void g2_fold_host(const G2Jac* partials, size_t count, G2Jac* out);
 void g2_to_affine_host(const G2Jac* p, G2Affine* out);
 int g2_op_device(Ctx& c, int op, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n);
@@ -324,6 +326,10 @@ void g16_release_all();
 void g16_free(Ctx& c);
 int g16_h_run(Ctx& c, uint64_t h, const Fp* d_z, uint32_t batch, Fp* d_h);
 int g16_prove_run(Ctx& c, uint64_t h, const Fp* z, bool z_on_device, const Fp* r_host, const Fp* s_host, uint32_t batch, uzk_g16_proof* out);
+// the same proofs with C, the affine maps and the verifier's blob computed on the device; any of the three outputs may be null but one
+int g16_prove_finish_run(Ctx& c, uint64_t h, const Fp* z, bool z_on_device, const Fp* r_host, const Fp* s_host, uint32_t batch, uzk_g16_proof* proofs_out,
+                         uint8_t* blobs_out, uint8_t* d_blobs_out);
+int g16_finish_test_run(Ctx& c, const Jac* a, const Jac* b1, const Jac* k, const Fp* r_host, const Fp* s_host, uint32_t n, Affine* a_out, Affine* c_out);
 // g16verify.hip: Groth16 verifying keys (process-wide handles) and the fold of a batch of proofs
 int g16v_key_check(const uzk_g16_vk_desc* d);
 int g16v_key_create(Ctx& c, const uzk_g16_vk_desc* d, uint64_t* out);
@@ -384,6 +390,8 @@ int rcs_circuit_key(uint64_t circuit, uint64_t* key_out);
 int rcs_witness_batch(uint64_t circuit, const uint64_t* sk, const uint64_t* e1_mont, uint32_t m, void* d_z, uint64_t* statements_out);
 int rcs_prove_snark_batch(uint64_t circuit, const uint64_t* sk, const uint64_t* e1_mont, const uint64_t* r_mont, const uint64_t* s_mont, uint32_t m,
                           uint64_t* statements_out, uzk_g16_proof* proofs_out);
+int rcs_prove_snark_batch_finish(uint64_t circuit, const uint64_t* sk, const uint64_t* e1_mont, const uint64_t* r_mont, const uint64_t* s_mont, uint32_t m,
+                                 uint64_t* statements_out, uzk_g16_proof* proofs_out, uint8_t* blobs_out, void* d_blobs_out);
 int remark_tables_run(Ctx& c, uint64_t h, Fp* pk_tables_out, Fp* gen_tables_out);
 int remark_run(Ctx& c, uint64_t h, const EdAffine* e1, const EdAffine* e2, const uint8_t* digits, const uint32_t* slot, uint32_t n, EdAffine* e1_out,
                EdAffine* e2_out, Fp* trace_out);

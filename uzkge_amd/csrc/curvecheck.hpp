@@ -1,5 +1,6 @@
 // The point checks that the Groth16 fold (g16verify.hip) and the pairing product (pairing.hip) share: a coordinate against its modulus,
-// a G1 point on y^2 = x^3 + 3, a G2 point on the twist y^2 = x^3 + 3 / (9 + u).  Infinity (all zeros) is the caller's case.
+// a G1 point on y^2 = x^3 + 3, a G2 point on the twist y^2 = x^3 + 3 / (9 + u).  Infinity (all zeros) is the caller's case.  And the Fq
+// inversion of the affine maps that run in a lane (g16verify.hip, groth16.hip, g2msm.hip).
 #pragma once
 #include "ec.hpp"
 #include "g2_29.hpp"
@@ -17,6 +18,18 @@ UZK_HD bool gv_g1_on_curve(const Affine& p) {
     const Fp one = Fq::one();
     const Fp three = Fq::add(Fq::add(one, one), one);
     return Fq::eq(Fq::sqr(p.y), Fq::add(Fq::mul(Fq::sqr(p.x), p.x), three));
+}
+
+__device__ inline Fp gv_fq_inv(const Fp& a) {                     // a^(p - 2)
+    Fp e = Fq::modulus();
+    e.v[0] -= 2;                                                   // the low word of p ends in ...fd47
+    Fp acc = Fq::one();
+#pragma unroll 1
+    for (int i = 253; i >= 0; --i) {
+        acc = Fq::sqr(acc);
+        if ((e.v[i >> 5] >> (i & 31)) & 1) acc = Fq::mul(acc, a);
+    }
+    return acc;
 }
 
 #if defined(__HIP_DEVICE_COMPILE__)

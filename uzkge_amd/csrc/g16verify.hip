@@ -124,18 +124,6 @@ __global__ __launch_bounds__(256) void g16v_reduce_kernel(const Fp* __restrict__
 }
 
 // ---- rho_i A_i and t_0 alpha as canonical affine points ------------------------------------------------------------------------------
-__device__ inline Fp gv_fq_inv(const Fp& a) {                     // a^(p - 2)
-    Fp e = Fq::modulus();
-    e.v[0] -= 2;                                                   // the low word of p ends in ...fd47
-    Fp acc = Fq::one();
-#pragma unroll 1
-    for (int i = 253; i >= 0; --i) {
-        acc = Fq::sqr(acc);
-        if ((e.v[i >> 5] >> (i & 31)) & 1) acc = Fq::mul(acc, a);
-    }
-    return acc;
-}
-
 __global__ __launch_bounds__(kGvBlock) void g16v_amul_kernel(const Affine* __restrict__ pa, const Fp* __restrict__ wm, const Fp* __restrict__ t, Affine alpha,
                                                               Affine* __restrict__ out, uint32_t m) {
     const uint32_t i = blockIdx.x * kGvBlock + threadIdx.x;

@@ -12,10 +12,17 @@
 //   g2_windows     one lane per (vector, window): the 16 segment sums
 // and on the host the Horner combination of the 32 window sums per vector (host_g2.hpp).  Longer inputs run as point chunks of
 // 2^15 whose window sums are added on the host before the one Horner chain.
+//
+// uzk_msm_g2_batch_finish ends on the device instead (the same pass, then):
+//   g2_chunk_sum   n > 2^15 only, one lane per window: a vector's window sums += those of the chunk just run
+//   g2_horner      one lane per vector: total = sum_w 256^w S_w from the top window down, 31 x 8 doublings and 32 general additions
+//                  (a window sum can equal or negate the running total: the addition falls through to the doubling, or to infinity)
+//   g2_affine      one lane per vector: (X / ZZ, Y / ZZZ) by one inversion in Fq2, conj / norm over one Fq inversion chain
 #include <algorithm>
 #include <cstring>
 
 #include "ctx.hpp"
+#include "curvecheck.hpp"
 #include "g2_29.hpp"
 #include "handles.hpp"
 #include "host_g2.hpp"
@@ -35,6 +42,7 @@ constexpr uint32_t task_cap(uint32_t n) { return kBuckets + n / kTaskLen + 1; }
 
 struct G2Work {
     DevBuf digits, sorted, tstart, tasks, tpart, segs, wsum;
+    DevBuf csum, total, aff;           // the device finish: a group's chunk-summed window sums, its Horner totals, its affine results
 };
 
 struct G2Entry {
@@ -166,6 +174,70 @@ __global__ __launch_bounds__(64) void g2_windows_kernel(const G2XYZZ* __restrict
     for (uint32_t s = 0; s < kSegs; ++s) g2p_add(acc, g2p_load(segs[(uint64_t)slot * kSegs + s]));
     wsum[slot] = g2p_store(acc);
 #endif
+}
+
+// ---- the finish on the device (uzk_msm_g2_batch_finish) ----------------------------------------------------------------------
+
+// csum[w] (+)= wsum[w] for the 32 windows of one vector: `first` starts the sum.  No barrier.
+__global__ __launch_bounds__(64) void g2_chunk_sum_kernel(const G2XYZZ* __restrict__ wsum, G2XYZZ* __restrict__ csum, uint32_t first) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    const uint32_t w = threadIdx.x;
+    if (w >= kW) return;
+    G2P acc = first ? g2p_inf() : g2p_load(csum[w]);
+    g2p_add(acc, g2p_load(wsum[w]));
+    csum[w] = g2p_store(acc);
+#endif
+}
+
+// One lane per vector: total[b] = sum_w 256^w sums[b * 32 + w].  The additions are the general ones: after eight doublings the running
+// total can be the next window's sum (doubling) or its negative (infinity), and it is infinite until the first nonzero window.
+__global__ __launch_bounds__(64) void g2_horner_kernel(const G2XYZZ* __restrict__ sums, G2XYZZ* __restrict__ total, uint32_t nb) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    const uint32_t b = blockIdx.x * 64 + threadIdx.x;
+    if (b >= nb) return;                                            // no barrier and no cross-lane move below
+    G2P acc = g2p_inf();
+#pragma unroll 1
+    for (int w = (int)kW - 1; w >= 0; --w) {
+        if (w != (int)kW - 1) {
+#pragma unroll 1
+            for (int d = 0; d < 8; ++d) g2p_dbl(acc);
+        }
+        g2p_add(acc, g2p_load(sums[(uint64_t)b * kW + w]));
+    }
+    total[b] = g2p_store(acc);
+#endif
+}
+
+// Fq2 on the wire words (canonical Montgomery, Fq's own product): the affine map runs once per vector, behind a chain of 280 group
+// operations, so it takes the plain field
+__device__ inline Fq2w g2w_mul(const Fq2w& a, const Fq2w& b) {
+    Fq2w r;
+    r.c0 = Fq::sub(Fq::mul(a.c0, b.c0), Fq::mul(a.c1, b.c1));
+    r.c1 = Fq::add(Fq::mul(a.c0, b.c1), Fq::mul(a.c1, b.c0));
+    return r;
+}
+// 1 / (a + b u) = (a - b u) / (a^2 + b^2); a + b u != 0 (-1 is no square in Fq: the norm of a nonzero element is nonzero)
+__device__ inline Fq2w g2w_inv(const Fq2w& a) {
+    const Fp ni = gv_fq_inv(Fq::add(Fq::sqr(a.c0), Fq::sqr(a.c1)));
+    Fq2w r;
+    r.c0 = Fq::mul(a.c0, ni);
+    r.c1 = Fq::neg(Fq::mul(a.c1, ni));
+    return r;
+}
+
+// One lane per point: wire XYZZ -> canonical affine (X / ZZ, Y / ZZZ) by one inversion of ZZ ZZZ; infinity (zz = 0) -> all zeros
+__global__ __launch_bounds__(64) void g2_affine_kernel(const G2XYZZ* __restrict__ in, G2Affine* __restrict__ out, uint32_t n) {
+    const uint32_t i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    const G2XYZZ p = in[i];
+    G2Affine r;
+    r.x.c0 = Fq::zero(); r.x.c1 = r.x.c0; r.y = r.x;
+    if (!(Fq::is_zero(p.zz.c0) && Fq::is_zero(p.zz.c1))) {
+        const Fq2w inv = g2w_inv(g2w_mul(p.zz, p.zzz));
+        r.x = g2w_mul(p.x, g2w_mul(inv, p.zzz));
+        r.y = g2w_mul(p.y, g2w_mul(inv, p.zz));
+    }
+    out[i] = r;
 }
 
 // The primitives element-wise (uzk_test_g2_kat).  Fq2 ops: a, b, out are Fq2w; group ops: a, b affine, out XYZZ.
@@ -300,7 +372,7 @@ static G2Work& work(Ctx& c) {
 void g2_free(Ctx& c) {
     if (!c.g2) return;
     G2Work* w = static_cast<G2Work*>(c.g2);
-    w->digits.release(); w->sorted.release(); w->tstart.release(); w->tasks.release(); w->tpart.release(); w->segs.release(); w->wsum.release();
+    w->digits.release(); w->sorted.release(); w->tstart.release(); w->tasks.release(); w->tpart.release(); w->segs.release(); w->wsum.release(); w->csum.release(); w->total.release(); w->aff.release();
     delete w;
     c.g2 = nullptr;
 }
@@ -342,8 +414,8 @@ bool g2_release(uint64_t handle) {
 }
 void g2_release_all() { g_reg.drain(g2_entry_free); }
 
-// window sums of `batch` vectors over n <= 2^15 points: out[b * 32 + w], wire XYZZ on the host
-static int g2_pass(Ctx& c, const G2Affine* d_points, const Fp* d_scalars, uint32_t n, uint32_t batch, G2XYZZ* out) {
+// window sums of `batch` vectors over n <= 2^15 points, left in the workspace: wsum[b * 32 + w], wire XYZZ; nothing is waited for
+static int g2_pass_launch(Ctx& c, const G2Affine* d_points, const Fp* d_scalars, uint32_t n, uint32_t batch) {
     G2Work& w = work(c);
     const uint32_t slots = batch * kW, cap = task_cap(n);
     UZK_TRY(w.digits.reserve((size_t)slots * n));
@@ -362,7 +434,13 @@ static int g2_pass(Ctx& c, const G2Affine* d_points, const Fp* d_scalars, uint32
     UZK_LAUNCH(c, "g2_segments", g2_segments_kernel, dim3((slots * kSegs + 63) / 64), dim3(64), 0, c.stream, w.tstart.as<uint32_t>(), w.tpart.as<G2XYZZ>(),
                w.segs.as<G2XYZZ>(), slots, cap);
     UZK_LAUNCH(c, "g2_windows", g2_windows_kernel, dim3((slots + 63) / 64), dim3(64), 0, c.stream, w.segs.as<G2XYZZ>(), w.wsum.as<G2XYZZ>(), slots);
-    UZK_HIP(hipMemcpyAsync(out, w.wsum.p, (size_t)slots * sizeof(G2XYZZ), hipMemcpyDeviceToHost, c.stream));
+    return UZK_OK;
+}
+
+// the same, copied to the host: out[b * 32 + w]
+static int g2_pass(Ctx& c, const G2Affine* d_points, const Fp* d_scalars, uint32_t n, uint32_t batch, G2XYZZ* out) {
+    UZK_TRY(g2_pass_launch(c, d_points, d_scalars, n, batch));
+    UZK_HIP(hipMemcpyAsync(out, work(c).wsum.p, (size_t)batch * kW * sizeof(G2XYZZ), hipMemcpyDeviceToHost, c.stream));
     UZK_HIP(hipStreamSynchronize(c.stream));
     return UZK_OK;
 }
@@ -401,6 +479,49 @@ int g2_msm_run(Ctx& c, const G2Affine* d_points, const Fp* d_scalars, size_t n, 
             out[b0 + b] = h64::j2_to(total);
         }
     }
+    return UZK_OK;
+}
+
+// The same sums as canonical affine points (infinity all zeros), finished on the device: to `out` (host), to `d_out` (device), or to
+// both; at least one of them.  The window sums never leave the device.  With d_out alone nothing is waited for.
+int g2_msm_finish_run(Ctx& c, const G2Affine* d_points, const Fp* d_scalars, size_t n, uint32_t batch, G2Affine* out, G2Affine* d_out) {
+    if (batch == 0) return UZK_OK;
+    if (n == 0) {
+        if (out) std::memset(out, 0, (size_t)batch * sizeof(G2Affine));
+        if (d_out) UZK_HIP(hipMemsetAsync(d_out, 0, (size_t)batch * sizeof(G2Affine), c.stream));
+        return UZK_OK;
+    }
+    G2Work& w = work(c);
+    const size_t chunk = (size_t)1 << kChunkLog;
+    for (uint32_t b0 = 0; b0 < batch; b0 += kGroup) {
+        const uint32_t nb = std::min(kGroup, batch - b0);
+        UZK_TRY(w.total.reserve((size_t)nb * sizeof(G2XYZZ)));
+        const G2XYZZ* sums = nullptr;
+        if (n <= chunk) {
+            UZK_TRY(g2_pass_launch(c, d_points, d_scalars + (size_t)b0 * n, (uint32_t)n, nb));
+            sums = w.wsum.as<G2XYZZ>();
+        } else {
+            // point chunks, each vector on its own (as g2_msm_run): its window sums gather in csum
+            UZK_TRY(w.csum.reserve((size_t)nb * kW * sizeof(G2XYZZ)));
+            for (uint32_t b = 0; b < nb; ++b)
+                for (size_t lo = 0; lo < n; lo += chunk) {
+                    const size_t len = std::min(chunk, n - lo);
+                    UZK_TRY(g2_pass_launch(c, d_points + lo, d_scalars + (size_t)(b0 + b) * n + lo, (uint32_t)len, 1));
+                    UZK_LAUNCH(c, "g2_chunk_sum", g2_chunk_sum_kernel, dim3(1), dim3(64), 0, c.stream, w.wsum.as<G2XYZZ>(), w.csum.as<G2XYZZ>() + (size_t)b * kW,
+                               lo == 0 ? 1u : 0u);
+                }
+            sums = w.csum.as<G2XYZZ>();
+        }
+        G2Affine* dst = d_out ? d_out + b0 : nullptr;
+        if (!dst) {
+            UZK_TRY(w.aff.reserve((size_t)nb * sizeof(G2Affine)));
+            dst = w.aff.as<G2Affine>();
+        }
+        UZK_LAUNCH(c, "g2_horner", g2_horner_kernel, dim3((nb + 63) / 64), dim3(64), 0, c.stream, sums, w.total.as<G2XYZZ>(), nb);
+        UZK_LAUNCH(c, "g2_affine", g2_affine_kernel, dim3((nb + 63) / 64), dim3(64), 0, c.stream, w.total.as<G2XYZZ>(), dst, nb);
+        if (out) UZK_HIP(hipMemcpyAsync(out + b0, dst, (size_t)nb * sizeof(G2Affine), hipMemcpyDeviceToHost, c.stream));
+    }
+    if (out) UZK_HIP(hipStreamSynchronize(c.stream));
     return UZK_OK;
 }
 

@@ -14,10 +14,13 @@
 //   g16_scalar_rows   the scalar vectors of the MSMs: the tail (1, r) of A, z || 1 || s for B in G1 and G2,
 //                     z[l ..] || h[0 .. n - 1) || -r s for K
 //   msm_dispatch_view (A, B1, K) and g2_msm_run (B), then on the host C = s A + r B1 + K and the affine maps.
+// uzk_g16_prove_batch_finish shares all of it up to the MSMs, lets the G2 MSM end on the device (g2_msm_finish_run), uploads the three
+// G1 sums and finishes there: g16_chains (s A, r B1), g16_combine (C and the affine maps), g16_encode (the verifier's blob).
 #include <algorithm>
 #include <cstring>
 
 #include "ctx.hpp"
+#include "curvecheck.hpp"
 #include "g2_29.hpp"
 #include "handles.hpp"
 #include "host_ec64.hpp"
@@ -29,6 +32,7 @@ namespace uzk {
 namespace {
 constexpr uint32_t kSlice = 32;                 // entries of a row one lane multiplies
 constexpr uint32_t kGroup = UZK_G16_GROUP;      // the G2 MSM's group: proofs of one launch sequence
+constexpr uint32_t kFinBlock = 64;               // lanes of a workgroup of the finish kernels
 constexpr uint64_t kGroupElems = 1ull << 21;    // domain points of one group at most (bounds the transform buffers: 3 x 64 MiB)
 
 struct Slice {
@@ -49,6 +53,7 @@ struct G16Key {
 
 struct G16Work {
     DevBuf z_in, zT, part, abc, tail_a, row_b, row_k, rs;
+    DevBuf fin_sums, fin_terms, fin_a, fin_b, fin_c, fin_proofs, fin_blobs, fin_test;     // the device finish
 };
 
 HandleTable<G16Key> g_reg(1ull << 58);
@@ -122,6 +127,66 @@ __global__ __launch_bounds__(256) void g16_scalar_rows_kernel(const Fp* __restri
     if (i < m - l) row_k[b * len_k + i] = z[(uint64_t)b * m + l + i];
     else if (i < len_k - 1) row_k[b * len_k + i] = h[(uint64_t)b * n + (i - (m - l))];
     else if (i == len_k - 1) row_k[b * len_k + i] = Fr::neg(Fr::mul(r, s));
+}
+
+// ---- the finish on the device: C = s A + r B1 + K, the affine maps, the blob ---------------------------------------------------------
+// One lane per (term, proof): lane t < nb is s_t A_t, lane nb + t is r_t B1_t, by double-and-add over the 254 bits of the canonical
+// scalar (g16v_amul's chain; the base is a Jacobian sum with Z != 1, so the addition is the full one).  No barrier.
+__global__ __launch_bounds__(kFinBlock) void g16_chains_kernel(const Jac* __restrict__ sums, const Fp* __restrict__ rs, XYZZ* __restrict__ terms, uint32_t nb) {
+    const uint32_t t = blockIdx.x * kFinBlock + threadIdx.x;
+    if (t >= 2 * nb) return;
+    const XYZZ p = xyzz_from_jac(sums[t]);                         // A then B1
+    const Fp s = Fr::from_mont(t < nb ? rs[nb + t] : rs[t - nb]);  // s for A, r for B1; canonical: below r < 2^254
+    XYZZ acc = xyzz_inf();
+#pragma unroll 1
+    for (int k = 253; k >= 0; --k) {
+        acc = xyzz_dbl(acc);
+        if ((s.v[k >> 5] >> (k & 31)) & 1) xyzz_add(acc, p);
+    }
+    terms[t] = acc;
+}
+
+__device__ inline Affine g16_affine_of(const XYZZ& p) {
+    Affine r;
+    r.x = Fq::zero(); r.y = r.x;
+    if (!xyzz_is_inf(p)) {
+        const Fp inv = gv_fq_inv(Fq::mul(p.zz, p.zzz));
+        r.x = Fq::mul(p.x, Fq::mul(inv, p.zzz));                   // X / ZZ
+        r.y = Fq::mul(p.y, Fq::mul(inv, p.zz));                    // Y / ZZZ
+    }
+    return r;
+}
+
+// One lane per (point, proof): lane t < nb writes the affine A_t; lane nb + t adds s A + r B1 + K by general additions (the two terms
+// can be equal or opposite, any operand and the sum itself can be infinite) and writes the affine C_t.  The inversion is in the lane.
+__global__ __launch_bounds__(kFinBlock) void g16_combine_kernel(const Jac* __restrict__ sums, const XYZZ* __restrict__ terms, Affine* __restrict__ a_out,
+                                                                 Affine* __restrict__ c_out, uint32_t nb) {
+    const uint32_t t = blockIdx.x * kFinBlock + threadIdx.x;
+    if (t >= 2 * nb) return;
+    if (t < nb) { a_out[t] = g16_affine_of(xyzz_from_jac(sums[t])); return; }
+    const uint32_t b = t - nb;
+    XYZZ acc = terms[b];
+    xyzz_add(acc, terms[nb + b]);
+    xyzz_add(acc, xyzz_from_jac(sums[2 * (size_t)nb + b]));
+    c_out[b] = g16_affine_of(acc);
+}
+
+// One lane per (proof, word): word t of the blob (a.x, a.y, b.x.c1, b.x.c0, b.y.c1, b.y.c0, c.x, c.y) as the canonical integer in 32
+// big-endian bytes, and the same element, in Montgomery form, at its place in the struct (where c0 comes before c1).
+__global__ __launch_bounds__(kFinBlock) void g16_encode_kernel(const Affine* __restrict__ pa, const G2Affine* __restrict__ pb, const Affine* __restrict__ pc,
+                                                                Fp* __restrict__ proofs, uint8_t* __restrict__ blobs, uint32_t nb) {
+    const uint32_t i = blockIdx.x * kFinBlock + threadIdx.x;
+    if (i >= 8 * nb) return;
+    const uint32_t b = i / 8, t = i % 8;
+    const uint32_t slot = (t >= 2 && t < 6) ? (t ^ 1u) : t;        // the struct's word: c0 first
+    const Fp v = slot < 2 ? reinterpret_cast<const Fp*>(pa)[(size_t)b * 2 + slot]
+               : slot < 6 ? reinterpret_cast<const Fp*>(pb)[(size_t)b * 4 + slot - 2]
+                          : reinterpret_cast<const Fp*>(pc)[(size_t)b * 2 + slot - 6];
+    proofs[(size_t)b * 8 + slot] = v;
+    const Fp e = Fq::from_mont(v);
+    uint32_t* dst = reinterpret_cast<uint32_t*>(blobs + (size_t)b * UZK_G16_PROOF_BYTES + 32 * t);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) dst[j] = __builtin_bswap32(e.v[7 - j]);
 }
 
 // ---- keys -------------------------------------------------------------------------------------------------------------------
@@ -261,6 +326,8 @@ void g16_free(Ctx& c) {
     if (!c.g16) return;
     G16Work* w = static_cast<G16Work*>(c.g16);
     w->z_in.release(); w->zT.release(); w->part.release(); w->abc.release(); w->tail_a.release(); w->row_b.release(); w->row_k.release(); w->rs.release();
+    w->fin_sums.release(); w->fin_terms.release(); w->fin_a.release(); w->fin_b.release(); w->fin_c.release(); w->fin_proofs.release(); w->fin_blobs.release();
+    w->fin_test.release();
     delete w;
     c.g16 = nullptr;
 }
@@ -313,58 +380,72 @@ static h64::J j_scalar_mul(const h64::J& p, const Fp& k_mont) {
     return acc;
 }
 
-int g16_prove_run(Ctx& c, uint64_t h, const Fp* z, bool z_on_device, const Fp* r_host, const Fp* s_host, uint32_t batch, uzk_g16_proof* out) {
-    G16Key k;
-    if (!key_lookup(h, &k)) { set_error("uzk_g16_prove_batch: unknown key handle %llu", (unsigned long long)h); return UZK_ERR_PARAMETER; }
+// Everything of a group up to and including the four MSMs, shared by the two finishes: proofs b0 .. b0 + nb of the call.  The G1 sums
+// come back to the host (msm.hip's own final fold); B goes to jb2 on the host (the window sums combined there) or, when jb2 is null,
+// to d_b2 on the device as canonical affine points (g2_msm_finish_run: nothing of B leaves the device).  w.rs holds r, then s.
+static int msm_group(Ctx& c, const G16Key& k, const Fp* z, bool z_on_device, const Fp* r_host, const Fp* s_host, uint32_t b0, uint32_t nb, Jac* ja, Jac* jb1,
+                     Jac* jk, G2Jac* jb2, G2Affine* d_b2) {
     G16Work& w = work(c);
-    const uint32_t group = group_of(k), m = k.m;
+    const uint32_t m = k.m;
     const uint64_t n = k.n, len_b = (uint64_t)m + 2, len_k = (uint64_t)(m - k.l) + n;
     Ctx::Srs ga, gb1, gk;
     ga.d_points = k.ga; ga.n = len_b; ga.device = k.device;
     gb1.d_points = k.gb1; gb1.n = len_b; gb1.device = k.device;
     gk.d_points = k.gk; gk.n = len_k; gk.device = k.device;
+    const Fp* d_z = z + (size_t)b0 * m;
+    if (!z_on_device) {
+        UZK_TRY(w.z_in.reserve((size_t)nb * m * sizeof(Fp)));
+        UZK_HIP(hipMemcpyAsync(w.z_in.p, z + (size_t)b0 * m, (size_t)nb * m * sizeof(Fp), hipMemcpyHostToDevice, c.stream));
+        d_z = w.z_in.as<Fp>();
+    }
+    UZK_TRY(w.rs.reserve((size_t)2 * group_of(k) * sizeof(Fp)));
+    UZK_HIP(hipMemcpyAsync(w.rs.p, r_host + b0, (size_t)nb * sizeof(Fp), hipMemcpyHostToDevice, c.stream));
+    UZK_HIP(hipMemcpyAsync(w.rs.as<Fp>() + nb, s_host + b0, (size_t)nb * sizeof(Fp), hipMemcpyHostToDevice, c.stream));
+    {
+        HostScope hs(c, "host_g16_h");
+        UZK_TRY(h_group(c, k, d_z, nb));
+        UZK_TRY(w.tail_a.reserve((size_t)2 * nb * sizeof(Fp)));
+        UZK_TRY(w.row_b.reserve((size_t)len_b * nb * sizeof(Fp)));
+        UZK_TRY(w.row_k.reserve((size_t)len_k * nb * sizeof(Fp)));
+        UZK_LAUNCH(c, "g16_scalar_rows", g16_scalar_rows_kernel, dim3(blocks(std::max(len_b, len_k)), nb), dim3(256), 0, c.stream, d_z, w.abc.as<Fp>(), w.rs.as<Fp>(),
+                   w.tail_a.as<Fp>(), w.row_b.as<Fp>(), w.row_k.as<Fp>(), m, k.l, n, nb);
+        if (c.prof_on) UZK_HIP(hipStreamSynchronize(c.stream));     // so that the stage timers below hold one stage each
+    }
+    {
+        HostScope hs(c, "host_g16_msm_a");
+        ScalarView sv;                                              // z where it lies, the tail (1, r) behind it
+        sv.main = d_z; sv.stride = m; sv.n_main = m;
+        sv.tail = w.tail_a.as<Fp>(); sv.tail_n = 2;
+        UZK_TRY(msm_dispatch_view(ga, 0, sv, len_b, nb, ja));
+    }
+    {
+        HostScope hs(c, "host_g16_msm_b1");
+        UZK_TRY(msm_dispatch_view(gb1, 0, ScalarView::dense(w.row_b.as<Fp>(), len_b), len_b, nb, jb1));
+    }
+    {
+        HostScope hs(c, "host_g16_msm_k");
+        UZK_TRY(msm_dispatch_view(gk, 0, ScalarView::dense(w.row_k.as<Fp>(), len_k), len_k, nb, jk));
+    }
+    {
+        HostScope hs(c, "host_g16_msm_g2");
+        if (jb2) UZK_TRY(g2_msm_run(c, k.gb2, w.row_b.as<Fp>(), len_b, nb, jb2));
+        else {
+            UZK_TRY(g2_msm_finish_run(c, k.gb2, w.row_b.as<Fp>(), len_b, nb, nullptr, d_b2));
+            if (c.prof_on) UZK_HIP(hipStreamSynchronize(c.stream)); // the stage ends with its kernels
+        }
+    }
+    return UZK_OK;
+}
+
+int g16_prove_run(Ctx& c, uint64_t h, const Fp* z, bool z_on_device, const Fp* r_host, const Fp* s_host, uint32_t batch, uzk_g16_proof* out) {
+    G16Key k;
+    if (!key_lookup(h, &k)) { set_error("uzk_g16_prove_batch: unknown key handle %llu", (unsigned long long)h); return UZK_ERR_PARAMETER; }
+    const uint32_t group = group_of(k);
     std::vector<Jac> ja(group), jb1(group), jk(group);
     std::vector<G2Jac> jb2(group);
     for (uint32_t b0 = 0; b0 < batch; b0 += group) {
         const uint32_t nb = std::min(group, batch - b0);
-        const Fp* d_z = z + (size_t)b0 * m;
-        if (!z_on_device) {
-            UZK_TRY(w.z_in.reserve((size_t)nb * m * sizeof(Fp)));
-            UZK_HIP(hipMemcpyAsync(w.z_in.p, z + (size_t)b0 * m, (size_t)nb * m * sizeof(Fp), hipMemcpyHostToDevice, c.stream));
-            d_z = w.z_in.as<Fp>();
-        }
-        UZK_TRY(w.rs.reserve((size_t)2 * group * sizeof(Fp)));
-        UZK_HIP(hipMemcpyAsync(w.rs.p, r_host + b0, (size_t)nb * sizeof(Fp), hipMemcpyHostToDevice, c.stream));
-        UZK_HIP(hipMemcpyAsync(w.rs.as<Fp>() + nb, s_host + b0, (size_t)nb * sizeof(Fp), hipMemcpyHostToDevice, c.stream));
-        {
-            HostScope hs(c, "host_g16_h");
-            UZK_TRY(h_group(c, k, d_z, nb));
-            UZK_TRY(w.tail_a.reserve((size_t)2 * nb * sizeof(Fp)));
-            UZK_TRY(w.row_b.reserve((size_t)len_b * nb * sizeof(Fp)));
-            UZK_TRY(w.row_k.reserve((size_t)len_k * nb * sizeof(Fp)));
-            UZK_LAUNCH(c, "g16_scalar_rows", g16_scalar_rows_kernel, dim3(blocks(std::max(len_b, len_k)), nb), dim3(256), 0, c.stream, d_z, w.abc.as<Fp>(), w.rs.as<Fp>(),
-                       w.tail_a.as<Fp>(), w.row_b.as<Fp>(), w.row_k.as<Fp>(), m, k.l, n, nb);
-            if (c.prof_on) UZK_HIP(hipStreamSynchronize(c.stream));     // so that the stage timers below hold one stage each
-        }
-        {
-            HostScope hs(c, "host_g16_msm_a");
-            ScalarView sv;                                              // z where it lies, the tail (1, r) behind it
-            sv.main = d_z; sv.stride = m; sv.n_main = m;
-            sv.tail = w.tail_a.as<Fp>(); sv.tail_n = 2;
-            UZK_TRY(msm_dispatch_view(ga, 0, sv, len_b, nb, ja.data()));
-        }
-        {
-            HostScope hs(c, "host_g16_msm_b1");
-            UZK_TRY(msm_dispatch_view(gb1, 0, ScalarView::dense(w.row_b.as<Fp>(), len_b), len_b, nb, jb1.data()));
-        }
-        {
-            HostScope hs(c, "host_g16_msm_k");
-            UZK_TRY(msm_dispatch_view(gk, 0, ScalarView::dense(w.row_k.as<Fp>(), len_k), len_k, nb, jk.data()));
-        }
-        {
-            HostScope hs(c, "host_g16_msm_g2");
-            UZK_TRY(g2_msm_run(c, k.gb2, w.row_b.as<Fp>(), len_b, nb, jb2.data()));
-        }
+        UZK_TRY(msm_group(c, k, z, z_on_device, r_host, s_host, b0, nb, ja.data(), jb1.data(), jk.data(), jb2.data(), nullptr));
         HostScope hs(c, "host_g16_finish");
         for (uint32_t b = 0; b < nb; ++b) {
             const h64::J A = h64::j_from(ja[b]), B1 = h64::j_from(jb1[b]);
@@ -377,6 +458,73 @@ int g16_prove_run(Ctx& c, uint64_t h, const Fp* z, bool z_on_device, const Fp* r
             std::memcpy(&p.c, &cc, sizeof cc);
         }
     }
+    return UZK_OK;
+}
+
+// ---- the finish on the device ---------------------------------------------------------------------------------------------------
+// The three G1 sums of nb proofs lie in d_sums as A[nb], B1[nb], K[nb] (Jacobian, as msm.hip returns them), r then s in d_rs:
+//   g16_chains   2 nb lanes -> terms[0 .. nb) = s A, terms[nb .. 2 nb) = r B1
+//   g16_combine  2 nb lanes -> d_a[b] = affine A, d_c[b] = affine (s A + r B1 + K)
+static int finish_launch(Ctx& c, const Jac* d_sums, const Fp* d_rs, XYZZ* d_terms, uint32_t nb, Affine* d_a, Affine* d_c) {
+    const unsigned grid = (2 * nb + kFinBlock - 1) / kFinBlock;
+    UZK_LAUNCH(c, "g16_chains", g16_chains_kernel, dim3(grid), dim3(kFinBlock), 0, c.stream, d_sums, d_rs, d_terms, nb);
+    UZK_LAUNCH(c, "g16_combine", g16_combine_kernel, dim3(grid), dim3(kFinBlock), 0, c.stream, d_sums, d_terms, d_a, d_c, nb);
+    return UZK_OK;
+}
+
+// proofs_out (host, the struct layout), blobs_out (host) and d_blobs_out (device): UZK_G16_PROOF_BYTES per proof; at least one of them
+int g16_prove_finish_run(Ctx& c, uint64_t h, const Fp* z, bool z_on_device, const Fp* r_host, const Fp* s_host, uint32_t batch, uzk_g16_proof* proofs_out,
+                         uint8_t* blobs_out, uint8_t* d_blobs_out) {
+    G16Key k;
+    if (!key_lookup(h, &k)) { set_error("uzk_g16_prove_batch_finish: unknown key handle %llu", (unsigned long long)h); return UZK_ERR_PARAMETER; }
+    G16Work& w = work(c);
+    const uint32_t group = group_of(k);
+    std::vector<Jac> sums((size_t)3 * group);
+    UZK_TRY(w.fin_sums.reserve((size_t)3 * group * sizeof(Jac)));
+    UZK_TRY(w.fin_terms.reserve((size_t)2 * group * sizeof(XYZZ)));
+    UZK_TRY(w.fin_a.reserve((size_t)group * sizeof(Affine)));
+    UZK_TRY(w.fin_b.reserve((size_t)group * sizeof(G2Affine)));
+    UZK_TRY(w.fin_c.reserve((size_t)group * sizeof(Affine)));
+    UZK_TRY(w.fin_proofs.reserve((size_t)group * sizeof(uzk_g16_proof)));
+    if (!d_blobs_out) UZK_TRY(w.fin_blobs.reserve((size_t)group * UZK_G16_PROOF_BYTES));
+    for (uint32_t b0 = 0; b0 < batch; b0 += group) {
+        const uint32_t nb = std::min(group, batch - b0);
+        Jac *ja = sums.data(), *jb1 = ja + nb, *jk = jb1 + nb;
+        UZK_TRY(msm_group(c, k, z, z_on_device, r_host, s_host, b0, nb, ja, jb1, jk, nullptr, w.fin_b.as<G2Affine>()));
+        HostScope hs(c, "host_g16_finish_device");
+        UZK_HIP(hipMemcpyAsync(w.fin_sums.p, sums.data(), (size_t)3 * nb * sizeof(Jac), hipMemcpyHostToDevice, c.stream));
+        UZK_TRY(finish_launch(c, w.fin_sums.as<Jac>(), w.rs.as<Fp>(), w.fin_terms.as<XYZZ>(), nb, w.fin_a.as<Affine>(), w.fin_c.as<Affine>()));
+        uint8_t* d_blobs = d_blobs_out ? d_blobs_out + (size_t)b0 * UZK_G16_PROOF_BYTES : w.fin_blobs.as<uint8_t>();
+        UZK_LAUNCH(c, "g16_encode", g16_encode_kernel, dim3((8 * nb + kFinBlock - 1) / kFinBlock), dim3(kFinBlock), 0, c.stream, w.fin_a.as<Affine>(),
+                   w.fin_b.as<G2Affine>(), w.fin_c.as<Affine>(), w.fin_proofs.as<Fp>(), d_blobs, nb);
+        if (proofs_out) UZK_HIP(hipMemcpyAsync(proofs_out + b0, w.fin_proofs.p, (size_t)nb * sizeof(uzk_g16_proof), hipMemcpyDeviceToHost, c.stream));
+        if (blobs_out) UZK_HIP(hipMemcpyAsync(blobs_out + (size_t)b0 * UZK_G16_PROOF_BYTES, d_blobs, (size_t)nb * UZK_G16_PROOF_BYTES, hipMemcpyDeviceToHost, c.stream));
+        UZK_HIP(hipStreamSynchronize(c.stream));                    // `sums` is reused by the next group; the results are complete on return
+    }
+    return UZK_OK;
+}
+
+// uzk_test_g16_finish: the chains, the combination and the affine maps on the caller's Jacobian points
+int g16_finish_test_run(Ctx& c, const Jac* a, const Jac* b1, const Jac* kk, const Fp* r_host, const Fp* s_host, uint32_t n, Affine* a_out, Affine* c_out) {
+    WsCarver cv;
+    const auto a_sums = cv.array<Jac>((size_t)3 * n);
+    const auto a_rs = cv.array<Fp>((size_t)2 * n);
+    const auto a_terms = cv.array<XYZZ>((size_t)2 * n);
+    const auto a_a = cv.array<Affine>(n), a_c = cv.array<Affine>(n);
+    G16Work& w = work(c);
+    UZK_TRY(cv.reserve(w.fin_test));
+    Jac* d_sums = cv(a_sums);
+    Fp* d_rs = cv(a_rs);
+    UZK_HIP(hipMemcpyAsync(d_sums, a, (size_t)n * sizeof(Jac), hipMemcpyHostToDevice, c.stream));
+    UZK_HIP(hipMemcpyAsync(d_sums + n, b1, (size_t)n * sizeof(Jac), hipMemcpyHostToDevice, c.stream));
+    UZK_HIP(hipMemcpyAsync(d_sums + 2 * (size_t)n, kk, (size_t)n * sizeof(Jac), hipMemcpyHostToDevice, c.stream));
+    UZK_HIP(hipMemcpyAsync(d_rs, r_host, (size_t)n * sizeof(Fp), hipMemcpyHostToDevice, c.stream));
+    UZK_HIP(hipMemcpyAsync(d_rs + n, s_host, (size_t)n * sizeof(Fp), hipMemcpyHostToDevice, c.stream));
+    c.cur_stream = c.stream;
+    UZK_TRY(finish_launch(c, d_sums, d_rs, cv(a_terms), n, cv(a_a), cv(a_c)));
+    UZK_HIP(hipMemcpyAsync(a_out, cv(a_a), (size_t)n * sizeof(Affine), hipMemcpyDeviceToHost, c.stream));
+    UZK_HIP(hipMemcpyAsync(c_out, cv(a_c), (size_t)n * sizeof(Affine), hipMemcpyDeviceToHost, c.stream));
+    UZK_HIP(hipStreamSynchronize(c.stream));
     return UZK_OK;
 }
 

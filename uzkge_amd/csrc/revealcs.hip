@@ -387,4 +387,21 @@ int rcs_prove_snark_batch(uint64_t circuit, const uint64_t* sk, const uint64_t* 
     return g16_prove_run(c, e.key, c.reveal_z.as<Fp>(), true, reinterpret_cast<const Fp*>(r_mont), reinterpret_cast<const Fp*>(s_mont), m, proofs_out);
 }
 
+int rcs_prove_snark_batch_finish(uint64_t circuit, const uint64_t* sk, const uint64_t* e1_mont, const uint64_t* r_mont, const uint64_t* s_mont, uint32_t m,
+                                 uint64_t* statements_out, uzk_g16_proof* proofs_out, uint8_t* blobs_out, void* d_blobs_out) {
+    static const char* who = "uzk_reveal_prove_snark_batch_finish";
+    API_LOCK;
+    RcsEntry e;
+    UZK_TRY(rcs_lookup(who, circuit, &e));
+    UZK_TRY(rcs_check_inputs(who, sk, e1_mont, m));
+    if (!r_mont || !s_mont || !statements_out) { set_error("%s: null pointer", who); return UZK_ERR_PARAMETER; }
+    if (!proofs_out && !blobs_out && !d_blobs_out) { set_error("%s: no output asked for", who); return UZK_ERR_PARAMETER; }
+    UZK_TRY(rcs_for_ctx(who, e));
+    Ctx& c = ctx();
+    UZK_TRY(c.reveal_z.reserve((size_t)m * kRcsVars * sizeof(Fp)));
+    UZK_TRY(rcs_witness_launch(c, e, sk, e1_mont, m, c.reveal_z.as<Fp>(), statements_out));
+    return g16_prove_finish_run(c, e.key, c.reveal_z.as<Fp>(), true, reinterpret_cast<const Fp*>(r_mont), reinterpret_cast<const Fp*>(s_mont), m, proofs_out, blobs_out,
+                                static_cast<uint8_t*>(d_blobs_out));
+}
+
 }  // namespace uzk

@@ -148,14 +148,14 @@ def verify_reveal0(pks: Sequence[Point], masked_cards: Sequence[Tuple[Point, Poi
     return [int(v) for v in b.cp_reveal_verify_batch(st, b"".join(proofs), anemoi=True)]
 
 
-def reveal_with_snark(sk: int, masked_cards: Sequence[Tuple[Point, Point]], circuit, r: Sequence[int], s: Sequence[int]):
+def reveal_with_snark(sk: int, masked_cards: Sequence[Tuple[Point, Point]], circuit, r: Sequence[int], s: Sequence[int], finish: str = "host"):
     """One player's reveals with a Groth16 proof each (sdk.rs reveal_card_with_snark; RevealVerifier.sol): (reveal cards, proofs, pk).
     circuit: a reveal_cs.RevealCircuit; r, s: one pair of fresh uniform integers below the scalar field's order per card, drawn by the
     caller.  A proof is the 256-byte blob Groth16VerifierKey.verify_batch takes, with the public inputs e1.x e1.y reveal.x reveal.y
-    pk.x pk.y of its card."""
+    pk.x pk.y of its card.  finish="device": the proofs are finished and encoded on the device; the same blobs."""
     if len(r) != len(masked_cards) or len(s) != len(masked_cards):
         raise ValueError("one pair of blinds per card")
-    statements, proofs = circuit.prove(sk, [c[0] for c in masked_cards], r, s)
+    statements, proofs = circuit.prove(sk, [c[0] for c in masked_cards], r, s, finish=finish)
     return [(st[2], st[3]) for st in statements], proofs, (statements[0][4], statements[0][5])
 
 

@@ -123,11 +123,17 @@ class RevealCircuit(b.RevealCircuit):
             raise
         return RevealWitness(self.n_vars, m, d_z, st)
 
-    def prove(self, sk: int, cards, r: Sequence[int], s: Sequence[int]):
-        """(statements, proofs): per card the six integers e1.x e1.y reveal.x reveal.y pk.x pk.y and the 256-byte proof blob"""
+    def prove(self, sk: int, cards, r: Sequence[int], s: Sequence[int], finish: str = "host"):
+        """(statements, proofs): per card the six integers e1.x e1.y reveal.x reveal.y pk.x pk.y and the 256-byte proof blob.
+        finish="device": the proofs are finished and encoded on the device (uzk_reveal_prove_snark_batch_finish); the same blobs."""
+        if finish not in ("host", "device"):
+            raise ValueError("finish is 'host' or 'device'")
         e1 = rv.points_to_wire(_e1s(cards))
         if len(r) != e1.shape[0] or len(s) != e1.shape[0]:
             raise ValueError("one pair of blinds per card")
         frs = lambda vals: np.stack([pc.fr_from_int(int(v)) for v in vals]) if len(vals) else np.zeros((0, 4), dtype=np.uint64)
+        if finish == "device":
+            st, _, blobs = self.prove_snark_batch_finish(rv.scalars_to_wire([sk])[0], e1, frs(r), frs(s))
+            return [tuple(c for p in rv.points_from_wire(row) for c in p) for row in st], [bytes(row) for row in blobs]
         st, proofs = self.prove_snark_batch(rv.scalars_to_wire([sk])[0], e1, frs(r), frs(s))
         return [tuple(c for p in rv.points_from_wire(row) for c in p) for row in st], proof_blobs(proofs)
