@@ -249,12 +249,19 @@ typedef struct {
     const uint64_t* val[3];
 } uzk_g16_key_desc;
 typedef struct { uzk_g1_affine a; uzk_g2_affine b; uzk_g1_affine c; } uzk_g16_proof;
-/* Proofs of one launch sequence; a larger batch runs as groups of this many. */
+/* Proofs of one launch sequence at most; a larger batch runs as groups (the rule is below). */
 #define UZK_G16_GROUP 128
 /* Checks the descriptor on the host (null pointers, 1 <= n_inputs <= n_vars, the two lengths, row pointers, col < n_vars:
  * UZK_ERR_PARAMETER; uzk_domain_supported(n) == 0 or n_vars + 2 > 2^UZK_MSM_G2_MAX_LOG2: UZK_ERR_DEGREE) before the device is touched,
  * then uploads everything to the calling context's device.  The handle is process-wide (like an SRS or G2 handle) and is used by
- * contexts on that device; uzk_shutdown releases what is left. */
+ * contexts on that device; uzk_shutdown releases what is left.
+ * Groups: a batch runs as groups of min(UZK_G16_GROUP, 2^21 / max(n_vars + 2, (n_vars - n_inputs) + n)) proofs, at least one -- the
+ * divisor is the longest row a proof has (the scalars of B, of K; the domain is never longer than K's row), so the buffers of a
+ * group hold at most 2^21 elements per row kind and each of the three G1 MSMs of a group is one the MSM code admits in one call.
+ * The reveal key (n = 8192, n_vars = 4869) runs groups of 128.
+ * What is tested how: proofs are compared with a reference at domains up to 2^16 and n_vars up to 2^15 + 3 (groups of 128, 63 and
+ * 31; two G2 point chunks).  Every larger shape accepted here (domains up to 2^25, n_vars + 2 up to 2^20) is only PLANNED: its group
+ * size and the admission of its MSMs are checked without running a proof (tests/test_gpu_g16_large.py). */
 int uzk_g16_key_create(const uzk_g16_key_desc* desc, uint64_t* key_out);
 /* The caller makes sure no context still proves with this key. */
 int uzk_g16_key_release(uint64_t key);

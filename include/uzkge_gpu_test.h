@@ -50,6 +50,11 @@ int uzk_test_g2_kat(int op, const uint64_t* a, const uint64_t* b, uint64_t* out,
  * opposite terms, an infinite operand or sum); this can.  n <= 4096. */
 int uzk_test_g16_finish(const uzk_g1_jac* a_jac, const uzk_g1_jac* b1_jac, const uzk_g1_jac* k_jac, const uint64_t* r_mont, const uint64_t* s_mont, size_t n,
                         uzk_g1_affine* a_out, uzk_g1_affine* c_out);
+/* How uzk_g16_prove_batch* would run a key of this shape, with no key: uzk_g16_key_create's rules for the three sizes (their error
+ * codes), then *group_out = the proofs of one launch sequence, lens_out = the lengths of the G1 MSMs A, B1, K (n_vars + 2 twice,
+ * (n_vars - n_inputs) + n) and admitted_out[i] = 1 iff the MSM code takes `group` vectors of lens_out[i] points in one call under the
+ * calling context's tuning -- the very function the MSM entry refuses by.  Launches nothing, allocates nothing on the device. */
+int uzk_test_g16_plan(uint32_t n_vars, uint32_t n_inputs, uint32_t n_constraints, uint32_t* group_out, uint64_t lens_out[3], int admitted_out[3]);
 
 /* ---- raw 9 x 29-bit limbs: the primitives of the hot loops (fp29.hpp) and the typed lazy operations (lz29.hpp) at their bounds ----
  * in: n records of four operands a, b, c, d, 9 limbs (uint32) each, taken EXACTLY as given; out: n x 9 words, the raw result (no

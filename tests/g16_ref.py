@@ -6,6 +6,7 @@ transforms and the G1 MSMs, tests/g2_ref.py for G2.
   prove             A, B, C of a proof from a key, the matrices, an assignment and the blinds r, s
   trapdoor_setup    a key for a given R1CS from known tau, alpha, beta, gamma, delta: every query point is a known scalar times the
                     generator, so a proof has a closed form (closed_form) and can be verified (verify)
+  closed_form_logs  that closed form for ANY key whose points' logarithms are known (a trapdoor key, or tests/g16_pool.py's)
 
 G1 points are affine integer tuples (x, y), G2 points ((x0, x1), (y0, y1)); None = infinity.  Rows of a matrix are lists of
 (column, value)."""
@@ -202,7 +203,8 @@ def _g2_fixed():
 
 
 def trapdoor_scalars(matrices, l, m, trap):
-    """the discrete logarithms of every point of the key"""
+    """the discrete logarithms of every point of the key: u, v, gamma_abc as the setup names them, and the dictionary closed_form_logs
+    takes -- the columns a (= u), b1 and b2 (= v, both), l, h and the fixed points alpha, beta_g1 = beta_g2, delta_g1 = delta_g2"""
     tau, alpha, beta, gamma, delta = trap
     n = domain_of(len(matrices[0]), l)
     u, v, w = qap_at(matrices, l, m, tau)
@@ -210,7 +212,8 @@ def trapdoor_scalars(matrices, l, m, trap):
     comb = [(beta * u[j] + alpha * v[j] + w[j]) % R for j in range(m)]
     zt = (pow(tau, n, R) - 1) * di % R
     return dict(u=u, v=v, gamma_abc=[c * gi % R for c in comb[:l]], l=[c * di % R for c in comb[l:]],
-                h=[pow(tau, i, R) * zt % R for i in range(n - 1)])
+                h=[pow(tau, i, R) * zt % R for i in range(n - 1)], a=u, b1=v, b2=v, alpha=alpha, beta_g1=beta, beta_g2=beta, delta_g1=delta,
+                delta_g2=delta)
 
 
 def trapdoor_setup(matrices, l, m, trap):
@@ -222,14 +225,33 @@ def trapdoor_setup(matrices, l, m, trap):
                b_g2_query=[m2(x) for x in sc["v"]], h_query=[m1(x) for x in sc["h"]], l_query=[m1(x) for x in sc["l"]])
 
 
+def closed_form_sums(logs, l, z, h):
+    """the part of a proof's logarithms that the blinds do not enter: the four MSMs without their delta terms, (a0, b10, b20, k0).
+    logs: the logarithms of the key's points -- lists a, b1, b2 (m each), l (m - l), h (n - 1), integers alpha, beta_g1, beta_g2
+    (delta_g1, delta_g2 enter with the blinds); trapdoor_scalars makes one, tests/g16_pool.py another."""
+    dot = lambda xs, cs: sum(x * y for x, y in zip(xs, cs))
+    assert len(logs["a"]) == len(logs["b1"]) == len(logs["b2"]) == len(z) and len(logs["l"]) == len(z) - l and len(logs["h"]) == len(h) - 1
+    return ((logs["alpha"] + dot(z, logs["a"])) % R, (logs["beta_g1"] + dot(z, logs["b1"])) % R, (logs["beta_g2"] + dot(z, logs["b2"])) % R,
+            (dot(z[l:], logs["l"]) + dot(h, logs["h"])) % R)
+
+
+def closed_form_blind(sums, logs, r, s):
+    """(a, b, c) from closed_form_sums and the blinds: a = a0 + r delta_1, b1 = b10 + s delta_1, b = b20 + s delta_2,
+    c = s a + r b1 + k0 - r s delta_1"""
+    a0, b10, b20, k0 = sums
+    a = (a0 + r * logs["delta_g1"]) % R
+    b1 = (b10 + s * logs["delta_g1"]) % R
+    return a, (b20 + s * logs["delta_g2"]) % R, (s * a + r * b1 + k0 - r * s * logs["delta_g1"]) % R
+
+
+def closed_form_logs(logs, l, z, r, s, h):
+    """the discrete logarithms (a, b, c) of the proof under a key of known logarithms: A = a G, B = b G2, C = c G"""
+    return closed_form_blind(closed_form_sums(logs, l, z, h), logs, r, s)
+
+
 def closed_form(matrices, l, z, r, s, trap, h):
-    """the discrete logarithms (a, b, c) of a trapdoor proof: A = a G, B = b G2, C = c G"""
-    tau, alpha, beta, gamma, delta = trap
-    sc = trapdoor_scalars(matrices, l, len(z), trap)
-    a = (alpha + sum(x * y for x, y in zip(z, sc["u"])) + r * delta) % R
-    b = (beta + sum(x * y for x, y in zip(z, sc["v"])) + s * delta) % R
-    k = (sum(x * y for x, y in zip(z[l:], sc["l"])) + sum(x * y for x, y in zip(h, sc["h"])) - r * s * delta) % R
-    return a, b, (s * a + r * (b) + k) % R
+    """closed_form_logs for a trapdoor key"""
+    return closed_form_logs(trapdoor_scalars(matrices, l, len(z), trap), l, z, r, s, h)
 
 
 def points_of(a, b, c):

@@ -205,6 +205,7 @@ TEST_PROTOTYPES = {
     "uzk_test_g1_kat": (_I, [_I, _P, _P, _P, _SZ]),
     "uzk_test_g2_kat": (_I, [_I, _P, _P, _P, _SZ]),
     "uzk_test_g16_finish": (_I, [_P, _P, _P, _P, _P, _SZ, _P, _P]),
+    "uzk_test_g16_plan": (_I, [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(_U64), ctypes.POINTER(_I)]),
     "uzk_test_circuit_truncate_t": (_I, [_U64, _I]),
     "uzk_test_shuffle_cs_tables": (_I, [_U64, _U64, _P, _P, _P]),
     "uzk_test_match_cs_tables": (_I, [_U64, _P, _P, _P]),

@@ -2210,6 +2210,13 @@ int uzk_test_g16_finish(const uzk_g1_jac* a_jac, const uzk_g1_jac* b1_jac, const
                                as_fp(s_mont), (uint32_t)n, reinterpret_cast<Affine*>(a_out), reinterpret_cast<Affine*>(c_out));
 } catch (...) { return uzk::on_exception("uzk_test_g16_finish"); }
 
+int uzk_test_g16_plan(uint32_t n_vars, uint32_t n_inputs, uint32_t n_constraints, uint32_t* group_out, uint64_t lens_out[3], int admitted_out[3]) try {
+    API_LOCK;
+    if (!group_out || !lens_out || !admitted_out) { set_error("uzk_test_g16_plan: null pointer"); return UZK_ERR_PARAMETER; }
+    UZK_TRY(require_ready());                         // the admission depends on the calling context's tuning
+    return g16_plan_test(ctx(), n_vars, n_inputs, n_constraints, group_out, lens_out, admitted_out);
+} catch (...) { return uzk::on_exception("uzk_test_g16_plan"); }
+
 int uzk_test_g2_kat(int op, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n) try {
     API_LOCK;
     if (n > 0 && (!a || !b || !out)) { set_error("uzk_test_g2_kat: null pointer"); return UZK_ERR_PARAMETER; }

@@ -330,6 +330,7 @@ int g16_prove_run(Ctx& c, uint64_t h, const Fp* z, bool z_on_device, const Fp* r
 int g16_prove_finish_run(Ctx& c, uint64_t h, const Fp* z, bool z_on_device, const Fp* r_host, const Fp* s_host, uint32_t batch, uzk_g16_proof* proofs_out,
                          uint8_t* blobs_out, uint8_t* d_blobs_out);
 int g16_finish_test_run(Ctx& c, const Jac* a, const Jac* b1, const Jac* k, const Fp* r_host, const Fp* s_host, uint32_t n, Affine* a_out, Affine* c_out);
+int g16_plan_test(Ctx& c, uint32_t m, uint32_t l, uint32_t nc, uint32_t* group_out, uint64_t lens_out[3], int admitted_out[3]);
 // g16verify.hip: Groth16 verifying keys (process-wide handles) and the fold of a batch of proofs
 int g16v_key_check(const uzk_g16_vk_desc* d);
 int g16v_key_create(Ctx& c, const uzk_g16_vk_desc* d, uint64_t* out);
@@ -402,6 +403,8 @@ int remark_device_run(Ctx& c, uint64_t h, const EdAffine* d_e1, const EdAffine* 
                       EdAffine* d_e1_out, EdAffine* d_e2_out, Fp* d_trace);
 int remark_device_tables(Ctx& c, uint64_t h, const Fp** d_pk_out, const Fp** d_gen_out);
 void msm_plan_info(Ctx& c, size_t n, int* window_bits, int* windows);
+// UZK_OK when msm_run takes `batch` vectors of n points (pre_c > 0: over a window table), its refusal otherwise; launches nothing
+int msm_admit(Ctx& c, size_t n, uint32_t batch, int pre_c);
 int msm_run(Ctx& c, const Affine* points, const ScalarView& scalars, size_t n, uint32_t batch, Jac* out_host, int pre_c,
             uint32_t pre_stride, uint32_t pre_off);
 int msm_run_streamed(Ctx& c, const Affine* points, const Fp* scalars_host, size_t n, Jac* out_host);

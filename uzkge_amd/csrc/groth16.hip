@@ -33,7 +33,7 @@ namespace {
 constexpr uint32_t kSlice = 32;                 // entries of a row one lane multiplies
 constexpr uint32_t kGroup = UZK_G16_GROUP;      // the G2 MSM's group: proofs of one launch sequence
 constexpr uint32_t kFinBlock = 64;               // lanes of a workgroup of the finish kernels
-constexpr uint64_t kGroupElems = 1ull << 21;    // domain points of one group at most (bounds the transform buffers: 3 x 64 MiB)
+constexpr uint64_t kGroupElems = 1ull << 21;    // elements of one group's longest row at most (g16_group; transform buffers: 3 x 64 MiB)
 
 struct Slice {
     uint32_t start, len;                        // entries [start, start + len) of the concatenated col / val arrays
@@ -191,16 +191,24 @@ __global__ __launch_bounds__(kFinBlock) void g16_encode_kernel(const Affine* __r
 
 // ---- keys -------------------------------------------------------------------------------------------------------------------
 
-// Everything that can be said about a descriptor without a device; *domain_out = n.
-int g16_key_check(const uzk_g16_key_desc* d, uint64_t* domain_out) {
-    if (!d) { set_error("uzk_g16_key_create: null descriptor"); return UZK_ERR_PARAMETER; }
-    const uint64_t m = d->n_vars, l = d->n_inputs, nc = d->n_constraints;
+// What a key's three sizes must satisfy, before any of its arrays is looked at; *domain_out = n.
+static int g16_shape_check(uint64_t m, uint64_t l, uint64_t nc, uint64_t* domain_out) {
     if (l < 1 || l > m) { set_error("uzk_g16_key_create: n_inputs %llu must be in 1 .. n_vars %llu", (unsigned long long)l, (unsigned long long)m); return UZK_ERR_PARAMETER; }
     if (nc < 1) { set_error("uzk_g16_key_create: no constraints"); return UZK_ERR_PARAMETER; }
     uint64_t n = 1;
     while (n < nc + l) n <<= 1;
     if (!domain_supported(n)) { set_error("uzk_g16_key_create: no evaluation domain of size %llu", (unsigned long long)n); return UZK_ERR_DEGREE; }
     if (m + 2 > (1ull << UZK_MSM_G2_MAX_LOG2)) { set_error("uzk_g16_key_create: n_vars %llu exceeds the G2 MSM's 2^%d points", (unsigned long long)m, UZK_MSM_G2_MAX_LOG2); return UZK_ERR_DEGREE; }
+    *domain_out = n;
+    return UZK_OK;
+}
+
+// Everything that can be said about a descriptor without a device; *domain_out = n.
+int g16_key_check(const uzk_g16_key_desc* d, uint64_t* domain_out) {
+    if (!d) { set_error("uzk_g16_key_create: null descriptor"); return UZK_ERR_PARAMETER; }
+    const uint64_t m = d->n_vars, l = d->n_inputs, nc = d->n_constraints;
+    uint64_t n = 0;
+    UZK_TRY(g16_shape_check(m, l, nc, &n));
     if (d->l_query_len != m - l) { set_error("uzk_g16_key_create: l_query has %llu entries, n_vars - n_inputs = %llu", (unsigned long long)d->l_query_len, (unsigned long long)(m - l)); return UZK_ERR_PARAMETER; }
     if (d->h_query_len != n - 1) { set_error("uzk_g16_key_create: h_query has %llu entries, the domain has %llu points", (unsigned long long)d->h_query_len, (unsigned long long)n); return UZK_ERR_PARAMETER; }
     if (!d->a_query || !d->b_g1_query || !d->b_g2_query || (m > l && !d->l_query) || (n > 1 && !d->h_query)) { set_error("uzk_g16_key_create: null query column"); return UZK_ERR_PARAMETER; }
@@ -332,7 +340,30 @@ void g16_free(Ctx& c) {
     c.g16 = nullptr;
 }
 
-static uint32_t group_of(const G16Key& k) { return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(kGroup, kGroupElems / k.n)); }
+// Proofs of one launch sequence for a key of domain n with m variables, l of them inputs: at most kGroup, and as many as keep the
+// longest per-proof row within kGroupElems elements in all -- the domain (the transform buffers), the row of B (m + 2: z_in, zT,
+// row_b) and the row of K ((m - l) + n: row_k, the longest MSM).  Every G1 MSM of such a group is one msm.hip admits
+// (uzk_test_g16_plan; tests/test_gpu_g16_large.py sweeps the accepted shapes).
+static uint32_t g16_group(uint64_t n, uint64_t m, uint64_t l) {
+    const uint64_t longest = std::max<uint64_t>(m + 2, (m - l) + n);
+    return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(kGroup, kGroupElems / longest));
+}
+static uint32_t group_of(const G16Key& k) { return g16_group(k.n, k.m, k.l); }
+
+// uzk_test_g16_plan: the shape rules of a key and the plan of its groups, with no key; the lengths of the MSMs A, B1, K and whether
+// msm.hip takes each at batch = group under this context's tuning.  Launches nothing, reserves nothing.
+int g16_plan_test(Ctx& c, uint32_t m, uint32_t l, uint32_t nc, uint32_t* group_out, uint64_t lens_out[3], int admitted_out[3]) {
+    uint64_t n = 0;
+    UZK_TRY(g16_shape_check(m, l, nc, &n));
+    const uint32_t group = g16_group(n, m, l);
+    const uint64_t lens[3] = {(uint64_t)m + 2, (uint64_t)m + 2, (uint64_t)(m - l) + n};
+    *group_out = group;
+    for (int i = 0; i < 3; ++i) {
+        lens_out[i] = lens[i];
+        admitted_out[i] = msm_admit(c, (size_t)lens[i], group, 0) == UZK_OK ? 1 : 0;
+    }
+    return UZK_OK;
+}
 static unsigned blocks(uint64_t threads) { return (unsigned)((threads + 255) / 256); }
 
 // h of nb <= group_of(k) assignments: left in the first nb * n elements of the work buffer `abc`

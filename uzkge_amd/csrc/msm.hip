@@ -1947,24 +1947,36 @@ struct MsmGroup {
     XYZZ* part_cur = nullptr;
 };
 
+// What the general pipeline refuses of `batch` vectors of n points each over W windows of cb bits -- both of its refusals, and nothing
+// else: no launch, no reservation.  *NB_out, *Wd_out (optional): the bucket windows the task scans run over.
+static int msm_group_admit(size_t n, uint32_t batch, int cb, bool pre, uint32_t W, uint32_t* NB_out, uint32_t* Wd_out) {
+    // one 31-bit index per (vector, window, point); n and W n first, so that no product here wraps
+    const uint64_t per_poly = n < (1ull << 31) ? (uint64_t)W * n : 1ull << 31;
+    if (per_poly >= (1ull << 31) || per_poly * batch >= (1ull << 31)) { set_error("msm: batch*W*n overflows the 31-bit index space"); return UZK_ERR_PARAMETER; }
+    const uint32_t NBL = 1u << (cb - 1), S0 = pre ? batch : batch * W;      // buckets of a window; sort segments
+    // bucket windows of <= 2^15 buckets for the task scans, as many of them as the 1024-entry window table holds
+    uint32_t NB = std::min<uint32_t>(NBL, 1u << 15);
+    while (((uint64_t)S0 * NBL) / NB > 1024 && NB < (1u << 15)) NB <<= 1;
+    const uint64_t Wd = ((uint64_t)S0 * NBL) / NB;
+    if (Wd > 1024) { set_error("msm: too many bucket windows (%llu): lower the batch", (unsigned long long)Wd); return UZK_ERR_PARAMETER; }
+    if (NB_out) *NB_out = NB;
+    if (Wd_out) *Wd_out = (uint32_t)Wd;
+    return UZK_OK;
+}
+
 // idx_span (precomputed mode): the sorted values are table indices pre_stride * j + pre_off + i < idx_span, not positions in the
 // scalar vector -- the packed sort entries must have room for those (0: no bound known, unpacked entries)
 static int msm_group_plan(Ctx& c, MsmGroup& g, size_t n, uint32_t batch, int cb, bool pre, uint32_t W_total, uint32_t w0,
                           uint32_t W, uint64_t idx_span = 0) {
     g.pre = pre; g.cb = cb; g.W_total = W_total; g.w0 = w0; g.W = W; g.n32 = (uint32_t)n; g.batch = batch;
+    UZK_TRY(msm_group_admit(n, batch, cb, pre, W, &g.NB, &g.Wd));
     g.per_poly = (uint64_t)W * n;
     g.entries = g.per_poly * batch;
-    if (g.entries >= (1ull << 31)) { set_error("msm: batch*W*n overflows the 31-bit index space"); return UZK_ERR_PARAMETER; }
     g.kb = (uint32_t)cb - 1;
     g.NBL = 1u << g.kb;
     g.S0 = pre ? batch : batch * W;                         // sort segments
     g.seg_n = pre ? (uint32_t)g.per_poly : g.n32;
-    // bucket windows of <= 2^15 buckets for the task scans, as many of them as the 1024-entry window table holds
-    g.NB = std::min<uint32_t>(g.NBL, 1u << 15);
-    while (((uint64_t)g.S0 * g.NBL) / g.NB > 1024 && g.NB < (1u << 15)) g.NB <<= 1;
-    g.Wd = (uint32_t)(((uint64_t)g.S0 * g.NBL) / g.NB);
     g.TBK = (uint64_t)g.Wd * g.NB;
-    if (g.Wd > 1024) { set_error("msm: too many bucket windows (%u): lower the batch", g.Wd); return UZK_ERR_PARAMETER; }
     g.RW = pre ? batch : batch * W;                         // logical windows in the reduction
     // scan-based reduction: segments of 8 buckets per lane (power of two), at most 256 workgroups per window
     // (measured: the scan form wins for windows of <= 2^14 buckets, the double-and-add form above that).
@@ -2757,6 +2769,17 @@ void msm_plan_info(Ctx& c, size_t n, int* window_bits, int* windows) {
     *windows = msm_num_windows(cb);
 }
 
+// Whether msm_run takes `batch` vectors of n points (over plain bases, or over a window table of pre_c-bit windows) under this
+// context's tuning: every refusal msm_run can make for its sizes, stated once -- msm_run calls this before it touches anything, and a
+// caller that plans its own batches (groth16.hip) asks here first.  Launches nothing, reserves nothing.
+int msm_admit(Ctx& c, size_t n, uint32_t batch, int pre_c) {
+    if (batch == 0 || n == 0) return UZK_OK;
+    if (n >= (1ull << 31)) { set_error("msm: n = %zu exceeds 2^31 - 1 points per call", n); return UZK_ERR_PARAMETER; }
+    if (msm_small_applies(c, n, batch, pre_c)) return UZK_OK;
+    const int cb = pre_c > 0 ? pre_c : choose_window_bits(n, c.msm_window_bits);
+    return msm_group_admit(n, batch, cb, pre_c > 0, (uint32_t)msm_num_windows(cb), nullptr, nullptr);
+}
+
 // `points`: base array the sorted indices refer to (the SRS slice, or the window table).
 // Precomputed mode (pre_c > 0): `points` = table, entries of window j index pre_stride * j + pre_off + i.
 // `batch` scalar vectors of n elements each share the same bases; out_host[batch].
@@ -2765,7 +2788,7 @@ int msm_run(Ctx& c, const Affine* points, const ScalarView& d_scalars, size_t n,
     if (batch == 0) return UZK_OK;
     if ((size_t)d_scalars.n_main + d_scalars.tail_n != n) { set_error("msm: scalar view covers %u + %u elements, n = %zu", d_scalars.n_main, d_scalars.tail_n, n); return UZK_ERR_PARAMETER; }
     if (n == 0) { for (uint32_t b = 0; b < batch; ++b) out_host[b] = jac_inf(); return UZK_OK; }
-    if (n >= (1ull << 31)) { set_error("msm: n = %zu exceeds 2^31 - 1 points per call", n); return UZK_ERR_PARAMETER; }
+    UZK_TRY(msm_admit(c, n, batch, pre_c));
     if (!c.msm) c.msm = new MsmWork[2];
     const bool pre = pre_c > 0;
     if (msm_small_applies(c, n, batch, pre_c)) return msm_run_small(c, points, d_scalars, n, batch, out_host, pre_c, pre_stride, pre_off);
