@@ -13,7 +13,7 @@
 
 #include "anemoi29.hpp"
 #include "ctx.hpp"
-#include "curvecheck.hpp"
+#include "lane_tools.hpp"
 #include "fq12_29.hpp"
 #include "g16_pk_layout.hpp"
 #include "g2_29.hpp"
@@ -1926,7 +1926,7 @@ int uzk_test_sqrt_kat(int field, const uint64_t* a_mont, size_t n, uint64_t* roo
     UZK_TRY(codec_batch_args("uzk_test_sqrt_kat", a_mont, n, root_out, is_square_out));
     const size_t words = field == 1 ? 2 * n : n;
     for (size_t i = 0; i < words; ++i)
-        if (!(field == 2 ? gv_below_modulus<FrCfg>(as_fp(a_mont)[i]) : gv_below_modulus<FqCfg>(as_fp(a_mont)[i]))) {
+        if (!(field == 2 ? below_modulus<FrCfg>(as_fp(a_mont)[i]) : below_modulus<FqCfg>(as_fp(a_mont)[i]))) {
             set_error("uzk_test_sqrt_kat: element %zu is not below the modulus", i);
             return UZK_ERR_PARAMETER;
         }

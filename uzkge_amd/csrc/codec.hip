@@ -3,7 +3,7 @@
 //   codec_g1_dec    x little-endian, flags in the top two bits; y = sqrt(x^3 + 3) in one chain of Fq (sqrt29.hpp), the root chosen by the
 //                   sign flag against its negation in canonical, non-Montgomery words
 //   codec_g2_dec    x.c0, x.c1; y = sqrt(x^3 + 3 / (9 + u)) in Fq2 by the norm method: three chain lengths, two of them side by side
-//   codec_g2_sub    [r] Q = O for the decoded points with status 0: the double-and-add of g16verify.hip's g16v_subgroup over G2P
+//   codec_g2_sub    [r] Q = O for the decoded points with status 0: the double-and-add over G2P (g2_in_subgroup of lane_tools.hpp)
 //   codec_ed_dec    y; x = sqrt((1 - y^2) / (1 - d y^2)) in Fr with the division inside the root (fr_sqrt_ratio)
 //   codec_ed_sub    ed::classify on the decoded points with status 0
 //   codec_*_enc     the cheap direction: leave Montgomery form, compare the coordinate with its negation, write the bytes
@@ -11,10 +11,10 @@
 // Every lane of a decoding batch walks the same constant exponent; lanes that stop early (an infinity, a word that is not canonical)
 // only sit out.  A point whose status is not 0 is written as zeros.  tests/codec_ref.py is the restatement on Python integers.
 #include "ctx.hpp"
-#include "curvecheck.hpp"
 #include "ed29.hpp"
 #include "g2_29.hpp"
 #include "handles.hpp"
+#include "lane_tools.hpp"
 #include "sqrt29.hpp"
 
 namespace uzk {
@@ -59,7 +59,7 @@ __global__ __launch_bounds__(kCdBlock) void codec_g1_dec_kernel(const uint8_t* _
     uint32_t st = CD_OK;
     if (flags & 1) {
         if ((flags & 2) || !Fq::is_zero(x)) st = CD_NOT_CANONICAL;
-    } else if (!gv_below_modulus<FqCfg>(x)) {
+    } else if (!below_modulus<FqCfg>(x)) {
         st = CD_NOT_CANONICAL;
     } else {
         const Fp xm = Fq::to_mont(x);
@@ -95,13 +95,13 @@ __global__ __launch_bounds__(kCdBlock) void codec_g2_dec_kernel(const uint8_t* _
     uint32_t st = CD_OK;
     if (flags & 1) {
         if ((flags & 2) || !Fq::is_zero(x0) || !Fq::is_zero(x1)) st = CD_NOT_CANONICAL;
-    } else if (!gv_below_modulus<FqCfg>(x0) || !gv_below_modulus<FqCfg>(x1)) {
+    } else if (!below_modulus<FqCfg>(x0) || !below_modulus<FqCfg>(x1)) {
         st = CD_NOT_CANONICAL;
     } else {
         Fq2w xw;
         xw.c0 = Fq::to_mont(x0); xw.c1 = Fq::to_mont(x1);
         const auto X = q2::ldr(xw);
-        const auto rhs = q2::red(q2::add(q2::mul(q2::sqr(X), X), q2::ldr(gv_twist_b())));
+        const auto rhs = q2::red(q2::add(q2::mul(q2::sqr(X), X), q2::ldr(g2_twist_b())));
         q2::E2<1, 2> Y;
         if (!sq::fq2_sqrt(rhs, &Y)) st = CD_NO_POINT;
         else {
@@ -121,21 +121,13 @@ __global__ __launch_bounds__(kCdBlock) void codec_g2_dec_kernel(const uint8_t* _
 #endif
 }
 
-// [r] Q = O over G2P, as g16verify.hip's g16v_subgroup has it: the bits of r are the same for every lane
+// [r] Q = O over G2P (g2_in_subgroup of lane_tools.hpp): the bits of r are the same for every lane
 __global__ __launch_bounds__(kCdBlock) void codec_g2_sub_kernel(G2Affine* __restrict__ pts, uint8_t* __restrict__ status, uint32_t n) {
 #if defined(__HIP_DEVICE_COMPILE__)
     const uint32_t i = blockIdx.x * kCdBlock + threadIdx.x;
     if (i >= n) return;
     if (status[i] != CD_OK) return;
-    const G2P base = g2p_from_affine(pts[i]);
-    if (base.inf) return;
-    G2P acc = g2p_inf();
-#pragma unroll 1
-    for (int k = 253; k >= 0; --k) {
-        g2p_dbl(acc);
-        if ((FrCfg::M[k >> 5] >> (k & 31)) & 1) g2p_add(acc, base);
-    }
-    if (!acc.inf) {
+    if (!g2_in_subgroup(g2p_from_affine(pts[i]))) {
         G2Affine z;
         z.x = fq2w_zero(); z.y = z.x;
         pts[i] = z;
@@ -202,7 +194,7 @@ __global__ __launch_bounds__(kCdBlock) void codec_g1_enc_kernel(const Affine* __
     const Affine p = pts[i];
     Fp x = Fq::zero();
     uint32_t flags = 0, st = CD_OK;
-    if (!gv_below_modulus<FqCfg>(p.x) || !gv_below_modulus<FqCfg>(p.y)) st = CD_NOT_CANONICAL;
+    if (!below_modulus<FqCfg>(p.x) || !below_modulus<FqCfg>(p.y)) st = CD_NOT_CANONICAL;
     else if (affine_is_inf(p)) flags = 1u << 30;
     else {
         x = Fq::from_mont(p.x);
@@ -220,7 +212,7 @@ __global__ __launch_bounds__(kCdBlock) void codec_g2_enc_kernel(const G2Affine* 
     const G2Affine p = pts[i];
     Fp x0 = Fq::zero(), x1 = x0;
     uint32_t flags = 0, st = CD_OK;
-    if (!gv_below_modulus<FqCfg>(p.x.c0) || !gv_below_modulus<FqCfg>(p.x.c1) || !gv_below_modulus<FqCfg>(p.y.c0) || !gv_below_modulus<FqCfg>(p.y.c1))
+    if (!below_modulus<FqCfg>(p.x.c0) || !below_modulus<FqCfg>(p.x.c1) || !below_modulus<FqCfg>(p.y.c0) || !below_modulus<FqCfg>(p.y.c1))
         st = CD_NOT_CANONICAL;
     else if (fq2w_is_zero(p.x) && fq2w_is_zero(p.y)) flags = 1u << 30;
     else {

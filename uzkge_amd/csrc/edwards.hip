@@ -31,6 +31,7 @@
 #include "ctx.hpp"
 #include "ed29.hpp"
 #include "handles.hpp"
+#include "lane_tools.hpp"
 
 namespace uzk {
 
@@ -38,19 +39,7 @@ constexpr uint32_t kEdBlock = 64;
 static_assert(sizeof(EdAffine) == 64, "a point is eight 64-bit words on the wire");
 static_assert(UZK_CP_PROOF_BYTES == 160, "a proof is five 32-byte words");
 
-// a 32-byte big-endian word of a blob as an integer
-__device__ __forceinline__ Fp cp_word_be(const uint8_t* blob, uint32_t word) {
-    const uint32_t* src = reinterpret_cast<const uint32_t*>(blob) + 8 * word;     // blobs are 160 bytes apart in a 256-byte aligned array
-    Fp v;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v.v[j] = __builtin_bswap32(src[7 - j]);
-    return v;
-}
-__device__ __forceinline__ void cp_store_word_be(uint8_t* blob, uint32_t word, const Fp& v) {
-    uint32_t* dst = reinterpret_cast<uint32_t*>(blob) + 8 * word;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) dst[7 - j] = __builtin_bswap32(v.v[j]);
-}
+// a blob is 32-byte big-endian words (load_be32 / store_be32 of lane_tools.hpp); blobs are 160 bytes apart in a 256-byte aligned array
 
 __global__ __launch_bounds__(kEdBlock) void ed_check_kernel(const EdAffine* __restrict__ pts, uint8_t* __restrict__ status, uint32_t n) {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -103,7 +92,7 @@ __device__ __forceinline__ EdAffine cp_at(const EdAffine* p, uint32_t stride, ui
 
 // a (which = 0) or b (which = 1) of a blob in Montgomery words; false (and zeros) when a word is not below q
 __device__ __forceinline__ bool cp_blob_point(const uint8_t* blob, uint32_t which, EdAffine* p) {
-    const Fp x = cp_word_be(blob, 2 * which), y = cp_word_be(blob, 2 * which + 1);
+    const Fp x = load_be32(blob + 64 * which), y = load_be32(blob + 64 * which + 32);
     const bool canonical = ed_coord_canonical(x) && ed_coord_canonical(y);
     p->x = canonical ? Fr::to_mont(x) : Fr::zero();
     p->y = canonical ? Fr::to_mont(y) : Fr::zero();
@@ -142,7 +131,7 @@ __global__ __launch_bounds__(kEdBlock) void cp_transcript_kernel(CpStatement s, 
     for (int k = 0; k < 4; ++k) { w[2 * k] = Fr::from_mont(pts[k].x); w[2 * k + 1] = Fr::from_mont(pts[k].y); }
     if (proofs_in) {
 #pragma unroll
-        for (int k = 0; k < 4; ++k) w[8 + k] = cp_word_be(proofs_in + (size_t)i * UZK_CP_PROOF_BYTES, k);
+        for (int k = 0; k < 4; ++k) w[8 + k] = load_be32(proofs_in + (size_t)i * UZK_CP_PROOF_BYTES + 32 * k);
     } else {
 #pragma unroll
         for (int k = 0; k < 2; ++k) { w[8 + 2 * k] = Fr::from_mont(ab[2 * (size_t)i + k].x); w[9 + 2 * k] = Fr::from_mont(ab[2 * (size_t)i + k].y); }
@@ -161,8 +150,8 @@ __global__ __launch_bounds__(kEdBlock) void cp_transcript_kernel(CpStatement s, 
         const Fp r = ed_muladd_order(ed_mod_order(omega[i]), c, ed_mod_order(sk[(size_t)i * s_sk]));
         uint8_t* blob = proofs_out + (size_t)i * UZK_CP_PROOF_BYTES;
 #pragma unroll
-        for (int k = 0; k < 4; ++k) cp_store_word_be(blob, k, w[8 + k]);
-        cp_store_word_be(blob, 4, r);
+        for (int k = 0; k < 4; ++k) store_be32(blob + 32 * k, w[8 + k]);
+        store_be32(blob + 128, r);
     }
 #endif
 }
@@ -216,7 +205,7 @@ __global__ __launch_bounds__(kEdBlock) void cp_check_kernel(CpStatement s, const
     const bool canonical = cp_blob_point(blob, q, &rhs) && ed_coord_canonical(base.x) && ed_coord_canonical(base.y) && ed_coord_canonical(other.x) &&
                            ed_coord_canonical(other.y);
     if (!canonical) { ok[t] = 0; return; }
-    const Fp r = cp_word_be(blob, 4);                               // any 256-bit integer: an integer multiple is defined on the whole curve
+    const Fp r = load_be32(blob + 128);                             // any 256-bit integer: an integer multiple is defined on the whole curve
     const ed::P t1 = ed::from_affine(base), t2 = ed::neg(ed::from_affine(other)), t3 = ed::add(t1, t2);
     const ed::P lhs = ed::mul2(t1, t2, t3, r, c[i]);
     ok[t] = ed::eq_affine(lhs, ed::ld(rhs.x), ed::ld(rhs.y)) ? 1 : 0;

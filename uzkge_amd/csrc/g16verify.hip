@@ -22,11 +22,11 @@
 #include <vector>
 
 #include "ctx.hpp"
-#include "curvecheck.hpp"
 #include "fq12_29.hpp"
 #include "g2_29.hpp"
 #include "handles.hpp"
 #include "host_math.hpp"
+#include "lane_tools.hpp"
 
 namespace uzk {
 
@@ -43,15 +43,13 @@ __global__ __launch_bounds__(kGvBlock) void g16v_decode_kernel(const uint8_t* __
 #if defined(__HIP_DEVICE_COMPILE__)
     const uint32_t i = blockIdx.x * kGvBlock + threadIdx.x;
     if (i >= m) return;
-    const uint32_t* src = reinterpret_cast<const uint32_t*>(proofs + (size_t)i * UZK_G16_PROOF_BYTES);
+    const uint8_t* blob = proofs + (size_t)i * UZK_G16_PROOF_BYTES;
     Fp w[kGvWords];
     bool canonical = true;
 #pragma unroll
     for (uint32_t t = 0; t < kGvWords; ++t) {                     // unrolled: w stays in registers
-        Fp v;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v.v[j] = __builtin_bswap32(src[8 * t + 7 - j]);
-        canonical = canonical && gv_below_modulus<FqCfg>(v);
+        const Fp v = load_be32(blob + 32 * t);
+        canonical = canonical && below_modulus<FqCfg>(v);
         w[t] = Fq::to_mont(v);
     }
     Affine a, c;
@@ -63,9 +61,9 @@ __global__ __launch_bounds__(kGvBlock) void g16v_decode_kernel(const uint8_t* __
     if (!canonical) st = GV_NOT_CANONICAL;
     else {
         const bool b_inf = fq2w_is_zero(b.x) && fq2w_is_zero(b.y);
-        if (!affine_is_inf(a) && !gv_g1_on_curve(a)) st = GV_OFF_CURVE;
-        else if (!affine_is_inf(c) && !gv_g1_on_curve(c)) st = GV_OFF_CURVE;
-        else if (!b_inf && !gv_g2_on_twist(b)) st = GV_OFF_CURVE;
+        if (!affine_is_inf(a) && !g1_on_curve(a)) st = GV_OFF_CURVE;
+        else if (!affine_is_inf(c) && !g1_on_curve(c)) st = GV_OFF_CURVE;
+        else if (!b_inf && !g2_on_twist(b)) st = GV_OFF_CURVE;
     }
     if (st != GV_OK) {
         a.x = Fq::zero(); a.y = a.x; c = a;
@@ -83,25 +81,14 @@ __global__ __launch_bounds__(kGvBlock) void g16v_subgroup_kernel(Affine* __restr
     const uint32_t i = blockIdx.x * kGvBlock + threadIdx.x;
     if (i >= m) return;                                            // no barrier and no cross-lane move below
     uint32_t st = status[i];
-    if (st == GV_OK) {
-        const G2P base = g2p_from_affine(pb[i]);
-        if (!base.inf) {
-            G2P acc = g2p_inf();
-#pragma unroll 1
-            for (int k = 253; k >= 0; --k) {
-                g2p_dbl(acc);
-                if ((FrCfg::M[k >> 5] >> (k & 31)) & 1) g2p_add(acc, base);
-            }
-            if (!acc.inf) st = GV_NOT_IN_SUBGROUP;
-        }
-        if (st != GV_OK) {
-            Affine z;
-            z.x = Fq::zero(); z.y = z.x;
-            G2Affine z2;
-            z2.x = fq2w_zero(); z2.y = z2.x;
-            pa[i] = z; pc[i] = z; pb[i] = z2;
-            status[i] = (uint8_t)st;
-        }
+    if (st == GV_OK && !g2_in_subgroup(g2p_from_affine(pb[i]))) {
+        st = GV_NOT_IN_SUBGROUP;
+        Affine z;
+        z.x = Fq::zero(); z.y = z.x;
+        G2Affine z2;
+        z2.x = fq2w_zero(); z2.y = z2.x;
+        pa[i] = z; pc[i] = z; pb[i] = z2;
+        status[i] = (uint8_t)st;
     }
     wm[i] = st == GV_OK ? rho[i] : Fr::zero();
 #endif
@@ -130,20 +117,7 @@ __global__ __launch_bounds__(kGvBlock) void g16v_amul_kernel(const Affine* __res
     if (i > m) return;
     const Affine p = i < m ? pa[i] : alpha;
     const Fp s = Fr::from_mont(i < m ? wm[i] : t[0]);              // canonical: below r < 2^254
-    XYZZ acc = xyzz_inf();
-#pragma unroll 1
-    for (int k = 253; k >= 0; --k) {
-        acc = xyzz_dbl(acc);
-        if ((s.v[k >> 5] >> (k & 31)) & 1) xyzz_madd(acc, p, false);
-    }
-    Affine r;
-    r.x = Fq::zero(); r.y = r.x;
-    if (!xyzz_is_inf(acc)) {
-        const Fp inv = gv_fq_inv(Fq::mul(acc.zz, acc.zzz));
-        r.x = Fq::mul(acc.x, Fq::mul(inv, acc.zzz));               // X / ZZ
-        r.y = Fq::mul(acc.y, Fq::mul(inv, acc.zz));                // Y / ZZZ
-    }
-    out[i] = r;
+    out[i] = xyzz_to_affine_lane(g1_mul_lane(p, s));
 }
 
 // ---- keys ---------------------------------------------------------------------------------------------------------------------
@@ -155,9 +129,8 @@ struct GvEntry {
 };
 static HandleTable<GvEntry> g_gv(6ull << 59);
 
-static bool gv_lookup(uint64_t h, GvEntry* out) { return g_gv.get(h, out); }
 // frees the key's device memory; the calling thread's current device is left as it was
-static void gv_free(const GvEntry& e) {
+static void g16v_key_free(const GvEntry& e) {
     DeviceGuard on(e.device);
     if (e.d_ic) (void)hipFree(e.d_ic);
 }
@@ -181,7 +154,7 @@ int g16v_key_create(Ctx& c, const uzk_g16_vk_desc* d, uint64_t* out) {
     if (err == hipSuccess) err = hipStreamSynchronize(c.stream);  // the caller's array may go away
     if (err != hipSuccess) {
         (void)hipGetLastError();
-        gv_free(e);
+        g16v_key_free(e);
         set_error("uzk_g16_vk_create: %s", hipGetErrorString(err));
         return UZK_ERR_DEVICE;
     }
@@ -191,7 +164,7 @@ int g16v_key_create(Ctx& c, const uzk_g16_vk_desc* d, uint64_t* out) {
 
 bool g16v_key_known(uint64_t h, uint32_t* n_inputs, int* device) {
     GvEntry e;
-    if (!gv_lookup(h, &e)) return false;
+    if (!g_gv.get(h, &e)) return false;
     if (n_inputs) *n_inputs = e.n_inputs;
     if (device) *device = e.device;
     return true;
@@ -201,11 +174,11 @@ bool g16v_key_known(uint64_t h, uint32_t* n_inputs, int* device) {
 int g16v_key_release(uint64_t h) {
     GvEntry e;
     if (!g_gv.take(h, &e)) { set_error("uzk_g16_vk_release: unknown verifying key %llu", (unsigned long long)h); return UZK_ERR_PARAMETER; }
-    gv_free(e);
+    g16v_key_free(e);
     return UZK_OK;
 }
 
-void g16v_release_all() { g_gv.drain(gv_free); }
+void g16v_release_all() { g_gv.drain(g16v_key_free); }
 
 // ---- the fold -----------------------------------------------------------------------------------------------------------------
 // The G1 arguments of the last three pairs: -(t_0 alpha) from the scalar multiplications' array, -X and -C from the MSMs' Jacobian sums
@@ -219,12 +192,8 @@ __global__ __launch_bounds__(kGvBlock) void g16v_tail_kernel(const Affine* alpha
     if (t == 0) {
         if (!affine_is_inf(*alpha_w)) { r.x = alpha_w->x; r.y = Fq::neg(alpha_w->y); }
     } else {
-        const Jac j = xc[t - 1];
-        if (!Fq::is_zero(j.z)) {
-            const Fp zi = gv_fq_inv(j.z), zi2 = Fq::sqr(zi);
-            r.x = Fq::mul(j.x, zi2);
-            r.y = Fq::neg(Fq::mul(j.y, Fq::mul(zi2, zi)));
-        }
+        r = jac_to_affine_lane(xc[t - 1]);
+        r.y = Fq::neg(r.y);                                        // 0 stays 0
     }
     out[t] = r;
 }
@@ -268,7 +237,7 @@ static int g16v_fold_impl(Ctx& c, uint64_t h, const uint8_t* proofs, const Fp* p
                           Jac* alpha_out, Jac* x_out, Jac* c_out, uint8_t* status_out, GvKeep* keep) {
     GvEntry e;
     const char* who = keep ? keep->who : "uzk_g16_verify_fold";
-    if (!gv_lookup(h, &e)) { set_error("%s: unknown verifying key %llu", who, (unsigned long long)h); return UZK_ERR_PARAMETER; }
+    if (!g_gv.get(h, &e)) { set_error("%s: unknown verifying key %llu", who, (unsigned long long)h); return UZK_ERR_PARAMETER; }
     if (e.device != c.device) { set_error("%s: the key lives on device %d, the calling context on device %d", who, e.device, c.device); return UZK_ERR_PARAMETER; }
     const uint32_t n_pub = e.n_inputs - 1;
     WsCarver cv;

@@ -27,6 +27,7 @@
 #include "ctx.hpp"
 #include "ec29l.hpp"
 #include "host_math.hpp"
+#include "lane_tools.hpp"
 
 namespace uzk {
 
@@ -184,18 +185,8 @@ __global__ __launch_bounds__(kG1Block) void g1ntt_scale_kernel(P29* __restrict__
 #endif
 }
 
-// a^(p-2) in the wire's arithmetic (one per run of kAffineRun points)
-__device__ inline Fp g1ntt_fq_inv(const Fp& a) {
-    const uint32_t e[8] = {0xd87cfd45u, 0x3c208c16u, 0x6871ca8du, 0x97816a91u, 0x8181585du, 0xb85045b6u, 0xe131a029u, 0x30644e72u};
-    Fp acc = Fq::one();
-    for (int i = 253; i >= 0; --i) {
-        acc = Fq::sqr(acc);
-        if ((e[i >> 5] >> (i & 31)) & 1) acc = Fq::mul(acc, a);
-    }
-    return acc;
-}
-
-// x = X / ZZ, y = Y / ZZZ with 1 / ZZ = (ZZ / ZZZ)^2 (ZZ^3 = ZZZ^2): one inversion of the product of the run's ZZZ.
+// x = X / ZZ, y = Y / ZZZ with 1 / ZZ = (ZZ / ZZZ)^2 (ZZ^3 = ZZZ^2): one inversion of the product of the run's ZZZ, in the wire's
+// arithmetic (lane_tools.hpp; one per run of kAffineRun points).
 // prefix[i]: the product of the ZZZ of the run's points before i (infinity contributes 1).
 __global__ __launch_bounds__(64) void g1ntt_affine_kernel(const P29* __restrict__ work, Fp* __restrict__ prefix, Affine* __restrict__ out, uint32_t n) {
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
@@ -208,7 +199,7 @@ __global__ __launch_bounds__(64) void g1ntt_affine_kernel(const P29* __restrict_
         const P29 p = work[i];
         if (!p29_is_inf(p)) prod = Fq::mul(prod, p29_store(p).zzz);
     }
-    Fp inv = g1ntt_fq_inv(prod);
+    Fp inv = fq_inv_lane(prod);
     for (uint32_t i = hi; i-- > (uint32_t)lo;) {
         const P29 p = work[i];
         Affine a;

@@ -22,7 +22,7 @@
 #include <cstring>
 
 #include "ctx.hpp"
-#include "curvecheck.hpp"
+#include "lane_tools.hpp"
 #include "g2_29.hpp"
 #include "handles.hpp"
 #include "host_g2.hpp"
@@ -218,7 +218,7 @@ __device__ inline Fq2w g2w_mul(const Fq2w& a, const Fq2w& b) {
 }
 // 1 / (a + b u) = (a - b u) / (a^2 + b^2); a + b u != 0 (-1 is no square in Fq: the norm of a nonzero element is nonzero)
 __device__ inline Fq2w g2w_inv(const Fq2w& a) {
-    const Fp ni = gv_fq_inv(Fq::add(Fq::sqr(a.c0), Fq::sqr(a.c1)));
+    const Fp ni = fq_inv_lane(Fq::add(Fq::sqr(a.c0), Fq::sqr(a.c1)));
     Fq2w r;
     r.c0 = Fq::mul(a.c0, ni);
     r.c1 = Fq::neg(Fq::mul(a.c1, ni));

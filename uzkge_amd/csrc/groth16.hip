@@ -20,12 +20,12 @@
 #include <cstring>
 
 #include "ctx.hpp"
-#include "curvecheck.hpp"
 #include "g2_29.hpp"
 #include "handles.hpp"
 #include "host_ec64.hpp"
 #include "host_g2.hpp"
 #include "host_math.hpp"
+#include "lane_tools.hpp"
 
 namespace uzk {
 
@@ -131,30 +131,13 @@ __global__ __launch_bounds__(256) void g16_scalar_rows_kernel(const Fp* __restri
 
 // ---- the finish on the device: C = s A + r B1 + K, the affine maps, the blob ---------------------------------------------------------
 // One lane per (term, proof): lane t < nb is s_t A_t, lane nb + t is r_t B1_t, by double-and-add over the 254 bits of the canonical
-// scalar (g16v_amul's chain; the base is a Jacobian sum with Z != 1, so the addition is the full one).  No barrier.
+// scalar (g1_mul_lane of lane_tools.hpp; the base is a Jacobian sum with Z != 1, so the addition is the full one).  No barrier.
 __global__ __launch_bounds__(kFinBlock) void g16_chains_kernel(const Jac* __restrict__ sums, const Fp* __restrict__ rs, XYZZ* __restrict__ terms, uint32_t nb) {
     const uint32_t t = blockIdx.x * kFinBlock + threadIdx.x;
     if (t >= 2 * nb) return;
     const XYZZ p = xyzz_from_jac(sums[t]);                         // A then B1
     const Fp s = Fr::from_mont(t < nb ? rs[nb + t] : rs[t - nb]);  // s for A, r for B1; canonical: below r < 2^254
-    XYZZ acc = xyzz_inf();
-#pragma unroll 1
-    for (int k = 253; k >= 0; --k) {
-        acc = xyzz_dbl(acc);
-        if ((s.v[k >> 5] >> (k & 31)) & 1) xyzz_add(acc, p);
-    }
-    terms[t] = acc;
-}
-
-__device__ inline Affine g16_affine_of(const XYZZ& p) {
-    Affine r;
-    r.x = Fq::zero(); r.y = r.x;
-    if (!xyzz_is_inf(p)) {
-        const Fp inv = gv_fq_inv(Fq::mul(p.zz, p.zzz));
-        r.x = Fq::mul(p.x, Fq::mul(inv, p.zzz));                   // X / ZZ
-        r.y = Fq::mul(p.y, Fq::mul(inv, p.zz));                    // Y / ZZZ
-    }
-    return r;
+    terms[t] = g1_mul_lane(p, s);
 }
 
 // One lane per (point, proof): lane t < nb writes the affine A_t; lane nb + t adds s A + r B1 + K by general additions (the two terms
@@ -163,12 +146,12 @@ __global__ __launch_bounds__(kFinBlock) void g16_combine_kernel(const Jac* __res
                                                                  Affine* __restrict__ c_out, uint32_t nb) {
     const uint32_t t = blockIdx.x * kFinBlock + threadIdx.x;
     if (t >= 2 * nb) return;
-    if (t < nb) { a_out[t] = g16_affine_of(xyzz_from_jac(sums[t])); return; }
+    if (t < nb) { a_out[t] = xyzz_to_affine_lane(xyzz_from_jac(sums[t])); return; }
     const uint32_t b = t - nb;
     XYZZ acc = terms[b];
     xyzz_add(acc, terms[nb + b]);
     xyzz_add(acc, xyzz_from_jac(sums[2 * (size_t)nb + b]));
-    c_out[b] = g16_affine_of(acc);
+    c_out[b] = xyzz_to_affine_lane(acc);
 }
 
 // One lane per (proof, word): word t of the blob (a.x, a.y, b.x.c1, b.x.c0, b.y.c1, b.y.c0, c.x, c.y) as the canonical integer in 32
@@ -183,10 +166,7 @@ __global__ __launch_bounds__(kFinBlock) void g16_encode_kernel(const Affine* __r
                : slot < 6 ? reinterpret_cast<const Fp*>(pb)[(size_t)b * 4 + slot - 2]
                           : reinterpret_cast<const Fp*>(pc)[(size_t)b * 2 + slot - 6];
     proofs[(size_t)b * 8 + slot] = v;
-    const Fp e = Fq::from_mont(v);
-    uint32_t* dst = reinterpret_cast<uint32_t*>(blobs + (size_t)b * UZK_G16_PROOF_BYTES + 32 * t);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) dst[j] = __builtin_bswap32(e.v[7 - j]);
+    store_be32(blobs + (size_t)b * UZK_G16_PROOF_BYTES + 32 * t, Fq::from_mont(v));
 }
 
 // ---- keys -------------------------------------------------------------------------------------------------------------------

@@ -49,6 +49,7 @@
 #include "ec29l.hpp"
 #include "host_ec64.hpp"
 #include "host_math.hpp"
+#include "lane_tools.hpp"
 #include "msm_cut.hpp"
 
 namespace uzk {
@@ -1740,16 +1741,6 @@ __global__ __launch_bounds__(MAXT) void msm_small_reduce_kernel(XYZZ* __restrict
 }
 
 // ---- precomputation: T[j][i] = 2^c * T[j-1][i], affine --------------------------------------------
-__device__ inline Fp fq_inv_pow(const Fp& a) {   // a^(p-2)
-    const uint32_t e[8] = {0xd87cfd45u, 0x3c208c16u, 0x6871ca8du, 0x97816a91u,
-                           0x8181585du, 0xb85045b6u, 0xe131a029u, 0x30644e72u};
-    Fp acc = Fq::one();
-    for (int i = 253; i >= 0; --i) {
-        acc = Fq::sqr(acc);
-        if ((e[i >> 5] >> (i & 31)) & 1) acc = Fq::mul(acc, a);
-    }
-    return acc;
-}
 constexpr int kPreRun = 16;   // points normalised per lane with one inversion (Montgomery's trick)
 __global__ __launch_bounds__(64) void msm_precompute_kernel(const Affine* __restrict__ prev, Affine* __restrict__ out,
                                                             Fp* __restrict__ tmp_z, Fp* __restrict__ tmp_p, uint32_t n,
@@ -1776,16 +1767,7 @@ __global__ __launch_bounds__(64) void msm_precompute_kernel(const Affine* __rest
         tmp_p[i] = prod;
         prod = Fq::mul(prod, z);
     }
-    Fp inv = fq_inv_pow(prod);
-    for (uint32_t i = hi; i-- > lo;) {
-        Fp zi = Fq::mul(inv, tmp_p[i]);
-        inv = Fq::mul(inv, tmp_z[i]);
-        Fp zi2 = Fq::sqr(zi);
-        Affine xy = out[i];
-        xy.x = Fq::mul(xy.x, zi2);
-        xy.y = Fq::mul(xy.y, Fq::mul(zi2, zi));
-        out[i] = xy;
-    }
+    normalise_run(out, tmp_z, tmp_p, lo, hi, prod);
 }
 
 // The same table for a small SRS in ONE launch: lane i walks point i through all W - 1 levels (c doublings each),
@@ -1810,17 +1792,7 @@ __global__ __launch_bounds__(64) void msm_precompute_column_kernel(Affine* __res
         tmp_p[at] = prod;                                // product of the z's of the earlier levels
         prod = Fq::mul(prod, z);
     }
-    Fp inv = fq_inv_pow(prod);
-    for (uint32_t j = W - 1; j >= 1; --j) {
-        const size_t at = (size_t)j * n + i;
-        const Fp zi = Fq::mul(inv, tmp_p[at]);           // 1 / z_j
-        inv = Fq::mul(inv, tmp_z[at]);
-        const Fp zi2 = Fq::sqr(zi);
-        Affine xy = table[at];
-        xy.x = Fq::mul(xy.x, zi2);
-        xy.y = Fq::mul(xy.y, Fq::mul(zi2, zi));
-        table[at] = xy;
-    }
+    normalise_run(table + i, tmp_z + i, tmp_p + i, 1u, W, prod, n);      // levels 1 .. W - 1 of column i, n apart
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -1,7 +1,7 @@
 // The pairing product on the device: prod_i e(P_i, Q_i) over BN254 by the optimal ate pairing, bit for bit the element of
 // oracle/bn254_pairing.py (whose Python-integer restatement of THIS algorithm is tests/pairing_ref.py).
 //
-//   pairing_check    one lane per pair: every coordinate against p, P on y^2 = x^3 + 3, Q on the twist (curvecheck.hpp, the checks of
+//   pairing_check    one lane per pair: every coordinate against p, P on y^2 = x^3 + 3, Q on the twist (lane_tools.hpp, the checks of
 //                    g16v_decode); a status byte per pair.  Subgroup membership of Q is the caller's business.
 //   pairing_miller   one pair per group of eight lanes, eight pairs per workgroup of one wave (fq12_29.hpp: lane k of a group holds the
 //                    coefficient of w^k of f).  The loop runs over the 65 bits of 6 x + 2 in plain binary (64 doublings, 36
@@ -21,10 +21,10 @@
 
 #include "../../include/uzkge_gpu_test.h"
 #include "ctx.hpp"
-#include "curvecheck.hpp"
 #include "fq12_29.hpp"
 #include "handles.hpp"
 #include "host_g2.hpp"
+#include "lane_tools.hpp"
 
 namespace uzk {
 
@@ -43,10 +43,10 @@ __global__ __launch_bounds__(kPairBlock) void pairing_check_kernel(const Affine*
     const Affine a = p[i];
     const G2Affine b = q[i];
     uint32_t st = PC_OK;
-    if (!(gv_below_modulus<FqCfg>(a.x) && gv_below_modulus<FqCfg>(a.y) && gv_below_modulus<FqCfg>(b.x.c0) && gv_below_modulus<FqCfg>(b.x.c1) &&
-          gv_below_modulus<FqCfg>(b.y.c0) && gv_below_modulus<FqCfg>(b.y.c1))) st = PC_NOT_CANONICAL;
-    else if (!affine_is_inf(a) && !gv_g1_on_curve(a)) st = PC_OFF_CURVE;
-    else if (!(fq2w_is_zero(b.x) && fq2w_is_zero(b.y)) && !gv_g2_on_twist(b)) st = PC_OFF_CURVE;
+    if (!(below_modulus<FqCfg>(a.x) && below_modulus<FqCfg>(a.y) && below_modulus<FqCfg>(b.x.c0) && below_modulus<FqCfg>(b.x.c1) &&
+          below_modulus<FqCfg>(b.y.c0) && below_modulus<FqCfg>(b.y.c1))) st = PC_NOT_CANONICAL;
+    else if (!affine_is_inf(a) && !g1_on_curve(a)) st = PC_OFF_CURVE;
+    else if (!(fq2w_is_zero(b.x) && fq2w_is_zero(b.y)) && !g2_on_twist(b)) st = PC_OFF_CURVE;
     status[i] = (uint8_t)st;
 #endif
 }

@@ -14,6 +14,7 @@
 
 #include "ctx.hpp"
 #include "keccak.hpp"
+#include "lane_tools.hpp"
 
 namespace uzk {
 
@@ -24,20 +25,13 @@ constexpr uint64_t kSrsNone = ~0ull;
 // what one workgroup found; first_bad relative to the array the kernel was given
 struct SrsCurveRecord { uint64_t first_bad, infinity, non_canonical, off_curve; };
 
-UZK_HD bool srs_below_p(const Fp& a) {
-    uint64_t br = 0;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) { const uint64_t t = (uint64_t)a.v[i] - FqCfg::M[i] - br; br = (t >> 32) & 1; }
-    return br != 0;
-}
-
 enum { SRS_GOOD = 0, SRS_INF = 1, SRS_NON_CANONICAL = 2, SRS_OFF_CURVE = 3 };
 UZK_HD int srs_classify(const Affine& p) {
     if (affine_is_inf(p)) return SRS_INF;
-    if (!srs_below_p(p.x) || !srs_below_p(p.y)) return SRS_NON_CANONICAL;
+    if (!below_modulus<FqCfg>(p.x) || !below_modulus<FqCfg>(p.y)) return SRS_NON_CANONICAL;
     const Fp one = Fq::one();
-    const Fp three = Fq::add_portable(Fq::add_portable(one, one), one);   // a constant: plain C++, folded at compile time
-    const Fp rhs = Fq::add(Fq::mul(Fq::sqr(p.x), p.x), three);
+    const Fp three = Fq::add_portable(Fq::add_portable(one, one), one);   // g1_b() in plain C++: folded at compile time, which this
+    const Fp rhs = g1_rhs(p.x, three);                                     // kernel's 64 registers (occupancy 8) depend on
     return Fq::eq(Fq::sqr(p.y), rhs) ? SRS_GOOD : SRS_OFF_CURVE;
 }
 

@@ -5,6 +5,7 @@
 //   synth_points_arith   P_i = (i+1) * Q: known discrete logs => closed-form MSM check at any size
 #include "ctx.hpp"
 #include "host_math.hpp"
+#include "lane_tools.hpp"
 
 namespace uzk {
 
@@ -50,27 +51,14 @@ __global__ __launch_bounds__(256) void synth_scalars_mix_kernel(Fp* __restrict__
     out[i] = r;
 }
 
-// a^((p+1)/4) for the BN254 base field (p = 3 mod 4): square root candidate
-__device__ inline Fp fq_sqrt_candidate(const Fp& a) {
-    // (p+1)/4, little-endian 32-bit words
-    const uint32_t e[8] = {0xb61f3f52u, 0x4f082305u, 0x5a1c72a3u, 0x65e05aa4u,
-                           0xa0605617u, 0x6e14116du, 0xb84c680au, 0x0c19139cu};
-    Fp acc = Fq::one();
-    for (int i = 253; i >= 0; --i) {
-        acc = Fq::sqr(acc);
-        if ((e[i >> 5] >> (i & 31)) & 1) acc = Fq::mul(acc, a);
-    }
-    return acc;
-}
-
 __global__ __launch_bounds__(256) void synth_points_random_kernel(Affine* __restrict__ out, uint64_t n, uint64_t seed) {
     uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    Fp three = Fq::add(Fq::one(), Fq::add(Fq::one(), Fq::one()));
+    const Fp b = g1_b();
     Affine p;
     for (uint64_t attempt = 0;; ++attempt) {
         Fp x = random_fe<Fq>(seed ^ 0xA5A5A5A5DEADBEEFull, i * 64 + attempt);
-        Fp rhs = Fq::add(Fq::mul(Fq::sqr(x), x), three);
+        Fp rhs = g1_rhs(x, b);
         Fp y = fq_sqrt_candidate(rhs);
         if (Fq::eq(Fq::sqr(y), rhs) && !(Fq::is_zero(x) && Fq::is_zero(y))) {
             if (splitmix64(seed + i) & 1) y = Fq::neg(y);
@@ -85,18 +73,6 @@ __global__ __launch_bounds__(256) void synth_points_random_kernel(Affine* __rest
 // Thread t produces points (t*L + 1 .. t*L + L) * Q in Jacobian-like form (X*ZZ, Y*ZZZ, ZZ),
 // then normalises its run with one inversion (Montgomery's trick).
 constexpr int kArithRun = 64;
-
-__device__ inline Fp fq_inv_device(const Fp& a) {
-    // a^(p-2)
-    const uint32_t e[8] = {0xd87cfd45u, 0x3c208c16u, 0x6871ca8du, 0x97816a91u,
-                           0x8181585du, 0xb85045b6u, 0xe131a029u, 0x30644e72u};
-    Fp acc = Fq::one();
-    for (int i = 253; i >= 0; --i) {
-        acc = Fq::sqr(acc);
-        if ((e[i >> 5] >> (i & 31)) & 1) acc = Fq::mul(acc, a);
-    }
-    return acc;
-}
 
 __global__ __launch_bounds__(64) void synth_points_arith_kernel(Affine* __restrict__ out, Fp* __restrict__ tmp_z,
                                                                  Fp* __restrict__ tmp_p, uint64_t n, Affine q) {
@@ -123,16 +99,7 @@ __global__ __launch_bounds__(64) void synth_points_arith_kernel(Affine* __restri
         prod = Fq::mul(prod, acc.zz);
         xyzz_madd(acc, q, false);
     }
-    Fp inv = fq_inv_device(prod);
-    for (uint64_t j = hi; j-- > lo;) {
-        Fp zi = Fq::mul(inv, tmp_p[j]);      // 1 / z_j
-        inv = Fq::mul(inv, tmp_z[j]);
-        Fp zi2 = Fq::sqr(zi);
-        Affine xy = out[j];
-        xy.x = Fq::mul(xy.x, zi2);
-        xy.y = Fq::mul(xy.y, Fq::mul(zi2, zi));
-        out[j] = xy;
-    }
+    normalise_run(out, tmp_z, tmp_p, lo, hi, prod);
 }
 
 int synth_scalars(Ctx& c, Fp* d_scalars, size_t n, uint64_t seed) {

@@ -23,6 +23,7 @@
 #include "handles.hpp"
 #include "host_math.hpp"
 #include "keccak.hpp"
+#include "lane_tools.hpp"
 
 namespace uzk {
 
@@ -84,12 +85,6 @@ UZK_HD void vf_be_lanes(const Fp& c, uint64_t (&l)[4]) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) l[j] = vf_bswap(((uint64_t)c.v[7 - 2 * j] << 32) | c.v[6 - 2 * j]);
 }
-template <class C>
-UZK_HD bool vf_below_modulus(const Fp& a) {
-    uint64_t br = 0;
-    for (int i = 0; i < 8; ++i) { const uint64_t t = (uint64_t)a.v[i] - C::M[i] - br; br = (t >> 32) & 1; }
-    return br != 0;
-}
 
 // ---- decode and check ---------------------------------------------------------------------------------------------------------
 // One workgroup per proof, one thread per word.  flag: 1 = word >= its modulus; the point threads then add 2 = not on the curve.
@@ -103,12 +98,9 @@ __global__ __launch_bounds__(kVfBlock) void vf_decode_kernel(const uint8_t* __re
     Fp* row = words + (size_t)i * kVfWords;
     uint32_t f = 0;
     if (t < (uint32_t)L.n_words) {
-        const uint32_t* src = reinterpret_cast<const uint32_t*>(proofs + (size_t)i * proof_bytes + 32u * t);
-        Fp v;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v.v[j] = __builtin_bswap32(src[7 - j]);
+        const Fp v = load_be32(proofs + (size_t)i * proof_bytes + 32u * t);
         const bool coord = t < (uint32_t)L.prk3 || t >= (uint32_t)L.open0;
-        f = (coord ? vf_below_modulus<FqCfg>(v) : vf_below_modulus<FrCfg>(v)) ? 0u : 1u;
+        f = (coord ? below_modulus<FqCfg>(v) : below_modulus<FrCfg>(v)) ? 0u : 1u;
         row[t] = coord ? Fq::to_mont(v) : Fr::to_mont(v);
     }
     flag[t] = f;
@@ -122,12 +114,7 @@ __global__ __launch_bounds__(kVfBlock) void vf_decode_kernel(const uint8_t* __re
     uint32_t g = 0;
     if (is_point) {
         p.x = row[pw]; p.y = row[pw + 1];
-        if (!(flag[pw] | flag[pw + 1]) && !affine_is_inf(p)) {
-            const Fp one = Fq::one();
-            const Fp three = Fq::add(Fq::add(one, one), one);
-            const Fp rhs = Fq::add(Fq::mul(Fq::sqr(p.x), p.x), three);
-            if (!Fq::eq(Fq::sqr(p.y), rhs)) g = 2;
-        }
+        if (!(flag[pw] | flag[pw + 1]) && !affine_is_inf(p) && !g1_on_curve(p)) g = 2;
     }
     __syncthreads();
     flag[t] |= g;
@@ -377,16 +364,6 @@ __global__ __launch_bounds__(kVfBlock) void vf_keccak_kernel(const uint8_t* __re
 }
 
 // ---- verifier scalars ---------------------------------------------------------------------------------------------------------
-__device__ inline Fp vf_fr_inv(const Fp& a) {                     // a^(r - 2)
-    const uint32_t e[8] = {0xefffffffu, 0x43e1f593u, 0x79b97091u, 0x2833e848u, 0x8181585du, 0xb85045b6u, 0xe131a029u, 0x30644e72u};
-    Fp acc = Fr::one();
-#pragma unroll 1
-    for (int i = 253; i >= 0; --i) {
-        acc = Fr::sqr(acc);
-        if ((e[i >> 5] >> (i & 31)) & 1) acc = Fr::mul(acc, a);
-    }
-    return acc;
-}
 __device__ __forceinline__ Fp vf_pow5(const Fp& a) { const Fp a2 = Fr::sqr(a); return Fr::mul(Fr::sqr(a2), a); }
 
 // One lane per proof.  Outputs, every one already times the proof's weight rho:
@@ -431,7 +408,7 @@ __global__ __launch_bounds__(kVfBlock) void vf_scalars_kernel(const VfKey* __res
         pre[j] = prod;
         prod = Fr::mul(prod, d);
     }
-    Fp inv = vf_fr_inv(prod);
+    Fp inv = fr_inv_lane(prod);
     Fp acc = Fr::zero();
 #pragma unroll 1
     for (uint32_t j = n_pi; j >= 1; --j) {
